@@ -16,15 +16,28 @@ bit-exact with the CPU oracle, distribution-checked against the PCG mode); the n
 the reference itself (kernel k_step) is measured in the same run and reported under "alt_rng", and the 1024-episode batch
 (configs[1], the per-GPU share of an 8-GPU job) under "envs_1024".
 
-Timing: W untimed warm-up steps, then regions of EXACTLY K steps, each bracketed by barrier + device synchronise on
-both sides, repeated back to back (the episodes keep running across regions) until at least --min-seconds of timed
-work has accumulated, so that a small K still averages over whole episodes including their scenario regenerations.
-Region time = MAX over ranks.  `value` = steps of all regions / sum of the region times; the median region is
-reported beside it.
+Timing: W untimed warm-up steps, then ONE timed region of EXACTLY K steps, bracketed by barrier + device synchronise on
+both sides: K is the number of timed steps, and `ms_per_step` = region time / K.  --min-seconds S > 0 repeats the region
+back to back (the episodes keep running across regions) until at least S seconds of timed work have accumulated, so that
+a small K averages over whole episodes including their scenario regenerations; the number of steps run then depends on
+the timing.  Region time = MAX over ranks.  `value` = steps of all regions / sum of the region times; the median region
+is reported beside it.
 
 Prints ONE JSON line on rank 0.  `roofline` = algorithmic bytes per k_step launch / mean launch duration from HIP
-events recorded on the launch stream inside the timed regions; `cpu_baseline` = the CPU oracle (kind "port": the
-host build of the same restatement) on a bounded sample of the same workload, rank 0, N=1 only.
+events recorded on the launch stream inside the timed regions, beside the committed counter figures of that kernel.
+
+A plain run measures the headline only.  --full adds what takes runs of its own: the other RNG mode ("alt_rng"), the
+1024-episode batch ("envs_1024"), the uniform topology, the learner loops ("policy_in_loop"), the exchange on a one-rank
+communicator, the weak-scaled leg of an N>1 job, the host-API rates and `cpu_baseline` (the CPU oracle, kind "port": the
+host build of the same restatement, on a bounded sample of the same workload, rank 0, N=1 only); --no-alt and
+--no-cpu-baseline drop parts of it.  The sub-entries of --full time regions of K steps for 0.2-1 s each (a fifth or a
+half of --min-seconds, 2 s when that is 0).
+
+--dump-outputs DIR writes what the timed path computed in its last step, after the timed region: the observations,
+rewards, done flags and engine error flags a caller fetches (cc4_fetch) and the blue actions that step consumed (drawn
+in the kernel), for rank 0's episodes, as DIR/<name>.npy in float32 / float64 (64 MB at most: above that, a fixed seeded
+sample of the episodes, whose indices are in episode_index.npy).  The inputs are fixed by the arguments (seeds, action
+key, step counts), so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -245,6 +258,34 @@ def load_valu_issue(envs, kernel, steps_per_launch):
         return None
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, env):
+    """--dump-outputs: what the last step of the timed path left for its caller, as float32 / float64 .npy files (see the module
+    docstring).  A batch whose arrays pass DUMP_MAX_BYTES is written as a fixed seeded sample of its episodes."""
+    import numpy as np
+    arrays = {'observations': env._obs.astype(np.float32), 'rewards': env._rew.astype(np.float32),
+              'dones': env._done.astype(np.float32), 'error_flags': env._err.astype(np.float64),
+              'actions': env.device_actions().astype(np.float32)}
+    n = env.num_envs
+    per_env = sum(a.nbytes for a in arrays.values()) / n
+    budget = DUMP_MAX_BYTES - 4096                              # (room for the .npy headers)
+    if per_env * n > budget:
+        keep = int((budget - 8 * n) // per_env)                  # (and for the index file)
+        idx = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+        arrays = {k: v[idx] for k, v in arrays.items()}
+        arrays['episode_index'] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), np.ascontiguousarray(a))
+
+
+def full_seconds(args):
+    """The timed work the sub-entries of --full take their shares of: --min-seconds, or 2 s when the headline is one region."""
+    return args.min_seconds if args.min_seconds > 0 else 2.0
+
+
 def cpu_model():
     try:
         for line in open('/proc/cpuinfo'):
@@ -265,7 +306,7 @@ def exchange_world1(make_env, measure, D, args, lo, timeout_s=90.0):
     import numpy as np
     from cage_challenge_4_amd import RNG_PHILOX
     out, box = {}, {}
-    sub_seconds = max(0.2, args.min_seconds / 5.0)
+    sub_seconds = max(0.2, full_seconds(args) / 5.0)
 
     def leg():
         try:
@@ -310,12 +351,18 @@ def main():
     ap.add_argument('--total-envs', type=int, default=TOTAL_ENVS)
     ap.add_argument('--envs-per-gpu', type=int, default=0, help='override: total = envs-per-gpu x gpus (weak-scaled run)')
     ap.add_argument('--episode-steps', type=int, default=500)
-    ap.add_argument('--min-seconds', type=float, default=2.0, help='timed regions of the headline are repeated until this much timed work has accumulated (the sub-entries take a fifth of it each, 0.2 s at least)')
+    ap.add_argument('--min-seconds', type=float, default=0.0, help='0 (default): ONE timed region of exactly --steps steps; more: the region is repeated until '
+                    'this much timed work has accumulated (the step count then depends on the timing).  The sub-entries of --full take a fifth of it each, '
+                    '0.2 s at least (of 2 s when this is 0)')
     ap.add_argument('--rng', choices=['pcg64', 'philox'], default='philox')
-    ap.add_argument('--no-alt', action='store_true', help='skip the sub-entries (other RNG mode, 1024 episodes, uniform topology)')
+    ap.add_argument('--full', action='store_true', help='also measure the sub-entries, the host-API rates and the CPU baseline (see the module docstring)')
+    ap.add_argument('--no-alt', action='store_true', help='with --full: skip the sub-entries (other RNG mode, 1024 episodes, uniform topology, ...) and the host-API rates')
     ap.add_argument('--seed0', type=int, default=1000)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write the last timed step\'s outputs to DIR/<name>.npy (float32 / float64)')
     args = ap.parse_args()
+    if args.dump_outputs and args.min_seconds > 0:
+        ap.error('--dump-outputs needs a fixed number of steps: leave --min-seconds at 0')
 
     from cage_challenge_4_amd import CC4VecEnv, RNG_PCG64, RNG_PHILOX
     from cage_challenge_4_amd import distributed as D
@@ -404,7 +451,7 @@ def main():
         out['run_kernel'] = run_kernel
         return out
 
-    sub_seconds = max(0.2, args.min_seconds / 5.0)      # the sub-entries' share of timed work
+    sub_seconds = max(0.2, full_seconds(args) / 5.0)      # the sub-entries' share of timed work
     main_res = measure(env, lo, total_envs)
     # what this rank's host did (cc4_host_stats): a multi-GPU curve is explained by these -- the slowest rank's kernel period, the
     # host time per step spent enqueueing launches and all-gathers, and whether an all-gather ever held a step up
@@ -425,9 +472,11 @@ def main():
         digest = plane.allreduce(digest, 'sum')
         err_any = digest[2] > 0
     mean_hosts = float(np.mean([int(env.topology(i)[27::2].sum()) for i in range(0, n_local, max(1, n_local // 64))]))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, env)
 
     subs = {}
-    if dist_on and not args.envs_per_gpu and not exchange_note and os.environ.get('CC4_BENCH_NO_WEAK') != '1':
+    if args.full and dist_on and not args.envs_per_gpu and not exchange_note and os.environ.get('CC4_BENCH_NO_WEAK') != '1':
         # The same job WEAK-scaled in the same run: the strong line above cuts BASELINE configs[3]'s 8192 episodes into world shares --
         # 1024 per GPU at 8 GPUs, the latency regime of this engine --; here every GPU keeps the full single-GPU batch (8192 per rank,
         # world x 8192 in total) with the exchange of every step's observations across all ranks, which is the efficient way to use N GPUs.
@@ -441,7 +490,7 @@ def main():
                 ew = make_env(per, mode, lo_w)
                 D.init_rccl(ew, rank, world, plane)
                 ew.reset(seeds=np.uint64(args.seed0) + np.arange(lo_w, lo_w + per, dtype=np.uint64))
-                rw = measure(ew, lo_w, per * world, min_seconds=max(0.2, args.min_seconds / 2.0))
+                rw = measure(ew, lo_w, per * world, min_seconds=max(0.2, full_seconds(args) / 2.0))
                 rw.update({'unit': 'agent-env steps/s', 'scaling': 'weak', 'envs_per_gpu': per, 'total_envs': per * world, 'kernel': ew.step_kernel,
                            'exchange_info': ew.exchange_info(), 'note': 'every rank keeps 8192 episodes; RCCL all-gather of every step\'s packed observations across all ranks'})
                 ew.close()
@@ -461,10 +510,10 @@ def main():
         os.dup2(saved_fd2, 1)
         os.close(saved_fd2)
         subs['weak_scaled'] = wbox.get('res') or {'skipped': 'the weak-scaled leg did not finish within its time limit on this rank', '_stalled': True}
-    if not args.no_alt and not dist_on:      # single-GPU runs also time the other RNG mode and the small batch
+    if args.full and not args.no_alt and not dist_on:      # single-GPU runs also time the other RNG mode and the small batch
         other = 'pcg64' if args.rng == 'philox' else 'philox'
         e2 = make_env(n_local, RNG_PCG64 if other == 'pcg64' else RNG_PHILOX, lo)
-        r2 = measure(e2, lo, total_envs, min_seconds=max(sub_seconds, args.min_seconds / 2.0))
+        r2 = measure(e2, lo, total_envs, min_seconds=max(sub_seconds, full_seconds(args) / 2.0))
         k2 = e2.step_kernel
         e2.close()
         r2.update({'rng': other, 'kernel': k2, 'unit': 'agent-env steps/s', 'total_envs': total_envs,
@@ -641,9 +690,9 @@ def main():
         }
         out['config']['per_rank'] = per_rank
         out.update(subs)
-        if not dist_on and not args.no_alt:
+        if args.full and not dist_on and not args.no_alt:
             out.update(host_api_rates())
-        if not dist_on and not args.no_cpu_baseline:
+        if args.full and not dist_on and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(4096, args.seed0)   # ~15 s of CPU work (16 cores x ~0.8 s + one core x ~1.5 s)
         print(json.dumps(out), flush=True)
     env.close()

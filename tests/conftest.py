@@ -4,6 +4,14 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+# The suite runs with the hardware-queue count libcc4 is built around (its own default, csrc/cc4_api.hip cc4_runtime_env), even where
+# the environment asks for fewer: a handle holds more streams than the runtime's default four queues, and a rollout's persistent kernel
+# waits for the policy passes enqueued on the policy streams -- a policy stream that shares the kernel's queue waits behind it until
+# the rollout's watchdog gives up.  Set before anything in this process initialises HIP; child processes of the tests inherit it.
+_hwq = os.environ.get('GPU_MAX_HW_QUEUES', '')
+if not _hwq.isdigit() or int(_hwq) < 16:
+    os.environ['GPU_MAX_HW_QUEUES'] = '16'
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 

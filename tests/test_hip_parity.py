@@ -1241,11 +1241,11 @@ def test_counter_mode_event_log_ports_do_not_change_the_trajectory(philox_kernel
 
 
 def test_bench_line_contract():
-    """`python bench.py --steps 20 --warmup 5` (what the driver runs, with its own K / W): ONE JSON line with the contract's keys,
+    """`python bench.py --steps 20 --warmup 5 --full` (the driver's K / W with every sub-entry): ONE JSON line with the contract's keys,
     BASELINE.json's metric on the 8192-episode configuration, `roofline` and `cpu_baseline` objects, consistent numbers."""
     import json, os, subprocess, sys
     from conftest import ROOT
-    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '20', '--warmup', '5', '--min-seconds', '0.05'],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '20', '--warmup', '5', '--min-seconds', '0.05', '--full'],
                          capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
@@ -1292,6 +1292,37 @@ def test_bench_line_contract():
     assert c['kind'] == 'port' and c['cores'] >= 1 and c['value'] > 0 and 'sample' in c and c['one_core']['cores'] == 1
     assert c['reference_python']['kind'] == 'reference' and c['reference_python']['value'] == 172.0
     assert d['alt_rng']['rng'] == 'pcg64' and d['envs_1024']['total_envs'] == 1024 and d['value'] > 50e6
+
+
+def test_plain_bench_times_exactly_k_steps_and_dumps_what_the_oracle_computes(tmp_path):
+    """`python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR` (a plain run): the headline alone, ONE timed region of exactly K
+    steps, and the outputs of the last step -- observations, rewards, dones, error flags, the actions the kernel drew -- equal to the CPU
+    oracle's after W + K steps of the same seeded workload (8192 episodes, counter mode, autoreset)."""
+    import json, os, subprocess, sys
+    from conftest import ROOT
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '20', '--warmup', '5', '--dump-outputs', str(tmp_path)],
+                         capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d['steps'] == 20 and d['warmup'] == 5 and d['config']['timed_regions'] == 1 and d['config']['steps_run'] == 25
+    assert d['higher_is_better'] is True and d['dtype'] == 'int32' and d['unit'] == 'agent-env steps/s' and d['value'] > 50e6
+    assert abs(d['value'] - 5.0 * 8192 / (d['ms_per_step'] * 1e-3)) < 1e-6 * d['value']
+    for k in ('cpu_baseline', 'alt_rng', 'envs_1024', 'uniform_topology', 'policy_in_loop', 'exchange_world1', 'single_env_facade', 'eval_sequential'):
+        assert k not in d, k                                # --full's entries
+    n, seed0 = 8192, 1000
+    got = {k: np.load(tmp_path / f'{k}.npy') for k in ('observations', 'rewards', 'dones', 'error_flags', 'actions')}
+    assert sorted(os.listdir(tmp_path)) == sorted(f'{k}.npy' for k in got)
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values()) and sum(v.nbytes for v in got.values()) <= 64 << 20
+    ora = OracleVecEnv(n, steps=500, rng_mode=1, autoreset=True)
+    ora.reset_batch(seed0)
+    for t in range(25):
+        a = random_actions(seed0, t, n)
+        o = ora.step_batch(a)
+    assert np.array_equal(got['observations'], o[0].astype(np.float32)) and np.array_equal(got['rewards'], o[1].astype(np.float32))
+    assert np.array_equal(got['dones'], o[2].astype(np.float32)) and np.array_equal(got['error_flags'], o[3]['err'].astype(np.float64))
+    assert np.array_equal(got['actions'], a.astype(np.float32))
 
 
 def test_bench_line_of_long_regions():

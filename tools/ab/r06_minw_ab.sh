@@ -13,7 +13,7 @@ import sys,json
 for l in sys.stdin:
     if l.startswith('{'):
         d=json.loads(l); print('$lib per-step launches K=500', round(d['value']/1e6,1), 'M', d['roofline']['kernel'])" >> $OUT
-  python bench.py --warmup 5 --steps 20 --no-cpu-baseline --min-seconds 1.0 2>/dev/null | python -c "
+  python bench.py --warmup 5 --steps 20 --full --no-cpu-baseline --min-seconds 1.0 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -33,7 +33,7 @@ bash tools/valu_phases.sh > /dev/null 2>&1
 [ -f build_var/stopfast.so ] && bash tools/valu_phases_fast.sh > /dev/null 2>&1
 # 4. the launch's timeline (per-wave time stamps) at the driver's K and the full bench lines
 python tools/persist_timeline.py 2>&1 | grep "cc4 timeline" > $OUT/${TAG}_persist_timeline.txt
-python bench.py --steps 20 --warmup 5 > $OUT/${TAG}_bench_driver_flags.json 2> /dev/null
-python bench.py --steps 500 --warmup 50 --no-cpu-baseline > $OUT/${TAG}_bench_default.json 2> /dev/null
+python bench.py --steps 20 --warmup 5 --full > $OUT/${TAG}_bench_driver_flags.json 2> /dev/null
+python bench.py --steps 500 --warmup 50 --full --no-cpu-baseline > $OUT/${TAG}_bench_default.json 2> /dev/null
 for n in 16384 32768 4096 2048; do python bench.py --steps 500 --warmup 50 --no-alt --no-cpu-baseline --total-envs $n --min-seconds 1 > $OUT/${TAG}_bench_${n}env.json 2>/dev/null; done
 ls -la $OUT
