@@ -12,3 +12,11 @@ from .wrappers import (CybORG, EnterpriseScenarioGenerator, SleepAgent, Enterpri
 from .true_state import TrueStateTableWrapper  # noqa: F401
 
 __version__ = '0.1.0'
+
+
+def __getattr__(name):
+    # CC4TorchVecEnv needs torch: imported on first use, so that importing the package does not import torch
+    if name == 'CC4TorchVecEnv':
+        from .torch_env import CC4TorchVecEnv
+        return CC4TorchVecEnv
+    raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

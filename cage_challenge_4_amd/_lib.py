@@ -73,6 +73,9 @@ SIGNATURES = {
     'cc4_group_info': (ctypes.c_int, [_P, ctypes.c_int32, _P, _P, _P]),
     'cc4_step_group_device': (ctypes.c_int, [_P, ctypes.c_int32, _P, _P]),
     'cc4_random_actions_group_device': (ctypes.c_int, [_P, ctypes.c_int32, ctypes.c_uint64, ctypes.c_uint32]),
+    'cc4_stream_wait': (ctypes.c_int, [_P, _P]),
+    'cc4_stream_signal': (ctypes.c_int, [_P, _P]),
+    'cc4_policy_outputs': (ctypes.c_int, [_P, ctypes.c_int32, _P, _P, _P, _P, _P]),
     'cc4_rollout_begin': (ctypes.c_int, [_P, ctypes.c_int32]),
     'cc4_rollout_groups': (ctypes.c_int, [_P, _P, _P]),
     'cc4_rollout_policy_stream': (ctypes.c_int, [_P, _P]),

@@ -56,6 +56,7 @@ struct cc4_handle {
   hipStream_t gstream[MAX_GROUPS] = {};          // gstream[0] == stream
   hipEvent_t gev[MAX_GROUPS] = {};               // group stream -> main stream ordering (join_groups)
   hipEvent_t mev = nullptr;                      // main stream -> group streams ordering (fork_groups)
+  hipEvent_t ev_wait = nullptr, ev_signal = nullptr;   // a caller's stream -> main stream (cc4_stream_wait), main stream -> a caller's stream (cc4_stream_signal)
   bool auto_groups = true;                       // the number of groups is the library's choice (no CC4_GROUPS)
   bool groups_busy = false;                      // a group stream other than the main one may hold unfinished step launches
   bool joined_between = false;                   // something ordered the main stream behind all groups (or waited for them) since the last step launches:
@@ -572,6 +573,8 @@ int cc4_create(const cc4_config* cfg, cc4_handle** out) {
     HIPCHK(h, hipEventCreateWithFlags(&h->gev[g], hipEventDisableTiming));
   }
   HIPCHK(h, hipEventCreateWithFlags(&h->mev, hipEventDisableTiming));
+  HIPCHK(h, hipEventCreateWithFlags(&h->ev_wait, hipEventDisableTiming));
+  HIPCHK(h, hipEventCreateWithFlags(&h->ev_signal, hipEventDisableTiming));
   if (h->auto_groups && h->ngroups == 3) {
     // a fourth launch per step where this handle's four streams really run side by side (8192 episodes 717 -> 742 M, 2048: 310 ->
     // 314 M, 1024: 179 -> 183 M; with two of them on one hardware queue: 445 M)
@@ -672,6 +675,8 @@ void cc4_destroy(cc4_handle* h) {
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   for (int g = 1; g < cc4_handle::MAX_GROUPS; ++g) { if (h->gev[g]) (void)hipEventDestroy(h->gev[g]); if (h->gstream[g]) (void)hipStreamDestroy(h->gstream[g]); }
   if (h->mev) (void)hipEventDestroy(h->mev);
+  if (h->ev_wait) (void)hipEventDestroy(h->ev_wait);
+  if (h->ev_signal) (void)hipEventDestroy(h->ev_signal);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
 }
@@ -963,6 +968,42 @@ int cc4_random_actions_device(cc4_handle* h, uint64_t seed0, uint32_t t) {
   if (join_groups(h)) return -1;
   int tot = h->cfg.num_envs * NBLUE;
   hipLaunchKernelGGL(k_random_actions, dim3((tot + 255) / 256), dim3(256), 0, h->stream, h->d_actions, h->cfg.num_envs, seed0, t, 0);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+// ---- a policy on a stream of the caller's (a PyTorch learner on the same GPU): ordering in both directions without a host wait, and the
+// outputs written into the caller's own tensors by one kernel (k_policy_outputs)
+int cc4_stream_wait(cc4_handle* h, void* hip_stream) {
+  if (h->rollout_k > 0 && !h->rollout_entering) { h->err = "cc4_stream_wait: a rollout is in flight on this handle: cc4_rollout_end first"; return -1; }
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  HIPCHK(h, hipEventRecord(h->ev_wait, reinterpret_cast<hipStream_t>(hip_stream)));
+  HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_wait, 0));
+  if (h->ngroups > 1) h->main_ahead = true;      // the group streams follow at their next launch (launch_step / group_prologue)
+  return 0;
+}
+int cc4_stream_signal(cc4_handle* h, void* hip_stream) {
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  if (join_groups(h)) return -1;
+  HIPCHK(h, hipEventRecord(h->ev_signal, h->stream));
+  HIPCHK(h, hipStreamWaitEvent(reinterpret_cast<hipStream_t>(hip_stream), h->ev_signal, 0));
+  return 0;
+}
+int cc4_policy_outputs(cc4_handle* h, int32_t obs_dtype, void* d_obs, uint8_t* d_mask, float* d_reward, uint8_t* d_done, int32_t* d_err) {
+  if (obs_dtype < 0 || obs_dtype > 3) { h->err = "cc4_policy_outputs: obs_dtype must be 0 (uint8), 1 (float16), 2 (bfloat16) or 3 (float32)"; return -2; }
+  if (!d_obs || !d_mask || !d_reward || !d_done || !d_err) { h->err = "cc4_policy_outputs: every output buffer is required"; return -2; }
+  static const uintptr_t align[4] = {4, 8, 8, 16};          // one store of four values per lane
+  if (reinterpret_cast<uintptr_t>(d_obs) % align[obs_dtype] || reinterpret_cast<uintptr_t>(d_reward) % 4 || reinterpret_cast<uintptr_t>(d_err) % 4) {
+    h->err = "cc4_policy_outputs: the observation buffer must be aligned to four values, reward and error buffers to 4 bytes"; return -2;
+  }
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  if (join_groups(h)) return -1;
+  const int n = h->cfg.num_envs, tpb = 256;
+  const int ep_blocks = (n + tpb - 1) / tpb;
+  const long long vecs = (long long)n * OBS_TOTAL / 4;
+  // the observations are a streaming copy: enough blocks to fill the chip (8 per CU), each lane looping over what is left
+  const int obs_blocks = (int)std::max(1LL, std::min((vecs + tpb - 1) / tpb, 8LL * h->cus));
+  hipLaunchKernelGGL(k_policy_outputs, dim3(ep_blocks + obs_blocks), dim3(tpb), 0, h->stream, h->d_state, h->d_obs, h->d_reward, h->d_done, h->d_err,
+                     n, ep_blocks, (int)obs_dtype, d_obs, d_mask, d_reward, d_done, d_err);
   HIPCHK(h, hipGetLastError());
   return 0;
 }

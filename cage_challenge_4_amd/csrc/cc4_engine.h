@@ -1150,16 +1150,18 @@ CC4_HD Act blue_decode(const EnvState* s, int b, int idx) {
   a.type = (uint8_t)t; a.host = (uint8_t)h;
   return a;
 }
+// one entry of the mask: slot i of agent b is valid unless it decodes to Sleep -- except the list's own Sleep slot
+CC4_HD uint8_t blue_mask_slot(const EnvState* s, int b, int i) {
+  Act a = blue_decode(s, b, i);
+  int nh = ZONE_HOSTS * blue_nsub(b);
+  bool is_sleep_slot = (i == 3 * nh + 1);
+  return (uint8_t)((a.type != BA_SLEEP) || is_sleep_slot);
+}
 CC4_HD void blue_action_mask(const EnvState* s, uint8_t* mask /* MASK_TOTAL */) {
   int o = 0;
   for (int b = 0; b < NBLUE; ++b) {
     int n = b == 4 ? ACT_LONG : ACT_SHORT;
-    for (int i = 0; i < n; ++i) {
-      Act a = blue_decode(s, b, i);
-      int nh = ZONE_HOSTS * blue_nsub(b);
-      bool is_sleep_slot = (i == 3 * nh + 1);
-      mask[o++] = (uint8_t)((a.type != BA_SLEEP) || is_sleep_slot);
-    }
+    for (int i = 0; i < n; ++i) mask[o++] = blue_mask_slot(s, b, i);
   }
 }
 

@@ -108,6 +108,77 @@ __global__ void k_unpack_obs(const uint8_t* __restrict__ packed, uint8_t* __rest
   for (int k = 0; k < 4; ++k) if (4 * j + k < OBS_TOTAL) o[k] = (uint8_t)((b >> (2 * k)) & 3u);
 }
 
+// cc4_policy_outputs: the handle's outputs as a policy consumes them, in caller-owned buffers.  ONE launch, two kinds of blocks:
+//   blocks [0, ep_blocks): one lane per episode -- reward, done, error word, and the action-mask row of every episode whose row was
+//     (re)generated since its last step (step_count 0: cc4_reset, or the in-kernel autoreset of the step just taken); the wave ballots
+//     those and rebuilds each one's 570 entries with all 64 lanes (blue_mask_slot, the rule of blue_action_mask).  Mask rows of the other
+//     episodes are left as they are: a mask is a function of the scenario alone, so the caller's buffer is persistent.
+//   blocks [ep_blocks, grid): the observations as ONE flat array of n * 578 int32 values (a 2312-byte row is not 16-byte aligned, the
+//     flat array is), grid-stride, one int4 load and one store of the four converted values per lane (4 / 8 / 8 / 16 bytes).  Every value is
+//     0, 1 or 2 (CC4_OBS_PACKED_BYTES), so every dtype is exact; half and bfloat16 bit patterns come from a 4-entry table in one constant.
+// Reads the handle's buffers, never writes them.
+// float16 (0, 1, 2, 3 -> 0x0000 0x3C00 0x4000 0x4200) / bfloat16 (-> 0x0000 0x3F80 0x4000 0x4040): the bit pattern of a value out of one constant
+template <int DT> __device__ __forceinline__ uint32_t policy_half_bits(int x) {
+  constexpr uint64_t tab = DT == 1 ? 0x420040003C000000ull : 0x404040003F800000ull;
+  return (uint32_t)(tab >> (16 * (x & 3))) & 0xFFFFu;
+}
+template <int DT> __device__ __forceinline__ void policy_obs_put(void* out, size_t i, int4 v) {
+  if constexpr (DT == 0) {          // uint8
+    reinterpret_cast<uint32_t*>(out)[i] = (uint32_t)(v.x & 0xFF) | (uint32_t)(v.y & 0xFF) << 8 | (uint32_t)(v.z & 0xFF) << 16 | (uint32_t)(v.w & 0xFF) << 24;
+  } else if constexpr (DT == 3) {   // float32
+    reinterpret_cast<float4*>(out)[i] = make_float4((float)v.x, (float)v.y, (float)v.z, (float)v.w);
+  } else {                          // float16 / bfloat16
+    reinterpret_cast<uint2*>(out)[i] = make_uint2(policy_half_bits<DT>(v.x) | policy_half_bits<DT>(v.y) << 16, policy_half_bits<DT>(v.z) | policy_half_bits<DT>(v.w) << 16);
+  }
+}
+template <int DT> __device__ __forceinline__ void policy_obs_part(const int32_t* __restrict__ obs, void* __restrict__ out, size_t total, size_t i0, size_t stride) {
+  const size_t nv = total / 4;
+  const int4* __restrict__ src = reinterpret_cast<const int4*>(obs);
+  for (size_t i = i0; i < nv; i += stride) policy_obs_put<DT>(out, i, src[i]);
+  if (i0 == 0) {                    // an odd batch: the last two values one at a time (578 * n is even)
+    for (size_t j = 4 * nv; j < total; ++j) {
+      const int x = obs[j];
+      if constexpr (DT == 0) reinterpret_cast<uint8_t*>(out)[j] = (uint8_t)x;
+      else if constexpr (DT == 3) reinterpret_cast<float*>(out)[j] = (float)x;
+      else reinterpret_cast<uint16_t*>(out)[j] = (uint16_t)policy_half_bits<DT>(x);
+    }
+  }
+}
+__global__ __launch_bounds__(256) void k_policy_outputs(const EnvState* __restrict__ st, const int32_t* __restrict__ obs, const float* __restrict__ reward,
+                                                        const uint8_t* __restrict__ done, const uint32_t* __restrict__ err, int n, int ep_blocks, int dtype,
+                                                        void* __restrict__ out_obs, uint8_t* __restrict__ out_mask, float* __restrict__ out_reward,
+                                                        uint8_t* __restrict__ out_done, int32_t* __restrict__ out_err) {
+  if ((int)blockIdx.x < ep_blocks) {
+    const int e = (int)(blockIdx.x * blockDim.x + threadIdx.x), lane = (int)threadIdx.x & (WAVE - 1);
+    bool regen = false;
+    if (e < n) {
+      out_reward[e] = reward[e]; out_done[e] = done[e]; out_err[e] = (int32_t)err[e];
+      regen = st[e].step_count == 0;
+    }
+    unsigned long long todo = __ballot(regen);
+    while (todo) {
+      const int k = __ffsll(todo) - 1;
+      todo &= todo - 1;
+      const int er = e - lane + k;
+      const EnvState* s = st + er;
+      uint8_t* m = out_mask + (size_t)er * MASK_TOTAL;
+      for (int o = lane; o < MASK_TOTAL; o += WAVE) {
+        const int b = o < 4 * ACT_SHORT ? o / ACT_SHORT : 4;
+        m[o] = blue_mask_slot(s, b, o - b * ACT_SHORT);
+      }
+    }
+    return;
+  }
+  const size_t total = (size_t)n * OBS_TOTAL;
+  const size_t i0 = (size_t)(blockIdx.x - ep_blocks) * blockDim.x + threadIdx.x, stride = (size_t)(gridDim.x - ep_blocks) * blockDim.x;
+  switch (dtype) {
+    case 0: policy_obs_part<0>(obs, out_obs, total, i0, stride); break;
+    case 1: policy_obs_part<1>(obs, out_obs, total, i0, stride); break;
+    case 2: policy_obs_part<2>(obs, out_obs, total, i0, stride); break;
+    default: policy_obs_part<3>(obs, out_obs, total, i0, stride); break;
+  }
+}
+
 // CybORG.set_seed (env.py:316-325): a fresh generator for the controller, the state and the hosts; the agents' policies keep
 // the old one until the next reset (EnvCold.rng2); the episode itself stays as it is
 __global__ void k_set_seed(EnvState* st, EnvCold* cold, size_t cold_row, const uint64_t* seeds, int n, int rng_mode) {

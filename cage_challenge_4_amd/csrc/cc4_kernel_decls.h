@@ -34,6 +34,10 @@ __global__ void k_discover(int32_t* count, long long ticks);
 __global__ void k_random_actions(int32_t* actions, int n, uint64_t seed0, uint32_t t, int e0 = 0);
 __global__ void k_spin(long long cycles);
 __global__ void k_unpack_obs(const uint8_t* __restrict__ packed, uint8_t* __restrict__ out, int rows);
+__global__ void k_policy_outputs(const EnvState* __restrict__ st, const int32_t* __restrict__ obs, const float* __restrict__ reward,
+                                 const uint8_t* __restrict__ done, const uint32_t* __restrict__ err, int n, int ep_blocks, int dtype,
+                                 void* __restrict__ out_obs, uint8_t* __restrict__ out_mask, float* __restrict__ out_reward,
+                                 uint8_t* __restrict__ out_done, int32_t* __restrict__ out_err);
 __global__ void k_set_seed(EnvState* st, EnvCold* cold, size_t cold_row, const uint64_t* seeds, int n, int rng_mode);
 __global__ void k_set_rng_state(EnvState* st, const uint64_t* w, int n);
 __global__ void k_rng_state(const EnvState* st, uint64_t* out, int n);

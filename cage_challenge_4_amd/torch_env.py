@@ -1,0 +1,127 @@
+"""CC4TorchVecEnv -- CC4VecEnv for a PyTorch learner on the same GPU: actions in, observations / masks / rewards / dones out, as torch
+tensors on the device, with no host copy and no host synchronisation in step().
+
+The engine's work runs on the handle's own (non-blocking) HIP streams; every call here is ordered against torch.cuda.current_stream()
+in both directions (cc4_stream_wait / cc4_stream_signal, include/cc4.h), and one kernel (k_policy_outputs, cc4_policy_outputs) writes
+the outputs straight into this object's tensors in the dtype the policy wants.  Importing this module imports torch; importing the
+package does not."""
+import ctypes
+import numpy as np
+import torch
+from . import _lib as L
+from .vec_env import CC4VecEnv, split_obs, split_mask  # noqa: F401  (split_obs / split_mask slice tensors too)
+
+_OBS_DTYPES = {torch.uint8: 0, torch.float16: 1, torch.bfloat16: 2, torch.float32: 3}
+
+
+class CC4TorchVecEnv:
+    """N episodes of CC4VecEnv stepped from device tensors.
+
+    CC4TorchVecEnv(num_envs, *, obs_dtype=torch.uint8, **kw): kw are CC4VecEnv's keyword arguments (steps, rng_mode, device_id,
+    autoreset, red_policy, green_policy, topology_seed, blue_policy, strict); the tensors live on cuda:<device_id>.
+
+    reset(seeds=None, env_mask=None) -> (obs, info)             seeds / env_mask as CC4VecEnv.reset
+    step(actions, messages=None)     -> (obs, reward, done, info)
+        actions   integer tensor [N, 5] of wrapper action indices on the env's device (negative: no action), any integer dtype;
+        messages  optional [N, 5, 8] tensor of 0 / 1 bytes;
+        obs [N, 578] obs_dtype, reward [N] float32, done [N] bool, info {'action_mask': [N, 570] bool, 'err': [N] int32}.
+    Everything runs on torch.cuda.current_stream() as it stands at the call: whatever the caller enqueued there before (the policy that
+    wrote `actions`) happens before the step, and whatever it enqueues after the call sees the step's outputs.  Callers that switch
+    streams between calls order those streams themselves, as with any torch tensor.
+
+    The returned tensors are this object's own and are REUSED: they hold the outputs of the last step / reset and stay valid until the
+    next step() or reset() (clone what must outlive it).  `done` is terminated or truncated, as the reference's wrapper reports it
+    (BlueFixedActionWrapper.py:177-178).  With autoreset=True, the call that follows a `done` regenerates that episode and takes no
+    step in it (reward 0, the new scenario's first observation and action mask).  The action masks are refreshed for exactly the
+    episodes a call (re)generated, on the device.
+
+    No call synchronises except check_errors(), which reads the error flags and raises what CC4VecEnv raises (ValueError for a step past
+    the episode's end -- the reference's own error -- and CC4EngineError for any other flag; strict=False: the ValueError only)."""
+
+    def __init__(self, num_envs, *, obs_dtype=torch.uint8, **kw):
+        if obs_dtype not in _OBS_DTYPES:
+            raise ValueError(f'obs_dtype must be one of {list(_OBS_DTYPES)}, got {obs_dtype}')
+        self.venv = CC4VecEnv(num_envs, **kw)        # creates the handle (CC4Error without a HIP device) and keeps the error bookkeeping
+        self.lib, self._h = self.venv.lib, self.venv._h
+        self.num_envs = n = self.venv.num_envs
+        self.obs_dtype = obs_dtype
+        self._dt = _OBS_DTYPES[obs_dtype]
+        self.device = torch.device('cuda', int(kw.get('device_id', 0)))
+        with torch.cuda.device(self.device):
+            z = dict(device=self.device)
+            self.obs = torch.zeros((n, L.OBS_PER_ENV), dtype=obs_dtype, **z)
+            self.action_mask = torch.zeros((n, L.MASK_PER_ENV), dtype=torch.bool, **z)
+            self.reward = torch.zeros(n, dtype=torch.float32, **z)
+            self.done = torch.zeros(n, dtype=torch.bool, **z)
+            self.err = torch.zeros(n, dtype=torch.int32, **z)
+            self._actions = torch.zeros((n, L.NUM_BLUE), dtype=torch.int32, **z)
+            self._messages = torch.zeros((n, L.NUM_BLUE, L.MSG_LEN), dtype=torch.uint8, **z)
+        vp = ctypes.c_void_p
+        self._p_out = (vp(self.obs.data_ptr()), vp(self.action_mask.data_ptr()), vp(self.reward.data_ptr()), vp(self.done.data_ptr()),
+                       vp(self.err.data_ptr()))
+        self._p_act, self._p_msg = vp(self._actions.data_ptr()), vp(self._messages.data_ptr())
+
+    def _info(self):
+        return {'action_mask': self.action_mask, 'err': self.err}
+
+    def _outputs(self, s):
+        # (the handle's streams -> s behind the kernel that wrote this object's tensors)
+        lib, h = self.lib, self._h
+        rc = lib.cc4_policy_outputs(h, self._dt, *self._p_out)
+        if rc:
+            self.venv._chk(rc, 'cc4_policy_outputs')
+        self.venv._chk(lib.cc4_stream_signal(h, s), 'cc4_stream_signal')
+
+    def reset(self, seeds=None, env_mask=None):
+        with torch.cuda.device(self.device):
+            s = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            # the reset rewrites rows the last step's kernels may still read, and the outputs go into tensors the caller's stream may
+            # still read: everything on s first (cc4_reset itself waits for the device before it returns)
+            self.venv._chk(self.lib.cc4_stream_wait(self._h, s), 'cc4_stream_wait')
+            sp = mp = None
+            if seeds is not None:
+                if np.isscalar(seeds):
+                    seeds = np.uint64(seeds) + np.arange(self.num_envs, dtype=np.uint64)
+                seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
+                assert seeds.shape == (self.num_envs,)
+                sp = seeds.ctypes.data_as(ctypes.c_void_p)
+            if env_mask is not None:
+                env_mask = np.ascontiguousarray(env_mask, dtype=np.uint8)
+                assert env_mask.shape == (self.num_envs,)
+                mp = env_mask.ctypes.data_as(ctypes.c_void_p)
+            self.venv._chk(self.lib.cc4_reset(self._h, sp, mp), 'cc4_reset')
+            self._outputs(s)
+        return self.obs, self._info()
+
+    def step(self, actions, messages=None):
+        with torch.cuda.device(self.device):
+            if tuple(actions.shape) != (self.num_envs, L.NUM_BLUE) or (messages is not None and tuple(messages.shape) != tuple(self._messages.shape)):
+                raise ValueError(f'actions must be [{self.num_envs}, {L.NUM_BLUE}] and messages [{self.num_envs}, {L.NUM_BLUE}, {L.MSG_LEN}]')
+            s = torch.cuda.current_stream(self.device)
+            # staging copies on s: any integer dtype cast, and the env no longer depends on the lifetime of the caller's tensors
+            self._actions.copy_(actions)
+            if messages is not None:
+                self._messages.copy_(messages)
+            lib, h, sp = self.lib, self._h, ctypes.c_void_p(s.cuda_stream)
+            rc = lib.cc4_stream_wait(h, sp) or lib.cc4_step_device(h, self._p_act, self._p_msg if messages is not None else None)
+            if rc:
+                self.venv._chk(rc, 'cc4_step_device')
+            self._outputs(sp)
+        return self.obs, self.reward, self.done, self._info()
+
+    def check_errors(self):
+        """The one synchronising call: reads the error flags of the last step / reset and raises what CC4VecEnv.step would have raised
+        (strict mode: each engine flag once per episode, a step past the end every time)."""
+        self.venv._err[:] = self.err.cpu().numpy().view(np.uint32)
+        self.venv._check_err()
+
+    def close(self):
+        if getattr(self, 'venv', None) is not None:
+            self.venv.close()
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
