@@ -413,6 +413,38 @@ CC4_HD int rs_find_host_pid(const EnvState* s, const RedAgent& a, int h, int pid
   }
   return -1;
 }
+// What a red action reads from its agent's session list before it changes anything: the index of its acting session
+// (rs_find_id(a.sid)) and the agent's sessions on the target host (rs_on_host(a.host)).  The lane-parallel kernel computes it for all
+// six agents in one pass of the wave (rs_wave_query) and hands it in; ok = false: the action computes it itself.  (Passed by value: a
+// pointer that is null on some paths would keep it in scratch memory.)
+struct RedPre { int si = -1; HostSess hs = {0, -1, -1}; bool ok = false; };
+#if defined(__HIPCC__)
+// RedPre of all six agents in one pass of the wave.  Lane 8r + k reads entry i0 + k of agent r's list and its record, the agent's keys
+// reach it through ds_bpermute, one compare + ballot per question, and agent lane r takes byte r of each mask.  Agents with more than
+// eight sessions take further rounds; the round count is the largest nsess of an asking agent over eight (a ballot: uniform).  Call
+// with ALL lanes active; the keys are read from lanes 0..NRED-1 (sid < 0: the agent asks nothing) and the answers are valid there.
+__device__ __forceinline__ RedPre rs_wave_query(const EnvState* s, int lane, int sid, int host) {
+  const int r = lane >> 3, k = lane & 7, ra = r < NRED ? r : 0;
+  const RedAgent& A = s->red[ra];
+  const int ksid = __builtin_amdgcn_ds_bpermute(ra << 2, sid), khost = __builtin_amdgcn_ds_bpermute(ra << 2, host);
+  const int n = (r < NRED && ksid >= 0) ? (int)A.h.nsess : 0;
+  const int sh = 8 * k;                   // agent lane r < NRED: its byte of a mask
+  RedPre p; p.ok = true;
+  for (int i0 = 0; __ballot(i0 < n); i0 += 8) {
+    const bool v = i0 + k < n;
+    uint64_t w = 0;
+    if (v) w = rs_word(s, A.sord[i0 + k]);
+    const bool on = v && rsw_host(w) == khost;
+    const uint32_t bid = (uint32_t)(__ballot(v && rsw_id(w) == ksid) >> sh) & 0xFFu;
+    const uint32_t bh = (uint32_t)(__ballot(on) >> sh) & 0xFFu, br = (uint32_t)(__ballot(on && (rsw_flags(w) & RS_ROOT)) >> sh) & 0xFFu;
+    if (p.si < 0 && bid) p.si = i0 + ctz32(bid);
+    p.hs.n += __popc(bh);
+    if (p.hs.first < 0 && bh) p.hs.first = i0 + ctz32(bh);
+    if (p.hs.first_root < 0 && br) p.hs.first_root = i0 + ctz32(br);
+  }
+  return p;
+}
+#endif
 // list entries idx+1 .. nsess-1 move down by one: the 64-byte list is eight words, read as one batch and funnel-shifted
 CC4_HD void rs_list_remove(RedAgent& a, int idx) {
   uint64_t w[MAX_RS / 8];
@@ -1468,11 +1500,11 @@ CC4_HD void red_result(Ctx x, int r, const Act& a, int success) {
   obs_first(x, r, success, a.type, a.host, arg);
 }
 // DiscoverRemoteSystems -> Pingsweep.execute (ConcreteActions/Pingsweep.py:31-64)
-CC4_HD void red_drs(Ctx x, int r, const Act& a) {
+CC4_HD void red_drs(Ctx x, int r, const Act& a, RedPre pre = RedPre()) {
   EnvState* s = x.s;
   int sn = a.arg; bool any = false;
   // the session can die between filter_actions and execution (a blue Remove/Restore runs earlier in the same step)
-  if (rs_find_id(s, s->red[r], a.sid) < 0) { red_result(x, r, a, T_FALSE); return; }
+  if ((pre.ok ? pre.si : rs_find_id(s, s->red[r], a.sid)) < 0) { red_result(x, r, a, T_FALSE); return; }
   bool allowed = (red_allowed_mask(r) >> sn) & 1u;  // SimulationController._filter_obs drops foreign-subnet interfaces
   // the subnet's non-router hosts are the 16 ids lo .. lo+15; they straddle at most two bitmap words.  All of them get the same
   // observation entry (obs_put(ip key, OE_IFACE, subnet known)), so the bitmaps are updated per word and the new entries
@@ -1505,10 +1537,10 @@ CC4_HD void red_drs(Ctx x, int r, const Act& a) {
 }
 // DiscoverNetworkServices.execute + Portscan.execute (AbstractActions/DiscoverNetworkServices.py:44-86, Portscan.py:23-65)
 CC4_HD int port_of_bit(int pb) { return pb == PB_22 ? 22 : (pb == PB_80 ? 80 : (pb == PB_3390 ? 3390 : (pb == PB_25 ? 25 : (pb == PB_1 ? 1 : 443)))); }
-CC4_HD void red_scan(Ctx x, int r, const Act& a, double rate) {
+CC4_HD void red_scan(Ctx x, int r, const Act& a, double rate, RedPre pre = RedPre()) {
   EnvState* s = x.s;
   RedAgent& A = s->red[r];
-  int si = rs_find_id(s, A, a.sid);
+  int si = pre.ok ? pre.si : rs_find_id(s, A, a.sid);
   if (si < 0) { red_result(x, r, a, T_FALSE); return; }
   const int slot = A.sord[si];
   const uint64_t sw = rs_word(s, slot);
@@ -1547,10 +1579,10 @@ CC4_HD int exploit_new_session(Ctx x, int r, int parent_sid, int tgt, const P8N&
   return rs_add(x, r, tgt, pid, RS_CHILD, x.w->rs_slot[r]);   // Session(parent=self.session) (ExploitAction.py:250-259); slot reserved by rs_reserve
 }
 // ExploitRemoteService.execute (AbstractActions/ExploitRemoteService.py:149-202) + selector (:37-69)
-CC4_HD void red_exploit(Ctx x, int r, const Act& a) {
+CC4_HD void red_exploit(Ctx x, int r, const Act& a, RedPre pre = RedPre()) {
   EnvState* s = x.s;
   RedAgent& A = s->red[r];
-  int si = rs_find_id(s, A, a.sid);
+  int si = pre.ok ? pre.si : rs_find_id(s, A, a.sid);
   if (si < 0) { red_result(x, r, a, T_FALSE); return; }
   const int slot = A.sord[si];
   const uint64_t sw = rs_word(s, slot);
@@ -1642,11 +1674,11 @@ CC4_HD void red_exploit(Ctx x, int r, const Act& a) {
   red_result(x, r, a, T_TRUE);
 }
 // PrivilegeEscalate.execute (AbstractActions/PrivilegeEscalate.py:127-179)
-CC4_HD void red_privesc(Ctx x, int r, const Act& a) {
+CC4_HD void red_privesc(Ctx x, int r, const Act& a, RedPre pre = RedPre()) {
   EnvState* s = x.s;
   RedAgent& A = s->red[r];
   int h = a.host;
-  const HostSess hs = rs_on_host(s, A, h);
+  const HostSess hs = pre.ok ? pre.hs : rs_on_host(s, A, h);
   const int n = hs.n;
   int target = hs.first_root;
   if (n == 0) { red_result(x, r, a, T_FALSE); return; }
@@ -1654,7 +1686,7 @@ CC4_HD void red_privesc(Ctx x, int r, const Act& a) {
     target = rs_kth_on_host(s, A, h, (int)rng_below(x.r, (uint32_t)n));   // choice(sessions on the host)
     // DefaultEscalateActionSelector (PrivilegeEscalate.py:52-66): self.session must exist and be a RedAbstractSession,
     // else no sub-action -> Observation(False); then V4L2KernelExploit via TargetedLocalAction.execute
-    { int ss = rs_find_id(s, A, a.sid);
+    { int ss = pre.ok ? pre.si : rs_find_id(s, A, a.sid);
       if (ss < 0 || !(rsw_flags(rs_at(s, A, ss)) & RS_ABSTRACT)) { red_result(x, r, a, T_FALSE); return; } }
     const int tslot = A.sord[target];
     s->spool[tslot].flags |= RS_ROOT;  // EscalateAction.__upgrade_session (EscalateAction.py:57-87)
@@ -1666,25 +1698,25 @@ CC4_HD void red_privesc(Ctx x, int r, const Act& a) {
   obs_put(x, r, false, h, OE_SESS, false);
   { const uint64_t tw = rs_at(s, A, target); if (rsw_flags(tw) & RS_ABSTRACT) as_know_sid(x, r, rsw_id(tw)); }
   // ExploreHost (EscalateAction.py:90-106): host.info links exist only on server_host_0 (ESG.py:418-468)
-  if (rs_find_id(s, A, a.sid) >= 0 && h_slot(h) == 11) {
+  if ((pre.ok ? pre.si : rs_find_id(s, A, a.sid)) >= 0 && h_slot(h) == 11) {   // (privesc adds and removes no session)
     uint32_t m = info_links(h_subnet(h));
     for (int sn = 0; sn < NSUB; ++sn) if ((m >> sn) & 1u) obs_put(x, r, false, h_make(sn, 11), OE_IFACE, false);
   }
   red_result(x, r, a, T_TRUE);
 }
 // Impact.execute (AbstractActions/Impact.py:38-88)
-CC4_HD void red_impact(Ctx x, int r, const Act& a) {
+CC4_HD void red_impact(Ctx x, int r, const Act& a, RedPre pre = RedPre()) {
   EnvState* s = x.s;
   RedAgent& A = s->red[r];
   int h = a.host;
-  if (rs_on_host(s, A, h).first_root < 0) { red_result(x, r, a, T_FALSE); return; }   // no session, or none of them root
+  if ((pre.ok ? pre.hs : rs_on_host(s, A, h)).first_root < 0) { red_result(x, r, a, T_FALSE); return; }   // no session, or none of them root
   HostDyn& d = x.hd[h];
   const SvTab sv = svc_load(d);
   int si = -1;
   uint32_t sw = 0;   // the entry found (kept beside its index: a run-time index into the table would put the table into scratch memory)
   CC4_UNROLL for (int i = MAXSV - 1; i >= 0; --i) if (i < sv.n && svw_kind(sv.w[i]) == K_OT && (svw_st(sv.w[i]) & SV_ACTIVE)) { si = i; sw = sv.w[i]; }   // the first one
   if (si < 0) { red_result(x, r, a, T_FALSE); return; }
-  if (rs_find_id(s, A, a.sid) < 0) { red_result(x, r, a, T_FALSE); return; }  // StopService needs self.session too
+  if ((pre.ok ? pre.si : rs_find_id(s, A, a.sid)) < 0) { red_result(x, r, a, T_FALSE); return; }  // StopService needs self.session too
   hd_touch(x, h);
   d.svcs[si].st = (uint8_t)(svw_st(sw) & ~SV_ACTIVE);          // Host.stop_service (Host.py:295-300)
   int pi = find_proc(x, h, (int)(sw & 0xFFFF));                 // State.remove_process (State.py:390-418)
@@ -1693,11 +1725,11 @@ CC4_HD void red_impact(Ctx x, int r, const Act& a) {
   red_result(x, r, a, T_TRUE);
 }
 // DegradeServices.execute (AbstractActions/DegradeServices.py:38-82)
-CC4_HD void red_degrade(Ctx x, int r, const Act& a) {
+CC4_HD void red_degrade(Ctx x, int r, const Act& a, RedPre pre = RedPre()) {
   EnvState* s = x.s;
   RedAgent& A = s->red[r];
   int h = a.host;
-  if (rs_on_host(s, A, h).first_root < 0) { red_result(x, r, a, T_FALSE); return; }   // no session, or none of them root
+  if ((pre.ok ? pre.hs : rs_on_host(s, A, h)).first_root < 0) { red_result(x, r, a, T_FALSE); return; }   // no session, or none of them root
   HostDyn& d = x.hd[h];
   int n = 0;
   hd_touch(x, h);
@@ -1713,10 +1745,10 @@ CC4_HD void red_degrade(Ctx x, int r, const Act& a) {
   red_result(x, r, a, T_TRUE);
 }
 // DiscoverDeception.execute (AbstractActions/DiscoverDeception.py:44-101)
-CC4_HD void red_deception(Ctx x, int r, const Act& a) {
+CC4_HD void red_deception(Ctx x, int r, const Act& a, RedPre pre = RedPre()) {
   EnvState* s = x.s;
   RedAgent& A = s->red[r];
-  if (rs_find_id(s, A, a.sid) < 0) { red_result(x, r, a, T_FALSE); return; }
+  if ((pre.ok ? pre.si : rs_find_id(s, A, a.sid)) < 0) { red_result(x, r, a, T_FALSE); return; }
   int tgt = a.host;
   // detection_rate / fp_rate (DiscoverDeception.py:40-41), or the ones the action object came with (ExtAct)
   const double det_rate = (x.ext && (a.busy & AQ_RATE0)) ? x.c->xrate[r][0] : 0.5;
@@ -1786,10 +1818,10 @@ CC4_HD void red_session_check(Ctx x, int r) {
 }
 // Withdraw.execute (ConcreteActions/Withdraw.py:38-91) + StopProcess(stop_all=True).  a.host = ip_address (unused beyond the
 // route, which always exists), a.arg = hostname
-CC4_HD void red_withdraw(Ctx x, int r, const Act& a) {
+CC4_HD void red_withdraw(Ctx x, int r, const Act& a, RedPre pre = RedPre()) {
   EnvState* s = x.s;
   RedAgent& A = s->red[r];
-  if (rs_find_id(s, A, a.sid) < 0) { red_result(x, r, a, T_FALSE); return; }
+  if ((pre.ok ? pre.si : rs_find_id(s, A, a.sid)) < 0) { red_result(x, r, a, T_FALSE); return; }
   const int h = a.arg;
   // all_agents_sessions = child sessions on the host + parent sessions with ident != 0 + (the acting session if it sits there)
   // held as ids, because killing one shifts the others
@@ -1818,19 +1850,20 @@ CC4_HD void red_withdraw(Ctx x, int r, const Act& a) {
   }
   red_result(x, r, a, ok);
 }
-CC4_HD void red_execute(Ctx x, int r, const Act& a) {
+// pre: the agent's RedPre for this action when computed ahead (rs_wave_query; pre.ok)
+CC4_HD void red_execute(Ctx x, int r, const Act& a, RedPre pre = RedPre()) {
   switch (a.type) {
-    case RA_DRS: red_drs(x, r, a); break;
+    case RA_DRS: red_drs(x, r, a, pre); break;
     // detection_rate: the class's own, or the one the action object came with (ExtAct: the reference's tests set it to 0 and 1)
-    case RA_AGGR: red_scan(x, r, a, (x.ext && (a.busy & AQ_RATE0)) ? x.c->xrate[r][0] : 0.75); break;
-    case RA_STEALTH: red_scan(x, r, a, (x.ext && (a.busy & AQ_RATE0)) ? x.c->xrate[r][0] : 0.25); break;
-    case RA_DECEPTION: red_deception(x, r, a); break;
-    case RA_EXPLOIT: red_exploit(x, r, a); break;
-    case RA_PRIVESC: red_privesc(x, r, a); break;
-    case RA_IMPACT: red_impact(x, r, a); break;
-    case RA_DEGRADE: red_degrade(x, r, a); break;
+    case RA_AGGR: red_scan(x, r, a, (x.ext && (a.busy & AQ_RATE0)) ? x.c->xrate[r][0] : 0.75, pre); break;
+    case RA_STEALTH: red_scan(x, r, a, (x.ext && (a.busy & AQ_RATE0)) ? x.c->xrate[r][0] : 0.25, pre); break;
+    case RA_DECEPTION: red_deception(x, r, a, pre); break;
+    case RA_EXPLOIT: red_exploit(x, r, a, pre); break;
+    case RA_PRIVESC: red_privesc(x, r, a, pre); break;
+    case RA_IMPACT: red_impact(x, r, a, pre); break;
+    case RA_DEGRADE: red_degrade(x, r, a, pre); break;
     case RA_INVALID: obs_first(x, r, T_FALSE, RA_NONE, 0, 0); break;
-    case RA_WITHDRAW: red_withdraw(x, r, a); break;
+    case RA_WITHDRAW: red_withdraw(x, r, a, pre); break;
     default: obs_first(x, r, T_UNKNOWN, RA_NONE, 0, 0); break;  // Sleep -> Observation()
   }
 }

@@ -241,12 +241,20 @@ __device__ __forceinline__ void philox1_body(StepArgs a, const int e, const uint
           bool go = is_red && !((serial_red >> lane) & 1u);
           Ctx xe = xr;
           if (!side) { r = __ffs((int)todo) - 1; todo &= todo - 1u; go = lane == 0; xe.prof = x0.prof; xe.aprof = nullptr; }
+          // what each side-by-side action first reads from its agent's session list (its session by id, the agent's sessions on the target
+          // host): one pass of the wave for all six (rs_wave_query; `side` is uniform, every lane is here) instead of a list scan inside each
+          // action body.  The serial rounds run after other agents' actions and look up for themselves (pe.ok = false).
+          RedPre pe;
+          if (side) {
+            const bool look = go && s->rexec[lane].type < RA_SLEEP;              // (Sleep / InvalidAction / none look nothing up)
+            pe = rs_wave_query(s, lane, look ? (int)s->rexec[lane].sid : -1, look ? (int)s->rexec[lane].host : -1);
+          }
           if (go) {
             unsigned long long t0 = xe.aprof ? clock64() : 0;
             if (s->rexec[r].type != RA_NONE) {                                      // == step_red_exec_agent
               rng_set_stream(&rl, ST_RED_EXE + (uint32_t)r);
               if (side) rng_preload(&rl, pre_re);
-              red_execute(xe, r, s->rexec[r]);
+              red_execute(xe, r, s->rexec[r], pe);
             }
             if (xe.aprof) xe.aprof[1] += clock64() - t0;
           }
