@@ -1588,6 +1588,11 @@ int cc4_rollout_begin(cc4_handle* h, int32_t k) {
              (h->cfg.red_policy & 3) | (h->cfg.green_policy ? GP_SLEEP_BIT : 0) | (h->cfg.green_policy == 2 ? GP_OPEN_BIT : 0) | (h->cfg.blue_policy ? BP_RANDOM_BIT : 0),
              h->full_obs_next ? 1 : 0, (uint32_t)h->cfg.topology_seed, nullptr, h->d_reset_ws, nullptr, 0};
   XchgArgs x{h->d_xslab, nullptr, h->d_xflags + 1, cc4_handle::XRING, 0, h->d_rcnt, h->d_xtimeout};
+  // this parity's ticket lines start from zero.  A rollout counts in words 0 .. PG-1 of its lines and its last tickets clear the same words of the
+  // other parity; a one-launch call counts in word 0 and clears only word 0.  So behind a rollout and an odd number of one-launch calls, words
+  // 1 .. PG-1 of this parity still hold the earlier rollout's final counts: its groups would look handed out (a smaller k) or name steps the
+  // progress words never reach (a larger k).  (The one-launch calls keep their memset-free hand-over: a rollout is the rare call.)
+  HIPCHK(h, hipMemsetAsync(h->d_pool + (size_t)h->pool_parity * CC4_SLOTS * TK_STRIDE, 0, (size_t)h->run_P * TK_STRIDE * sizeof(uint32_t), h->stream));
   if (persist_launch(h, a, k, 0u, x, nullptr, nullptr, true)) return -1;
   HIPCHK(h, hipGetLastError());
   h->stat_steps += k;
@@ -1603,6 +1608,7 @@ int cc4_rollout_groups(cc4_handle* h, int32_t* groups, int32_t* block) {
 }
 int cc4_rollout_obs_packed(cc4_handle* h, int32_t j, const uint8_t** d_rows) {
   if (!h->d_xslab || !h->d_ract) { h->err = "cc4_rollout_obs_packed: no rollout was begun on this handle"; return -2; }      // (also behind cc4_rollout_end: the ring keeps the last 32 steps)
+  if (j < 0) { h->err = "cc4_rollout_obs_packed: step out of range"; return -2; }
   *d_rows = h->d_xslab + (size_t)((j + cc4_handle::XRING - 1) % cc4_handle::XRING) * (size_t)h->cfg.num_envs * OBS_PACKED;
   return 0;
 }
@@ -1645,6 +1651,7 @@ int cc4_rollout_sync(cc4_handle* h, int32_t pub_g, int32_t pub_j, int32_t gate_g
 }
 int cc4_rollout_random_policy(cc4_handle* h, int32_t g, int32_t j, uint64_t seed0, uint32_t t, void* hip_stream) {
   if (rollout_ready(h, "cc4_rollout_random_policy")) return -2;
+  if (g < 0 || g >= h->rpg || j < 0 || j >= h->rollout_k) { h->err = "cc4_rollout_random_policy: group or step out of range"; return -2; }
   hipStream_t st = hip_stream ? (hipStream_t)hip_stream : h->gpolicy[g];
   const int tot = h->cfg.num_envs * NBLUE;
   const int grp = ((h->cfg.num_envs + h->run_P - 1) / h->run_P + h->rpg - 1) / h->rpg * h->run_P * NBLUE;      // threads over the group's episodes (whole blocks of P)
@@ -1654,6 +1661,7 @@ int cc4_rollout_random_policy(cc4_handle* h, int32_t g, int32_t j, uint64_t seed
 }
 int cc4_rollout_hash_policy(cc4_handle* h, int32_t g, int32_t j, void* hip_stream) {
   if (rollout_ready(h, "cc4_rollout_hash_policy")) return -2;
+  if (g < 0 || g >= h->rpg || j < 0 || j >= h->rollout_k) { h->err = "cc4_rollout_hash_policy: group or step out of range"; return -2; }
   hipStream_t st = hip_stream ? (hipStream_t)hip_stream : h->gpolicy[g];
   const int n = h->cfg.num_envs;
   const uint8_t* rows = h->d_xslab + (size_t)((j + cc4_handle::XRING - 1) % cc4_handle::XRING) * (size_t)n * OBS_PACKED;
@@ -1695,6 +1703,12 @@ int cc4_rollout_end(cc4_handle* h) {
   uint32_t gate_failed = 0;
   HIPCHK(h, hipMemcpy(&gate_failed, h->d_rfail, sizeof(uint32_t), hipMemcpyDeviceToHost));
   if (*reinterpret_cast<volatile uint32_t*>(h->h_xtimeout) || gate_failed) {
+    // a wave whose progress wait ran into the watchdog left its item unrun (persist_loop): progress words short of the call's end, tickets never
+    // drawn and so the other parity's lines never cleared.  The schedule's counters start over, as at its setup.
+    HIPCHK(h, hipMemsetAsync(h->d_pool, 0, 2 * (size_t)CC4_SLOTS * TK_STRIDE * sizeof(uint32_t), h->stream));
+    HIPCHK(h, hipMemsetAsync(h->d_run, 0, h->run_words * sizeof(uint32_t), h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->pool_base = 0; h->pool_parity = 0;
     h->err = "cc4_rollout_end: a step of the " + std::to_string(k) + "-step rollout waited longer than " + std::to_string(h->rollout_watchdog_ms) +
              " ms for its actions (or a policy gate for its observations): not every group's policy pass of every step was published -- the episodes were "
              "stepped with whatever the action slots held (CC4_ROLLOUT_WATCHDOG_MS)";
@@ -1935,6 +1949,20 @@ int cc4_debug_policy_probe(cc4_handle* h, int32_t G, int32_t reps, double* out) 
   (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipFree(d_cyc);
   return 0;
 #endif
+}
+// test hook: the persistent schedule's progress words as if `base` steps had run since they were last cleared (every episode's word = base, no
+// runner; pool_base = base) -- the wrap of persist_launch within a few steps' reach
+int cc4_debug_persist_base(cc4_handle* h, uint32_t base) {
+  if (h->rollout_k > 0) { h->err = "cc4_debug_persist_base: a rollout is in flight on this handle"; return -2; }
+  if (base > 0x700000u) { h->err = "cc4_debug_persist_base: base 0 .. 0x700000"; return -2; }
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  if (join_groups(h)) return -1;
+  if (h->persist_state == 0) { if (persist_setup(h)) return -1; }
+  if (h->persist_state != 1 || h->run_pool != 2) { h->err = "cc4_debug_persist_base: this handle has no persistent kernel"; return -2; }
+  HIPCHK(h, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->d_run + 2 * (size_t)h->run_G), (int)base, (size_t)h->cfg.num_envs, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->pool_base = base;
+  return 0;
 }
 int cc4_debug_copy_from_device(cc4_handle* h, void* host_dst, const void* device_src, size_t bytes) {
   HIPCHK(h, hipSetDevice(h->cfg.device_id));

@@ -3,6 +3,24 @@
 #pragma once
 #include "cc4_kernels.h"
 
+// lane 0 of a rollout: wait until episode ee has finished the steps before step j, under the watchdog of the action waits (rollout_wait_actions,
+// act_wait_ticks from the wait's start).  A ticket of this call names a step whose predecessor some wave holds or will draw, so the wait normally
+// ends; a ticket line that does not belong to this call, or a predecessor a wave gave up, would leave it spinning for good.  On expiry both timeout
+// flags are raised and false is returned: the caller leaves without running the item, and cc4_rollout_end reports -6 instead of hanging.  (Only
+// the rollout build has a bound: the non-rollout kernels' progress wait is unbounded)
+__device__ __forceinline__ bool rollout_wait_progress(const RunArgs& ra, const XchgArgs& x, int ee, uint32_t j, uint32_t& w) {
+  const long long w0 = wall_clock64();
+  while ((((w = __hip_atomic_load(&ra.progress[ee], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) & PG_STEPS) - ra.base) < j) {
+    if (wall_clock64() - w0 > ra.act_wait_ticks) {
+      __hip_atomic_store(x.timeout, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      __hip_atomic_store(x.timeout_host, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      return false;
+    }
+    __builtin_amdgcn_s_sleep(8);
+  }
+  return true;
+}
+
 // The schedule (RunArgs).  The batch is cut into one partition per CU (episode e -> partition e % P); a partition's tickets hand out RUNS of
 // consecutive steps of its episodes in step-major order; a run of episode e may start once progress[e] says the steps before it are done.  A wave
 // normally serves its own CU's partition -- an episode then stays on one CU, whose waves share a write-through L1: no cache maintenance -- but it
@@ -70,7 +88,7 @@ __device__ __forceinline__ void persist_loop(StepArgs a, RunArgs ra, const XchgA
             if (t < (uint32_t)(ng * ra.K)) {
               const int j = (int)(t / (uint32_t)ng), ee = own + ((int)(t % (uint32_t)ng) * ra.PG + best_g) * ra.P;
               uint32_t w;
-              while ((((w = __hip_atomic_load(&ra.progress[ee], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) & PG_STEPS) - ra.base) < (uint32_t)j) __builtin_amdgcn_s_sleep(8);
+              if (!rollout_wait_progress(ra, x, ee, (uint32_t)j, w)) break;     // (res_e is -4: this wave leaves)
               __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
               rollout_wait_actions(ra, x, own, best_g, (uint32_t)j);   // (another wave may have drawn the last published ticket in between: then this one is of the next step)
               const uint32_t last = w >> 23;
@@ -86,18 +104,20 @@ __device__ __forceinline__ void persist_loop(StepArgs a, RunArgs ra, const XchgA
             __hip_atomic_store(x.timeout, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             __hip_atomic_store(x.timeout_host, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             // give up on the policy: run what is left with whatever the slots hold (cc4_rollout_end reports it)
-            for (int g = 0; g < ra.PG && res_e == -4; ++g) {
+            bool stuck = false;
+            for (int g = 0; g < ra.PG && res_e == -4 && !stuck; ++g) {
               const int ng = (ne - g + ra.PG - 1) / ra.PG;
               if (ng <= 0) continue;
               const uint32_t t = __hip_atomic_fetch_add(tkl + g, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
               if (t + 1u == (uint32_t)(ng * ra.K)) __hip_atomic_store(ra.ticket_next + (size_t)own * TK_STRIDE + g, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
               if (t < (uint32_t)(ng * ra.K)) {
                 const int j = (int)(t / (uint32_t)ng), ee = own + ((int)(t % (uint32_t)ng) * ra.PG + g) * ra.P;
-                while (((__hip_atomic_load(&ra.progress[ee], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & PG_STEPS) - ra.base) < (uint32_t)j) __builtin_amdgcn_s_sleep(8);
+                uint32_t w;
+                if (!rollout_wait_progress(ra, x, ee, (uint32_t)j, w)) { stuck = true; break; }
                 res_e = ee; res_k = j; res_sh = 1;
               }
             }
-            if (res_e != -4) break;
+            if (res_e != -4 || stuck) break;
           }
         }
       }

@@ -30,6 +30,10 @@ int cc4_debug_stop_phase(cc4_handle* h, int phase);
 
 /* debug: where a rollout stands (see csrc/cc4_api.hip) */
 int cc4_debug_rollout_state(cc4_handle* h, int64_t* out /* [22] */);
+/* test hook: the persistent schedule's progress words as if `base` steps had run since they were last cleared (they are cleared when a call would take
+ * them past 0x700000): every episode's word = base, no last runner.  Sets up the persistent path if that was not done yet.  -2: no persistent
+ * kernel on this handle, a rollout in flight, or base > 0x700000. */
+int cc4_debug_persist_base(cc4_handle* h, uint32_t base);
 /* test hook: `bytes` bytes of device memory of this handle's device -- e.g. an action slot of a rollout (cc4_rollout_actions), packed observation rows
  * (cc4_rollout_obs_packed) -- copied to the host, behind everything enqueued on the handle's streams. */
 int cc4_debug_copy_from_device(cc4_handle* h, void* host_dst, const void* device_src, size_t bytes);

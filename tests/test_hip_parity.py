@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import golden_util as G
 from oracle_binding import OracleVecEnv, random_actions
+from rollout_util import hash_policy, pack_rows
 
 pytestmark = pytest.mark.gpu
 
@@ -374,27 +375,6 @@ def test_sampled_self_check_runs_by_default(monkeypatch):
     dev.close()
 
 
-def _pack_rows(obs):
-    """[n, 578] observation values (0 / 1 / 2) -> [n, 148] bytes, 2 bits per value, low bits first (CC4_OBS_PACKED_BYTES)."""
-    n = obs.shape[0]
-    v = np.zeros((n, 592), np.uint8)
-    v[:, :578] = obs.astype(np.uint8) & 3
-    v = v.reshape(n, 148, 4)
-    return (v[:, :, 0] | (v[:, :, 1] << 2) | (v[:, :, 2] << 4) | (v[:, :, 3] << 6)).astype(np.uint8)
-
-
-def _hash_policy(packed, j):
-    """numpy restatement of k_rollout_hash_policy (csrc/cc4_k_misc.hip): FNV-1a over the 37 words of an episode's packed observation row."""
-    w = np.ascontiguousarray(packed).view('<u4').astype(np.uint64)          # [n, 37]
-    h = np.full(w.shape[0], 2166136261, np.uint64)
-    for c in range(w.shape[1]):
-        h = ((h ^ w[:, c]) * np.uint64(16777619)) & np.uint64(0xFFFFFFFF)
-    out = np.zeros((w.shape[0], 5), np.int32)
-    for b in range(5):
-        out[:, b] = ((h + np.uint64(2654435761 * (b + 1)) + np.uint64(40503 * j)) & np.uint64(0xFFFFFFFF)) % np.uint64(242 if b == 4 else 82)
-    return out
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize('n,policy', [(8192, 'random'), (6656, 'hash'), (8192, 'hash')])
 def test_rollout_with_the_policy_in_the_loop_matches_the_oracle_at_every_step(n, policy):
@@ -414,8 +394,8 @@ def test_rollout_with_the_policy_in_the_loop_matches_the_oracle_at_every_step(n,
         dev.run_rollout(K, policy, seed0, t, native=(c % 2 == 1))        # (the passes enqueued from Python / by cc4_rollout_standin)
         acts = []
         for j in range(K):
-            a = random_actions(seed0, t + j, n) if policy == 'random' else _hash_policy(_pack_rows(o_prev), j)
-            assert np.array_equal(dev.rollout_obs_packed(j), _pack_rows(o_prev)), (K, j, 'the rows the policy of this step read')
+            a = random_actions(seed0, t + j, n) if policy == 'random' else hash_policy(pack_rows(o_prev), j)
+            assert np.array_equal(dev.rollout_obs_packed(j), pack_rows(o_prev)), (K, j, 'the rows the policy of this step read')
             o = ora.step_batch(a)
             o_prev = o[0].copy()
             acts.append(a)
