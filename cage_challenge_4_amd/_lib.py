@@ -76,6 +76,10 @@ SIGNATURES = {
     'cc4_stream_wait': (ctypes.c_int, [_P, _P]),
     'cc4_stream_signal': (ctypes.c_int, [_P, _P]),
     'cc4_policy_outputs': (ctypes.c_int, [_P, ctypes.c_int32, _P, _P, _P, _P, _P]),
+    'cc4_snapshot_bytes': (ctypes.c_size_t, [_P]),
+    'cc4_copy_episodes_device': (ctypes.c_int, [_P, ctypes.c_int32, _P, ctypes.c_int32, _P, _P, ctypes.c_int32, _P, _P]),
+    'cc4_copy_faults': (ctypes.c_int, [_P, _P]),
+    'cc4_clone_episodes': (ctypes.c_int, [_P, ctypes.c_int32, _P, _P, _P]),
     'cc4_rollout_begin': (ctypes.c_int, [_P, ctypes.c_int32]),
     'cc4_rollout_groups': (ctypes.c_int, [_P, _P, _P]),
     'cc4_rollout_policy_stream': (ctypes.c_int, [_P, _P]),

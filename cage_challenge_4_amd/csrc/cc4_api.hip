@@ -150,6 +150,10 @@ struct cc4_handle {
   bool philox_lean = false;       // k_step_philox1 (one wave per episode) instead of k_step_philox (cc4_create)
   int philox_minw = 1;            // which register budget of k_step_philox this batch size runs (1, 7 or 8 blocks per CU; cc4_create)
   ncclComm_t comm = nullptr; int rank = 0, world = 1;
+  // episode copies (cc4_copy_episodes_device): claim words of the episodes, the OR of the copies' fault bits, the per-episode "mask stale" marks
+  // k_policy_outputs honours; the host-array surface (cc4_clone_episodes) stages its indices and seeds in d_copy_idx
+  uint32_t* d_claim = nullptr; uint32_t* d_copy_fault = nullptr; uint8_t* d_mask_stale = nullptr;
+  int32_t* d_copy_idx = nullptr; uint64_t* d_copy_seeds = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   std::vector<hipEvent_t> evs;                   // timing events of cc4_run_random_steps: [group][2 * timed group of launches + {start, stop}]
   std::string err;
@@ -628,6 +632,11 @@ int cc4_create(const cc4_config* cfg, cc4_handle** out) {
   h->d_done = reinterpret_cast<uint8_t*>(h->d_err + n);
   HIPCHK(h, hipMalloc(&h->d_mask, n * MASK_TOTAL));
   HIPCHK(h, hipMalloc(&h->d_rng, n * 7 * sizeof(uint64_t)));
+  HIPCHK(h, hipMalloc(&h->d_claim, n * sizeof(uint32_t) + sizeof(uint32_t)));     // [n] claim words + the fault word
+  h->d_copy_fault = h->d_claim + n;
+  HIPCHK(h, hipMalloc(&h->d_mask_stale, n));
+  HIPCHK(h, hipMemsetAsync(h->d_claim, 0, n * sizeof(uint32_t) + sizeof(uint32_t), h->stream));
+  HIPCHK(h, hipMemsetAsync(h->d_mask_stale, 0, n, h->stream));
   HIPCHK(h, hipMemsetAsync(h->d_state, 0, n * sizeof(EnvState), h->stream));
   HIPCHK(h, hipMemsetAsync(h->d_cold, 0, n * h->cold_row, h->stream));
   HIPCHK(h, hipMemsetAsync(h->d_obs, 0, n * OBS_TOTAL * sizeof(int32_t), h->stream));
@@ -658,7 +667,7 @@ void cc4_destroy(cc4_handle* h) {
   if (h->rev) (void)hipEventDestroy(h->rev);
   for (void* p : {(void*)h->d_ract, (void*)h->d_rready, (void*)h->d_rcnt, (void*)h->d_rfail}) if (p) (void)hipFree(p);
   void* ptrs[] = {h->d_state, h->d_cold, h->small_io ? nullptr : (void*)h->d_actions, h->d_seeds, h->d_envmask, h->small_io ? nullptr : (void*)h->d_obs,
-                  h->d_mask, h->d_rng, h->d_reset_ws, h->d_ext, h->d_run, h->d_slot_part, h->d_pool};     // (d_msgs, d_reward, d_err, d_done live inside d_actions / d_obs; small handles: pinned host memory, freed below)
+                  h->d_mask, h->d_rng, h->d_reset_ws, h->d_ext, h->d_run, h->d_slot_part, h->d_pool, h->d_claim, h->d_mask_stale, h->d_copy_idx, h->d_copy_seeds};     // (d_msgs, d_reward, d_err, d_done live inside d_actions / d_obs; small handles: pinned host memory, freed below)
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (h->shadow) { cc4_destroy(h->shadow); h->shadow = nullptr; (void)hipSetDevice(h->cfg.device_id); }
   for (void* p : {(void*)h->d_prev_state, (void*)h->d_prev_cold, (void*)h->d_prev_out}) if (p) (void)hipFree(p);
@@ -1003,8 +1012,62 @@ int cc4_policy_outputs(cc4_handle* h, int32_t obs_dtype, void* d_obs, uint8_t* d
   // the observations are a streaming copy: enough blocks to fill the chip (8 per CU), each lane looping over what is left
   const int obs_blocks = (int)std::max(1LL, std::min((vecs + tpb - 1) / tpb, 8LL * h->cus));
   hipLaunchKernelGGL(k_policy_outputs, dim3(ep_blocks + obs_blocks), dim3(tpb), 0, h->stream, h->d_state, h->d_obs, h->d_reward, h->d_done, h->d_err,
-                     n, ep_blocks, (int)obs_dtype, d_obs, d_mask, d_reward, d_done, d_err);
+                     n, ep_blocks, (int)obs_dtype, d_obs, d_mask, d_reward, d_done, d_err, h->d_mask_stale);
   HIPCHK(h, hipGetLastError());
+  return 0;
+}
+// ---- episode copies (cc4_k_copy.hip).  Two launches on the main stream, no host synchronisation: k_copy_claim (one lane per entry) claims the
+// destinations with a stamp no other call of the process uses, k_copy_episodes (one workgroup per entry) checks the claims and copies.
+static std::atomic<uint32_t> g_copy_stamp{0};
+size_t cc4_snapshot_bytes(cc4_handle* h) { return h ? slot_bytes(h->cold_row) : 0; }
+int cc4_copy_episodes_device(cc4_handle* h, int32_t n, const void* d_src_bank, int32_t src_capacity, const int32_t* d_src,
+                             void* d_dst_bank, int32_t dst_capacity, const int32_t* d_dst, const uint64_t* d_seeds) {
+  const char* who = "cc4_copy_episodes_device";
+  if (n < 0 || (n > 0 && (!d_src || !d_dst))) { h->err = std::string(who) + ": n < 0, or no index arrays"; return -2; }
+  if (h->comm) { h->err = std::string(who) + ": not on a handle with a communicator"; return -2; }
+  if (h->rollout_k > 0) { h->err = std::string(who) + ": a rollout is in flight on this handle: cc4_rollout_end first"; return -2; }
+  if (d_src_bank && d_dst_bank) { h->err = std::string(who) + ": bank -> bank copies are not supported (one side must be the handle's episodes)"; return -2; }
+  if (d_seeds && d_dst_bank) { h->err = std::string(who) + ": seeds apply to copies into the handle's episodes only"; return -2; }
+  if ((d_src_bank && src_capacity < 0) || (d_dst_bank && dst_capacity < 0)) { h->err = std::string(who) + ": negative bank capacity"; return -2; }
+  if (reinterpret_cast<uintptr_t>(d_src_bank) % 64 || reinterpret_cast<uintptr_t>(d_dst_bank) % 64) { h->err = std::string(who) + ": a bank must be 64-byte aligned"; return -2; }
+  if (n == 0) return 0;
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  if (join_groups(h)) return -1;
+  h->prev_valid = false;        // (cc4_replay_logged would repeat a step from rows that have moved on)
+  uint32_t stamp = g_copy_stamp.fetch_add(1) % 0x7FFFFFFFu + 1u;     // 1 .. 2^31 - 1: claim words 2 * stamp and 2 * stamp + 1, never 0
+  CopyArgs a{h->d_state, h->d_cold, h->cold_row, h->d_obs, h->d_reward, h->d_done, h->d_err, h->d_mask, h->d_mask_stale, h->d_claim,
+             static_cast<const uint8_t*>(d_src_bank), static_cast<uint8_t*>(d_dst_bank), slot_bytes(h->cold_row), d_src, d_dst, d_seeds,
+             n, h->cfg.num_envs, d_src_bank ? src_capacity : h->cfg.num_envs, d_dst_bank ? dst_capacity : h->cfg.num_envs,
+             h->cfg.steps, h->cfg.rng_mode, h->evlog_on, stamp, h->d_copy_fault};
+  hipLaunchKernelGGL(k_copy_claim, dim3((n + 255) / 256), dim3(256), 0, h->stream, a);
+  HIPCHK(h, hipGetLastError());
+  hipLaunchKernelGGL(k_copy_episodes, dim3(n), dim3(256), 0, h->stream, a);
+  HIPCHK(h, hipGetLastError());
+  if (h->ngroups > 1) h->main_ahead = true;      // the group streams follow at their next launch
+  return 0;
+}
+int cc4_copy_faults(cc4_handle* h, uint32_t* out) {
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  if (join_groups(h)) return -1;
+  HIPCHK(h, hipMemcpyAsync(out, h->d_copy_fault, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemsetAsync(h->d_copy_fault, 0, sizeof(uint32_t), h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return 0;
+}
+int cc4_clone_episodes(cc4_handle* h, int32_t n, const int32_t* src, const int32_t* dst, const uint64_t* seeds) {
+  if (n < 0 || n > h->cfg.num_envs) { h->err = "cc4_clone_episodes: n must be 0 .. num_envs"; return -2; }
+  if (n == 0) return 0;
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  if (h->rollout_k > 0) { h->err = "cc4_clone_episodes: a rollout is in flight on this handle: cc4_rollout_end first"; return -2; }
+  if (join_groups(h)) return -1;
+  const size_t N = (size_t)h->cfg.num_envs;
+  if (!h->d_copy_idx) HIPCHK(h, hipMalloc(&h->d_copy_idx, 2 * N * sizeof(int32_t)));
+  if (seeds && !h->d_copy_seeds) HIPCHK(h, hipMalloc(&h->d_copy_seeds, N * sizeof(uint64_t)));
+  HIPCHK(h, hipMemcpyAsync(h->d_copy_idx, src, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(h->d_copy_idx + N, dst, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+  if (seeds) HIPCHK(h, hipMemcpyAsync(h->d_copy_seeds, seeds, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
+  if (int rc = cc4_copy_episodes_device(h, n, nullptr, 0, h->d_copy_idx, nullptr, 0, h->d_copy_idx + N, seeds ? h->d_copy_seeds : nullptr)) return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));     // (the host arrays may go away once the call returns)
   return 0;
 }
 int cc4_synchronize(cc4_handle* h) {

@@ -112,11 +112,12 @@ __global__ void k_unpack_obs(const uint8_t* __restrict__ packed, uint8_t* __rest
 //   blocks [0, ep_blocks): one lane per episode -- reward, done, error word, and the action-mask row of every episode whose row was
 //     (re)generated since its last step (step_count 0: cc4_reset, or the in-kernel autoreset of the step just taken); the wave ballots
 //     those and rebuilds each one's 570 entries with all 64 lanes (blue_mask_slot, the rule of blue_action_mask).  Mask rows of the other
-//     episodes are left as they are: a mask is a function of the scenario alone, so the caller's buffer is persistent.
+//     episodes are left as they are: a mask is a function of the scenario alone, so the caller's buffer is persistent.  Rows of episodes
+//     that a copy overwrote (cc4_copy_episodes_device: the handle's per-episode "mask stale" mark) are rebuilt as well, and their marks cleared.
 //   blocks [ep_blocks, grid): the observations as ONE flat array of n * 578 int32 values (a 2312-byte row is not 16-byte aligned, the
 //     flat array is), grid-stride, one int4 load and one store of the four converted values per lane (4 / 8 / 8 / 16 bytes).  Every value is
 //     0, 1 or 2 (CC4_OBS_PACKED_BYTES), so every dtype is exact; half and bfloat16 bit patterns come from a 4-entry table in one constant.
-// Reads the handle's buffers, never writes them.
+// Reads the handle's buffers; of its own it writes only the mask-stale marks.
 // float16 (0, 1, 2, 3 -> 0x0000 0x3C00 0x4000 0x4200) / bfloat16 (-> 0x0000 0x3F80 0x4000 0x4040): the bit pattern of a value out of one constant
 template <int DT> __device__ __forceinline__ uint32_t policy_half_bits(int x) {
   constexpr uint64_t tab = DT == 1 ? 0x420040003C000000ull : 0x404040003F800000ull;
@@ -147,13 +148,14 @@ template <int DT> __device__ __forceinline__ void policy_obs_part(const int32_t*
 __global__ __launch_bounds__(256) void k_policy_outputs(const EnvState* __restrict__ st, const int32_t* __restrict__ obs, const float* __restrict__ reward,
                                                         const uint8_t* __restrict__ done, const uint32_t* __restrict__ err, int n, int ep_blocks, int dtype,
                                                         void* __restrict__ out_obs, uint8_t* __restrict__ out_mask, float* __restrict__ out_reward,
-                                                        uint8_t* __restrict__ out_done, int32_t* __restrict__ out_err) {
+                                                        uint8_t* __restrict__ out_done, int32_t* __restrict__ out_err, uint8_t* __restrict__ mask_stale) {
   if ((int)blockIdx.x < ep_blocks) {
     const int e = (int)(blockIdx.x * blockDim.x + threadIdx.x), lane = (int)threadIdx.x & (WAVE - 1);
     bool regen = false;
     if (e < n) {
       out_reward[e] = reward[e]; out_done[e] = done[e]; out_err[e] = (int32_t)err[e];
       regen = st[e].step_count == 0;
+      if (mask_stale[e]) { regen = true; mask_stale[e] = 0; }     // a copy of another episode landed here (k_copy_episodes)
     }
     unsigned long long todo = __ballot(regen);
     while (todo) {
@@ -179,17 +181,11 @@ __global__ __launch_bounds__(256) void k_policy_outputs(const EnvState* __restri
   }
 }
 
-// CybORG.set_seed (env.py:316-325): a fresh generator for the controller, the state and the hosts; the agents' policies keep
-// the old one until the next reset (EnvCold.rng2); the episode itself stays as it is
+// CybORG.set_seed (env.py:316-325) on every episode (episode_set_seed)
 __global__ void k_set_seed(EnvState* st, EnvCold* cold, size_t cold_row, const uint64_t* seeds, int n, int rng_mode) {
   int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= n) return;
-  if (rng_mode == 0) {        // numpy stream: the agents' policies stay on the stream they were created with (see EnvCold.rng2)
-    if (!st[e].rng_split) cold_at(cold, (size_t)e, cold_row)->rng2 = st[e].rng;
-    st[e].rng_split = 1;
-  }
-  rng_seed(&st[e].rng, seeds[e], (uint32_t)rng_mode);
-  if (rng_mode == 1) { rng_begin_episode(&st[e].rng); rng_park(&st[e].rng); }   // counter mode: the words a reset leaves behind
+  episode_set_seed(st + e, cold_at(cold, (size_t)e, cold_row), seeds[e], rng_mode);
 }
 
 // an externally built numpy Generator(PCG64) handed over as CybORG(seed=generator) (env.py:73-76): its bit-generator state

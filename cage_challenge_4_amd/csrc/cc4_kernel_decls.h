@@ -37,7 +37,10 @@ __global__ void k_unpack_obs(const uint8_t* __restrict__ packed, uint8_t* __rest
 __global__ void k_policy_outputs(const EnvState* __restrict__ st, const int32_t* __restrict__ obs, const float* __restrict__ reward,
                                  const uint8_t* __restrict__ done, const uint32_t* __restrict__ err, int n, int ep_blocks, int dtype,
                                  void* __restrict__ out_obs, uint8_t* __restrict__ out_mask, float* __restrict__ out_reward,
-                                 uint8_t* __restrict__ out_done, int32_t* __restrict__ out_err);
+                                 uint8_t* __restrict__ out_done, int32_t* __restrict__ out_err, uint8_t* __restrict__ mask_stale);
+// episode copies (cc4_k_copy.hip): phase 1 claims the destinations, phase 2 copies the live extents
+__global__ void k_copy_claim(CopyArgs a);
+__global__ void k_copy_episodes(CopyArgs a);
 __global__ void k_set_seed(EnvState* st, EnvCold* cold, size_t cold_row, const uint64_t* seeds, int n, int rng_mode);
 __global__ void k_set_rng_state(EnvState* st, const uint64_t* w, int n);
 __global__ void k_rng_state(const EnvState* st, uint64_t* out, int n);

@@ -7,6 +7,7 @@
 //   cc4_k_run1.hip     the persistent kernel of large batches: k_run_philox1 (cc4_persist.h: its schedule, shared with k_run_pcg)
 //   cc4_k_run1x.hip    its other builds: k_run_philox1x (beside RCCL), k_run_philox1r (rollouts with the policy in the loop)
 //   cc4_k_misc.hip     k_reset and the small helpers (exchange gate, CU discovery, stand-in policies, digest, ...)
+//   cc4_k_copy.hip     episode copies: k_copy_claim, k_copy_episodes (cc4_copy_episodes_device)
 // No MFMA anywhere: the path is integer / indexing.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -369,6 +370,45 @@ struct ResetArgs {
   int n, steps, rng_mode, policy;
   uint32_t topo;
   uint8_t* obs8;               // packed exchange row of the reset observations (multi-GPU), or null
+};
+// CybORG.set_seed (env.py:316-325) applied to one episode: a fresh generator for the controller, the state and the hosts; the agents'
+// policies keep the old one until the next reset (EnvCold.rng2); the episode itself stays as it is.  k_set_seed and the reseed of
+// k_copy_episodes.
+__device__ __forceinline__ void episode_set_seed(EnvState* s, EnvCold* c, uint64_t seed, int rng_mode) {
+  if (rng_mode == 0) {        // numpy stream: the agents' policies stay on the stream they were created with (see EnvCold.rng2)
+    if (!s->rng_split) c->rng2 = s->rng;
+    s->rng_split = 1;
+  }
+  rng_seed(&s->rng, seed, (uint32_t)rng_mode);
+  if (rng_mode == 1) { rng_begin_episode(&s->rng); rng_park(&s->rng); }   // counter mode: the words a reset leaves behind
+}
+// ---- episode copies (cc4_copy_episodes_device, cc4_k_copy.hip).  A snapshot slot of a bank: [SlotHdr | hot row | cold row (padded to 64 bytes) |
+// outputs: packed observation row, reward, error word, done (padded to 64 bytes)]; offsets only, no pointers: a bank may travel through host memory.
+struct alignas(16) SlotHdr {
+  uint32_t magic, version;     // SLOT_MAGIC / SLOT_VERSION: a slot that was never written has neither
+  int32_t steps, rng_mode;     // of the handle that wrote it: a load into a handle of another configuration is refused
+  uint32_t claim;              // phase 1 of a save claims its destination slots here (0 once written)
+  uint32_t pad[11];
+};
+static_assert(sizeof(SlotHdr) == 64, "64-byte slot header");
+constexpr uint32_t SLOT_MAGIC = 0x45344343u;   // "CC4E"
+constexpr uint32_t SLOT_VERSION = (1u << 24) | (uint32_t)((sizeof(EnvState) + sizeof(EnvCold)) & 0xFFFFFFu);   // a layout change changes it
+constexpr size_t SLOT_OUT_BYTES = 192;         // OBS_PACKED + reward + err + done, rounded up to 64
+CC4_HD size_t slot_cold_off() { return sizeof(SlotHdr) + sizeof(EnvState); }
+CC4_HD size_t slot_out_off(size_t cold_row) { return slot_cold_off() + ((cold_row + 63) & ~(size_t)63); }
+CC4_HD size_t slot_bytes(size_t cold_row) { return slot_out_off(cold_row) + SLOT_OUT_BYTES; }
+static_assert(OBS_PACKED + 12 <= (int)SLOT_OUT_BYTES && sizeof(SlotHdr) % 64 == 0 && sizeof(EnvState) % 64 == 0, "slot layout");
+enum : uint32_t { CF_RANGE = CC4_COPY_RANGE, CF_DUP_DST = CC4_COPY_DUP_DST, CF_SRC_IS_DST = CC4_COPY_SRC_IS_DST, CF_SLOT_EMPTY = CC4_COPY_SLOT_EMPTY,
+                  CF_SLOT_CONFIG = CC4_COPY_SLOT_CONFIG };   // cc4_copy_faults bits
+struct CopyArgs {
+  EnvState* st; EnvCold* cold; size_t cold_row;          // the handle's episodes
+  int32_t* obs; float* reward; uint8_t* done; uint32_t* err; uint8_t* mask; uint8_t* mask_stale;
+  uint32_t* claim;                                       // [n] claim words of the handle's episodes
+  const uint8_t* src_bank; uint8_t* dst_bank; size_t slot;   // banks (null: the handle's episodes), bytes per slot
+  const int32_t* src; const int32_t* dst; const uint64_t* seeds;
+  int count, n, src_cap, dst_cap, steps, rng_mode, evlog_on;
+  uint32_t stamp;                                        // this call's claims: 2 * stamp (one entry names it), 2 * stamp + 1 (several)
+  uint32_t* fault;
 };
 // the step bodies (defined in cc4_k_pcg.hip / cc4_philox1_body.h; declared here for the persistent schedule, cc4_persist.h)
 template <bool LOG> __device__ __forceinline__ void pcg_body(StepArgs a, const int e, const int lane, const bool first = true, const bool last = true);

@@ -318,4 +318,43 @@ CC4_HD const uint32_t* cold_povf(const EnvCold* c, int steps, int h) {
   return reinterpret_cast<const uint32_t*>(c + 1) + (size_t)NBLUE * (size_t)cold_sus_cap(steps) + (size_t)h * (size_t)cold_povf_cap(steps);
 }
 
+// The LIVE extents of a cold row: what a copy of the episode (cc4_copy_episodes_device) moves.  Everything else in the row is dead --
+// written before it is read again by every path that uses it -- and keeps whatever the destination held:
+//   CS_HS      hs (+ hs_pad)                              CS_EVHDR  the evlog header
+//   CS_EVREC   evlog.rec[0, n) when the log is on         CS_TAIL   xrate, gfail, known_sid, rng2 (contiguous: the end of the fixed part)
+//   CS_EPH     eph whole, numpy-stream mode only (eph_port / eph_clear return at once in the counter mode)
+//   CS_FIXED + i                  kports[i] for the pool slots i set in spool_used (rs_add clears the row of a new abstract session)
+//   CS_FIXED + RS_POOL + b        sus[b][0, blue[b].nsus)
+//   CS_FIXED + RS_POOL + NBLUE + h  povf[h][0, nproc(h) - PIN) for hosts with nproc > PIN
+// Counts are clamped to the containers' capacities (a copy never leaves the row whatever the hot row says).  Every span starts 16-byte
+// aligned; its length is a multiple of 4 bytes.
+enum : int { CS_HS = 0, CS_EVHDR = 1, CS_EVREC = 2, CS_TAIL = 3, CS_EPH = 4, CS_FIXED = 5, COLD_SPANS = CS_FIXED + RS_POOL + NBLUE + MAXH };
+struct ColdSpan { uint32_t off, bytes; };
+CC4_HD ColdSpan cold_live_span(const EnvState* s, int steps, int rng_mode, int evlog_on, uint32_t ev_n, int k) {
+  constexpr uint32_t o_ev = (uint32_t)offsetof(EnvCold, evlog), o_tail = (uint32_t)offsetof(EnvCold, xrate);
+  static_assert(offsetof(EnvCold, eph) % 16 == 0 && offsetof(EnvCold, evlog) % 16 == 0 && offsetof(EnvCold, kports) % 16 == 0 &&
+                offsetof(EnvCold, xrate) % 16 == 0 && (MAXH + 7) % 16 == 0 && offsetof(EvLog, rec) == 16, "live spans start 16-byte aligned");
+  static_assert(offsetof(EnvCold, gfail) > offsetof(EnvCold, xrate) && offsetof(EnvCold, known_sid) > offsetof(EnvCold, gfail) &&
+                offsetof(EnvCold, rng2) > offsetof(EnvCold, known_sid), "xrate .. rng2 close the fixed part");
+  if (k == CS_HS) return {0u, (uint32_t)offsetof(EnvCold, eph)};
+  if (k == CS_EVHDR) return {o_ev, 16u};
+  if (k == CS_EVREC) return {o_ev + 16u, evlog_on ? (uint32_t)sizeof(EvRec) * (ev_n < (uint32_t)MAX_EV ? ev_n : (uint32_t)MAX_EV) : 0u};
+  if (k == CS_TAIL) return {o_tail, (uint32_t)sizeof(EnvCold) - o_tail};
+  if (k == CS_EPH) return {(uint32_t)offsetof(EnvCold, eph), rng_mode == 0 ? (uint32_t)sizeof(EnvCold::eph) : 0u};
+  k -= CS_FIXED;
+  if (k < RS_POOL) {
+    const bool used = (s->spool_used[k >> 5] >> (k & 31)) & 1u;
+    return {(uint32_t)offsetof(EnvCold, kports) + (uint32_t)k * (uint32_t)(MAXH + 7), used ? (uint32_t)(MAXH + 7) : 0u};
+  }
+  k -= RS_POOL;
+  const uint32_t scap = (uint32_t)cold_sus_cap(steps), pcap = (uint32_t)cold_povf_cap(steps);
+  if (k < NBLUE) {
+    const uint32_t ns = s->blue[k].nsus;
+    return {(uint32_t)sizeof(EnvCold) + 4u * scap * (uint32_t)k, 4u * (ns < scap ? ns : scap)};
+  }
+  k -= NBLUE;
+  const uint32_t np = s->hd[k].nproc, nx = np > (uint32_t)PIN ? np - (uint32_t)PIN : 0u;
+  return {(uint32_t)sizeof(EnvCold) + 4u * (scap * (uint32_t)NBLUE + pcap * (uint32_t)k), 4u * (nx < pcap ? nx : pcap)};
+}
+
 }  // namespace cc4

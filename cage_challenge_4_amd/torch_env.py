@@ -9,7 +9,7 @@ import ctypes
 import numpy as np
 import torch
 from . import _lib as L
-from .vec_env import CC4VecEnv, split_obs, split_mask  # noqa: F401  (split_obs / split_mask slice tensors too)
+from .vec_env import CC4VecEnv, raise_on_copy_faults, split_obs, split_mask  # noqa: F401  (split_obs / split_mask slice tensors too)
 
 _OBS_DTYPES = {torch.uint8: 0, torch.float16: 1, torch.bfloat16: 2, torch.float32: 3}
 
@@ -35,8 +35,20 @@ class CC4TorchVecEnv:
     step in it (reward 0, the new scenario's first observation and action mask).  The action masks are refreshed for exactly the
     episodes a call (re)generated, on the device.
 
+    Episode copies on the device (branching, undo, checkpoints; include/cc4.h cc4_copy_episodes_device):
+    new_bank(capacity)                         -> uint8 tensor [capacity, snapshot_bytes] of never-written snapshot slots on the env's device
+    clone_episodes(src, dst, seeds=None)       -> (obs, info)   episode dst[i] becomes a copy of episode src[i]
+    save_episodes(env_ids, bank, slots)        -> (obs, info)   slot slots[i] of bank holds episode env_ids[i]
+    load_episodes(bank, slots, env_ids, seeds=None) -> (obs, info)   episode env_ids[i] becomes the episode saved in slot slots[i]
+        Index arguments are integer tensors on the device (any integer dtype), seeds an optional [n] int64 / uint64 tensor (cc4_set_seed applied
+        to the copy).  A copy carries the episode's outputs: obs, reward, done, err and the action mask of a destination are its source's at
+        once.  A slot holds no pointers: bank.cpu() and back, or into another env of the same steps and rng_mode, restores the episodes exactly.
+        Faulty entries (an index out of range, a duplicated destination, a source that is also a destination, a slot never written or written
+        by another configuration) are skipped; check_errors() raises CC4EngineError for them.
+
     No call synchronises except check_errors(), which reads the error flags and raises what CC4VecEnv raises (ValueError for a step past
-    the episode's end -- the reference's own error -- and CC4EngineError for any other flag; strict=False: the ValueError only)."""
+    the episode's end -- the reference's own error -- and CC4EngineError for any other flag; strict=False: the ValueError only), and raises
+    CC4EngineError for the faults of the copies since the last call."""
 
     def __init__(self, num_envs, *, obs_dtype=torch.uint8, **kw):
         if obs_dtype not in _OBS_DTYPES:
@@ -55,6 +67,7 @@ class CC4TorchVecEnv:
             self.done = torch.zeros(n, dtype=torch.bool, **z)
             self.err = torch.zeros(n, dtype=torch.int32, **z)
             self._actions = torch.zeros((n, L.NUM_BLUE), dtype=torch.int32, **z)
+            self._fresh = torch.zeros(n, dtype=torch.uint8, **z)     # episodes a copy overwrote since the last check_errors (strict mode: new episodes)
             self._messages = torch.zeros((n, L.NUM_BLUE, L.MSG_LEN), dtype=torch.uint8, **z)
         vp = ctypes.c_void_p
         self._p_out = (vp(self.obs.data_ptr()), vp(self.action_mask.data_ptr()), vp(self.reward.data_ptr()), vp(self.done.data_ptr()),
@@ -109,9 +122,70 @@ class CC4TorchVecEnv:
             self._outputs(sp)
         return self.obs, self.reward, self.done, self._info()
 
+    @property
+    def snapshot_bytes(self):
+        """cc4_snapshot_bytes: bytes of one snapshot slot (header, hot row, cold row, the outputs of the last step)."""
+        return int(self.lib.cc4_snapshot_bytes(self._h))
+
+    def new_bank(self, capacity):
+        return torch.zeros((int(capacity), self.snapshot_bytes), dtype=torch.uint8, device=self.device)
+
+    def _index(self, x, what):
+        if not torch.is_tensor(x) or x.dim() != 1 or x.dtype.is_floating_point or x.dtype == torch.bool or x.device != self.device:
+            raise ValueError(f'{what} must be a 1-D integer tensor on {self.device}')
+        return x.to(torch.int32).contiguous()       # (on the current stream, as step() casts its actions)
+
+    def _bank(self, bank):
+        if (not torch.is_tensor(bank) or bank.dtype != torch.uint8 or bank.dim() != 2 or bank.shape[1] != self.snapshot_bytes
+                or not bank.is_contiguous() or bank.device != self.device):
+            raise ValueError(f'a bank is a contiguous uint8 tensor [capacity, {self.snapshot_bytes}] on {self.device} (new_bank)')
+        return ctypes.c_void_p(bank.data_ptr()), int(bank.shape[0])
+
+    def _copy(self, src, dst, src_bank=None, dst_bank=None, seeds=None):
+        with torch.cuda.device(self.device):
+            s = torch.cuda.current_stream(self.device)
+            src, dst = self._index(src, 'source indices'), self._index(dst, 'destination indices')
+            if src.shape != dst.shape:
+                raise ValueError('source and destination indices must have the same length')
+            sb, sc = self._bank(src_bank) if src_bank is not None else (None, 0)
+            db, dc = self._bank(dst_bank) if dst_bank is not None else (None, 0)
+            sd = None
+            if seeds is not None:
+                if not torch.is_tensor(seeds) or seeds.shape != src.shape or seeds.device != self.device:
+                    raise ValueError('seeds must be a tensor with one entry per copy on the env\'s device')
+                seeds = (seeds.view(torch.int64) if seeds.dtype == torch.uint64 else seeds.to(torch.int64)).contiguous()
+                sd = ctypes.c_void_p(seeds.data_ptr())
+            lib, h, sp = self.lib, self._h, ctypes.c_void_p(s.cuda_stream)
+            rc = lib.cc4_stream_wait(h, sp) or lib.cc4_copy_episodes_device(h, int(src.numel()), sb, sc, ctypes.c_void_p(src.data_ptr()), db, dc,
+                                                                               ctypes.c_void_p(dst.data_ptr()), sd)
+            if rc:
+                self.venv._chk(rc, 'cc4_copy_episodes_device')
+            self._outputs(sp)
+            if dst_bank is None and dst.numel():
+                valid = (dst >= 0) & (dst < self.num_envs)
+                self._fresh.scatter_reduce_(0, dst.clamp(0, self.num_envs - 1).long(), valid.to(torch.uint8), 'amax')
+        return self.obs, self._info()
+
+    def clone_episodes(self, src, dst, seeds=None):
+        return self._copy(src, dst, seeds=seeds)
+
+    def save_episodes(self, env_ids, bank, slots):
+        return self._copy(env_ids, slots, dst_bank=bank)
+
+    def load_episodes(self, bank, slots, env_ids, seeds=None):
+        return self._copy(slots, env_ids, src_bank=bank, seeds=seeds)
+
     def check_errors(self):
         """The one synchronising call: reads the error flags of the last step / reset and raises what CC4VecEnv.step would have raised
-        (strict mode: each engine flag once per episode, a step past the end every time)."""
+        (strict mode: each engine flag once per episode, a step past the end every time; an episode a copy overwrote counts as a new
+        one); before that, CC4EngineError for the faults of the episode copies since the last call."""
+        faults = ctypes.c_uint32(0)
+        self.venv._chk(self.lib.cc4_copy_faults(self._h, ctypes.byref(faults)), 'cc4_copy_faults')
+        fresh = self._fresh.cpu().numpy().astype(bool)
+        if fresh.any():
+            self.venv._err_seen[fresh] = 0
+            self._fresh.zero_()
+        raise_on_copy_faults(faults.value)
         self.venv._err[:] = self.err.cpu().numpy().view(np.uint32)
         self.venv._check_err()
 

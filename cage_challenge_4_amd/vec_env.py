@@ -28,6 +28,10 @@ def pcg64_words(gen):
             int(st['has_uint32']), int(st['uinteger'])]
 
 
+COPY_FAULT_NAMES = {0: 'INDEX_OUT_OF_RANGE', 1: 'DUPLICATED_DESTINATION', 2: 'SOURCE_IS_DESTINATION', 3: 'SLOT_NEVER_WRITTEN',
+                    4: 'SLOT_OF_ANOTHER_CONFIGURATION'}     # cc4_copy_faults bits (include/cc4.h CC4_COPY_*)
+
+
 class CC4EngineError(RuntimeError):
     """An episode left the part of the reference's behaviour the engine reproduces (a fixed-size container overflowed, or the
     reference itself would have crashed): its results can no longer be trusted to equal the reference's."""
@@ -35,6 +39,13 @@ class CC4EngineError(RuntimeError):
 
 def err_names(bits):
     return [ERR_NAMES.get(i, f'bit{i}') for i in range(32) if (int(bits) >> i) & 1]
+
+
+def raise_on_copy_faults(bits):
+    """bits: cc4_copy_faults.  The faulty entries of an episode copy were skipped (their destinations are unchanged); the others took effect."""
+    if bits:
+        names = [COPY_FAULT_NAMES.get(i, f'bit{i}') for i in range(32) if (int(bits) >> i) & 1]
+        raise CC4EngineError(f"episode copy faults {names}: the faulty entries were skipped, the others applied (include/cc4.h CC4_COPY_*)")
 
 
 def raise_on_engine_error(err):
@@ -344,6 +355,32 @@ class CC4VecEnv:
         cold = np.ascontiguousarray(cold, dtype=np.uint8)
         assert cold.size == self.lib.cc4_cold_bytes(self._h)
         self._chk(self.lib.cc4_set_cold(self._h, int(env), cold.ctypes.data_as(ctypes.c_void_p)), 'cc4_set_cold')
+
+    def clone_episodes(self, src, dst, seeds=None):
+        """Episode dst[i] becomes a copy of episode src[i] (cc4_clone_episodes: the device copy of cc4_copy_episodes_device, include/cc4.h);
+        seeds: optional uint64 per entry, cc4_set_seed applied to the copy.  Faulty entries (an index out of range, a duplicated
+        destination, a source that is also a destination) are skipped and raise CC4EngineError after the others applied.  Outputs and
+        masks are fetched again; returns the observations.  A copied episode counts as a new one for strict mode."""
+        src = np.ascontiguousarray(src, dtype=np.int32).ravel()
+        dst = np.ascontiguousarray(dst, dtype=np.int32).ravel()
+        if src.shape != dst.shape:
+            raise ValueError('src and dst must have the same length')
+        sp = None
+        if seeds is not None:
+            seeds = np.ascontiguousarray(seeds, dtype=np.uint64).ravel()
+            if seeds.shape != src.shape:
+                raise ValueError('seeds must have one entry per copy')
+            sp = seeds.ctypes.data_as(ctypes.c_void_p)
+        vp = ctypes.c_void_p
+        self._chk(self.lib.cc4_clone_episodes(self._h, int(src.size), src.ctypes.data_as(vp), dst.ctypes.data_as(vp), sp), 'cc4_clone_episodes')
+        faults = ctypes.c_uint32(0)
+        self._chk(self.lib.cc4_copy_faults(self._h, ctypes.byref(faults)), 'cc4_copy_faults')
+        ok = dst[(dst >= 0) & (dst < self.num_envs)]
+        self._err_seen[ok] = 0
+        self._chk(self.lib.cc4_fetch(self._h, *self._p_out), 'cc4_fetch')
+        self._chk(self.lib.cc4_get_action_mask(self._h, self._mask.ctypes.data_as(vp)), 'cc4_get_action_mask')
+        raise_on_copy_faults(faults.value)
+        return self._check_err()[0]
 
     # device-resident loop used by bench.py
     def run_random_steps(self, seed0, t0, k, timed=True):
