@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get('CC4_LIB') or os.path.join(_HERE, 'libcc4.so')   # CC4
 
 OBS_PER_ENV = 578
 MASK_PER_ENV = 570
+OBS_PACKED_BYTES = 148     # CC4_OBS_PACKED_BYTES: a flat observation at 2 bits per value
 NUM_BLUE = 5
 MSG_LEN = 8
 TOPOLOGY_BYTES = 27 + 2 * 137
@@ -95,6 +96,9 @@ SIGNATURES = {
     'cc4_debug_comm_delay_us': (ctypes.c_int, [_P, ctypes.c_int]),
     'cc4_host_stats': (ctypes.c_int, [_P, _P]),
     'cc4_verify_stats': (ctypes.c_int, [_P, _P]),
+    'cc4_run_plan_device': (ctypes.c_int, [_P, ctypes.c_int32, _P, _P, _P, _P, _P]),
+    'cc4_plan_kernel_for': (ctypes.c_char_p, [_P, ctypes.c_int32]),
+    'cc4_unpack_rows_device': (ctypes.c_int, [_P, ctypes.c_int64, _P, ctypes.c_int32, _P]),
     'cc4_state_bytes': (ctypes.c_size_t, []),
     'cc4_hot_bytes': (ctypes.c_size_t, []),
     'cc4_step_kernel': (ctypes.c_char_p, [_P]),

@@ -134,6 +134,7 @@ struct cc4_handle {
   uint64_t persist_calls = 0;
   cc4_handle* shadow = nullptr;
   uint64_t* d_digest = nullptr;   // [num_envs] per-episode digest
+  uint32_t* d_plan_err = nullptr; // [num_envs] cc4_run_plan_device: the error flags the steps of the call in flight raised (zero between calls)
   long long verify_calls = 0, verify_mismatches = 0;
   int persist_min_k = 10;         // shorter calls keep the per-step launches: a launch's ramp and tail cost a few steps' worth (with the tail's items shared
                                   // among the CUs of an XCD: K = 10: 733 vs 685 M, K = 20: 813 vs 742 M, K = 32: 857 vs 756 M; CC4_PERSIST_MIN_K)
@@ -672,6 +673,7 @@ void cc4_destroy(cc4_handle* h) {
   if (h->shadow) { cc4_destroy(h->shadow); h->shadow = nullptr; (void)hipSetDevice(h->cfg.device_id); }
   for (void* p : {(void*)h->d_prev_state, (void*)h->d_prev_cold, (void*)h->d_prev_out}) if (p) (void)hipFree(p);
   if (h->d_digest) (void)hipFree(h->d_digest);
+  if (h->d_plan_err) (void)hipFree(h->d_plan_err);
   if (h->pin_in) (void)hipHostFree(h->pin_in);
   if (h->pin_out) (void)hipHostFree(h->pin_out);
   for (int b = 0; b < cc4_handle::OBS_RING; ++b) { if (h->d_obs8[b]) (void)hipFree(h->d_obs8[b]); if (h->d_all_obs8[b]) (void)hipFree(h->d_all_obs8[b]); }
@@ -1354,7 +1356,8 @@ int cc4_run_random_steps(cc4_handle* h, uint64_t seed0, uint32_t t0, int32_t k, 
 int cc4_verify_stats(cc4_handle* h, int64_t* out /* [2] */) { out[0] = h->verify_calls; out[1] = h->verify_mismatches; return 0; }
 // One launch of the persistent kernel for k steps of the whole batch (cc4_run_random_steps form 3; cc4_rollout_begin with rollout = true: every step
 // an item of its own, the actions from the rollout's slots behind the caller's publishes).
-static int persist_launch(cc4_handle* h, StepArgs a, int k, uint32_t t0, const XchgArgs& x, hipEvent_t e0, hipEvent_t e1, bool rollout) {
+// pl: a plan call (cc4_run_plan_device) -- the plan builds k_run_philox1p / k_run_pcgp on the same schedule, tickets and progress words.
+static int persist_launch(cc4_handle* h, StepArgs a, int k, uint32_t t0, const XchgArgs& x, hipEvent_t e0, hipEvent_t e1, bool rollout, const PlanArgs* pl = nullptr) {
   if (h->pool_base + (uint32_t)k > 0x700000u) {      // (the progress words count steps since they were last cleared)
     HIPCHK(h, hipMemsetAsync(h->d_run, 0, h->run_words * sizeof(uint32_t), h->stream));
     h->pool_base = 0;
@@ -1385,6 +1388,10 @@ static int persist_launch(cc4_handle* h, StepArgs a, int k, uint32_t t0, const X
     ra.act_ready = h->d_rready; ra.act = h->d_ract; ra.PG = h->rpg;
     ra.act_wait_ticks = (long long)h->rollout_watchdog_ms * (h->khz > 0 ? h->khz : 100000);
   }
+  if (pl) {
+    if (h->cfg.rng_mode == 0) hipExtLaunchKernelGGL(k_run_pcgp, dim3(h->run_grid), dim3(WAVE), offsetof(EnvState, hd), h->stream, e0, e1, 0, a, ra, *pl);
+    else hipExtLaunchKernelGGL(k_run_philox1p, dim3(h->run_grid), dim3(WAVE), offsetof(EnvState, hd), h->stream, e0, e1, 0, a, ra, *pl);
+  } else
   if (h->cfg.rng_mode == 0) hipExtLaunchKernelGGL(k_run_pcg, dim3(h->run_grid), dim3(WAVE), offsetof(EnvState, hd), h->stream, e0, e1, 0, a, ra, x);
   else
   if (h->comm) hipExtLaunchKernelGGL(k_run_philox1x, dim3(h->run_grid), dim3(WAVE), offsetof(EnvState, hd), h->stream, e0, e1, 0, a, ra, x);
@@ -1600,6 +1607,154 @@ static int run_random_steps_impl(cc4_handle* h, uint64_t seed0, uint32_t t0, int
     *ms_step_kernels = worst;
     if (hp) fprintf(stderr, "[cc4 host prof] reading the timing events: %.1f us\n", std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - p1).count());
   }
+  return 0;
+}
+// ---- cc4_run_plan_device (include/cc4.h): k steps with the blue actions of step j from row j of a plan on the device.  Two forms: ONE launch
+// of the persistent kernel's plan build (k_run_philox1p / k_run_pcgp: PlanArgs) where cc4_run_random_steps would take the persistent form, else k
+// launches of the step kernel, each followed by k_plan_collect (the step's trajectory row).  Neither waits on the host.
+// 1: a plan call of k steps takes the one-launch form on this handle as it stands, 0: the per-step form, -1: the persistent kernel's set-up failed
+static int plan_form(cc4_handle* h, int32_t k) {
+  const bool plain = !h->comm && !h->evlog_on && !h->ext_seen && !h->d_prof && !h->dbg_stop;
+  if (!plain || h->multistep || h->run1m || k < h->persist_min_k) return 0;
+  if (h->persist_state == 0 && persist_setup(h)) return -1;      // (first use: the discovery pass, the only host wait a plan call can meet; cc4_plan_kernel_for ahead of time keeps it out of the caller's loop)
+  return (h->persist_state == 1 && h->run_P > 0) ? 1 : 0;
+}
+static int run_plan_impl(cc4_handle* h, int32_t k, const int32_t* d_act, const uint8_t* d_msg, float* d_rew, uint8_t* d_done, uint8_t* d_packed, bool one_launch) {
+  const size_t n = (size_t)h->cfg.num_envs;
+  const int tpb = 256, nb = (int)((n + tpb - 1) / tpb);
+  if (join_groups(h)) return -1;
+  if (!h->d_plan_err) {
+    HIPCHK(h, hipMalloc(&h->d_plan_err, n * sizeof(uint32_t)));
+    HIPCHK(h, hipMemsetAsync(h->d_plan_err, 0, n * sizeof(uint32_t), h->stream));
+  }
+  if (one_launch) {
+    h->prev_valid = false;        // (as cc4_run_random_steps: the rows move without refreshing the kept copy of cc4_keep_previous)
+    StepArgs a{h->d_state, h->d_cold, d_act, d_msg, h->d_obs, h->d_reward, h->d_done, h->d_err, nullptr, nullptr, 0, 0,
+               h->cfg.num_envs, h->cfg.autoreset, h->cfg.steps, h->cfg.rng_mode,
+               (h->cfg.red_policy & 3) | (h->cfg.green_policy ? GP_SLEEP_BIT : 0) | (h->cfg.green_policy == 2 ? GP_OPEN_BIT : 0) | (h->cfg.blue_policy ? BP_RANDOM_BIT : 0),
+               h->full_obs_next ? 1 : 0, (uint32_t)h->cfg.topology_seed, nullptr, h->d_reset_ws, nullptr, 0};
+    const PlanArgs pl{d_act, d_msg, d_rew, d_done, d_packed, h->d_plan_err};
+    if (persist_launch(h, a, k, 0u, XchgArgs{}, nullptr, nullptr, false, &pl)) return -1;
+    HIPCHK(h, hipGetLastError());
+    if (h->d_timeline) { (void)hipFree(h->d_timeline); h->d_timeline = nullptr; }      // (debug, CC4_PERSIST_TIMELINE: only cc4_run_random_steps reports it)
+    h->stat_steps += k;
+    h->full_obs_next = false;
+    // the call's flags into the handle's error words; reward / done of the last step went into the trajectory's last row only
+    hipLaunchKernelGGL(k_plan_finish, dim3(nb), dim3(tpb), 0, h->stream, (int)n, h->d_err, h->d_plan_err, h->d_mask_stale, h->d_reward,
+                       d_rew ? d_rew + (size_t)(k - 1) * n : nullptr, h->d_done, d_done ? d_done + (size_t)(k - 1) * n : nullptr);
+    HIPCHK(h, hipGetLastError());
+  } else {
+    for (int32_t j = 0; j < k; ++j) {
+      // a step of the whole batch (one launch on the main stream when the handle steps in groups: launch_step's api_step form), then its row
+      if (j > 0 && join_groups(h)) return -1;
+      if (launch_step(h, d_act + (size_t)j * n * NBLUE, d_msg ? d_msg + (size_t)j * n * NBLUE * MSG_LEN : nullptr, false, 0, 0, false, true)) return -1;
+      if (join_groups(h)) return -1;
+      hipLaunchKernelGGL(k_plan_collect, dim3((unsigned)n), dim3(WAVE), 0, h->stream, (int)n, h->d_state, h->d_obs, h->d_reward, h->d_done, h->d_err,
+                         d_rew ? d_rew + (size_t)j * n : nullptr, d_done ? d_done + (size_t)j * n : nullptr,
+                         d_packed ? d_packed + (size_t)j * n * OBS_PACKED : nullptr, h->d_plan_err);
+      HIPCHK(h, hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_plan_finish, dim3(nb), dim3(tpb), 0, h->stream, (int)n, h->d_err, h->d_plan_err, h->d_mask_stale, h->d_reward, nullptr, h->d_done, nullptr);
+    HIPCHK(h, hipGetLastError());
+  }
+  // the handle's own action buffer holds the call's last row (cc4_get_actions; cc4_replay_logged reads its step's inputs from there)
+  const int32_t* last_act = d_act + (size_t)(k - 1) * n * NBLUE;
+  if (last_act != h->d_actions) HIPCHK(h, hipMemcpyAsync(h->d_actions, last_act, n * NBLUE * sizeof(int32_t), hipMemcpyDefault, h->stream));
+  if (d_msg && d_msg + (size_t)(k - 1) * n * NBLUE * MSG_LEN != h->d_msgs)
+    HIPCHK(h, hipMemcpyAsync(h->d_msgs, d_msg + (size_t)(k - 1) * n * NBLUE * MSG_LEN, n * NBLUE * MSG_LEN, hipMemcpyDefault, h->stream));
+  if (h->keep_prev && h->prev_valid) { h->prev_actions = h->d_actions; h->prev_msgs = d_msg ? h->d_msgs : nullptr; }
+  if (h->ngroups > 1) h->main_ahead = true;      // the group streams follow at their next launch
+  return 0;
+}
+const char* cc4_plan_kernel_for(cc4_handle* h, int32_t k) {
+  if (!h) return "";
+  if (k >= 1 && !h->comm && h->rollout_k <= 0 && hipSetDevice(h->cfg.device_id) == hipSuccess && plan_form(h, k) == 1)
+    return h->cfg.rng_mode == 0 ? "k_run_pcgp" : "k_run_philox1p";
+  return cc4_step_kernel(h);
+}
+int cc4_run_plan_device(cc4_handle* h, int32_t k, const int32_t* d_actions, const uint8_t* d_messages, float* d_rewards, uint8_t* d_dones, uint8_t* d_obs_packed) {
+  const char* who = "cc4_run_plan_device";
+  if (h->comm) { h->err = std::string(who) + ": not on a handle with a communicator"; return -2; }
+  if (h->rollout_k > 0) { h->err = std::string(who) + ": a rollout is in flight on this handle: cc4_rollout_end first"; return -2; }
+  if (k < 1 || !d_actions) { h->err = std::string(who) + ": k < 1, or no plan"; return -2; }
+  if (reinterpret_cast<uintptr_t>(d_obs_packed) % 4 || reinterpret_cast<uintptr_t>(d_rewards) % 4 || reinterpret_cast<uintptr_t>(d_actions) % 4) {
+    h->err = std::string(who) + ": plan, rewards and packed observation rows must be 4-byte aligned"; return -2;
+  }
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  const int form = plan_form(h, k);
+  if (form < 0) return -1;
+  if (h->is_shadow || form == 0) return run_plan_impl(h, k, d_actions, d_messages, d_rewards, d_dones, d_obs_packed, form == 1);
+  // the self-check of the one-launch forms (cc4_run_random_steps): every call with CC4_PERSIST_VERIFY=1, else every verify_every-th persistent call
+  bool check = h->verify;
+  if (!check && h->verify_every > 0 && ++h->persist_calls % (uint64_t)h->verify_every == 0) check = true;
+  if (!check) return run_plan_impl(h, k, d_actions, d_messages, d_rewards, d_dones, d_obs_packed, true);
+  if (ensure_shadow(h)) return -1;
+  cc4_handle* sh = h->shadow;
+  const size_t n = (size_t)h->cfg.num_envs;
+  if (join_groups(h) || join_groups(sh)) return -1;
+  HIPCHK(h, hipStreamSynchronize(sh->stream));
+  HIPCHK(h, hipMemcpyAsync(sh->d_state, h->d_state, n * sizeof(EnvState), hipMemcpyDeviceToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(sh->d_cold, h->d_cold, n * h->cold_row, hipMemcpyDeviceToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(sh->d_obs, h->d_obs, h->out_bytes, hipMemcpyDefault, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));      // (behind whatever cc4_stream_wait ordered this handle after: the plan is complete for the shadow's stream too)
+  sh->full_obs_next = h->full_obs_next; sh->main_ahead = sh->ngroups > 1;
+  float* s_rew = nullptr; uint8_t* s_done = nullptr; uint8_t* s_packed = nullptr;
+  auto release = [&]() { if (s_rew) (void)hipFree(s_rew); if (s_done) (void)hipFree(s_done); if (s_packed) (void)hipFree(s_packed); };
+  if (d_rewards && hipMalloc(&s_rew, (size_t)k * n * sizeof(float)) != hipSuccess) { h->err = "CC4_PERSIST_VERIFY: no memory for the shadow's trajectory"; return -1; }
+  if (d_dones && hipMalloc(&s_done, (size_t)k * n) != hipSuccess) { release(); h->err = "CC4_PERSIST_VERIFY: no memory for the shadow's trajectory"; return -1; }
+  if (d_obs_packed && hipMalloc(&s_packed, (size_t)k * n * OBS_PACKED) != hipSuccess) { release(); h->err = "CC4_PERSIST_VERIFY: no memory for the shadow's trajectory"; return -1; }
+  int rc = run_plan_impl(h, k, d_actions, d_messages, d_rewards, d_dones, d_obs_packed, true);
+  if (rc) { release(); return rc; }
+  rc = run_plan_impl(sh, k, d_actions, d_messages, s_rew, s_done, s_packed, false);
+  if (rc) { release(); h->err = "CC4_PERSIST_VERIFY: the shadow run failed: " + sh->err; return rc; }
+  std::vector<uint64_t> a, b;
+  if (verify_digest(h, a)) { release(); return -1; }
+  if (verify_digest(sh, b)) { release(); h->err = "CC4_PERSIST_VERIFY: " + sh->err; return -1; }
+  h->verify_calls++;
+  std::string bad;
+  for (size_t e = 0; e < n && bad.empty(); ++e) {
+    const bool hot = a[3 * e] != b[3 * e], cold = a[3 * e + 1] != b[3 * e + 1], outp = a[3 * e + 2] != b[3 * e + 2];
+    if (hot || cold || outp) bad = "first episode " + std::to_string(e) + " (" + (hot ? "hot row " : "") + (cold ? "cold row " : "") + (outp ? "outputs" : "") + ")";
+  }
+  // the trajectory, a step's row at a time (both streams are drained: verify_digest waited for them)
+  std::vector<uint8_t> ra, rb;
+  auto rows_differ = [&](const void* p, const void* q, size_t row_bytes, int32_t j) {
+    ra.resize(row_bytes); rb.resize(row_bytes);
+    if (hipMemcpy(ra.data(), static_cast<const uint8_t*>(p) + (size_t)j * row_bytes, row_bytes, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(rb.data(), static_cast<const uint8_t*>(q) + (size_t)j * row_bytes, row_bytes, hipMemcpyDeviceToHost) != hipSuccess) return true;
+    return memcmp(ra.data(), rb.data(), row_bytes) != 0;
+  };
+  for (int32_t j = 0; j < k && bad.empty(); ++j) {
+    if (d_rewards && rows_differ(d_rewards, s_rew, n * sizeof(float), j)) bad = "rewards of step " + std::to_string(j);
+    else if (d_dones && rows_differ(d_dones, s_done, n, j)) bad = "dones of step " + std::to_string(j);
+    else if (d_obs_packed && rows_differ(d_obs_packed, s_packed, n * OBS_PACKED, j)) bad = "packed observations of step " + std::to_string(j);
+  }
+  release();
+  if (!bad.empty()) {
+    h->verify_mismatches++;
+    h->err = "CC4_PERSIST_VERIFY: " + std::string(cc4_plan_kernel_for(h, k)) + " and the per-step launches disagree after a plan of " + std::to_string(k) + " steps: " + bad;
+    fprintf(stderr, "[cc4] %s\n", h->err.c_str());
+    return -5;
+  }
+  return 0;
+}
+int cc4_unpack_rows_device(cc4_handle* h, int64_t rows, const uint8_t* d_packed, int32_t obs_dtype, void* d_out) {
+  if (obs_dtype < 0 || obs_dtype > 3) { h->err = "cc4_unpack_rows_device: obs_dtype must be 0 (uint8), 1 (float16), 2 (bfloat16) or 3 (float32)"; return -2; }
+  if (rows < 0 || (rows > 0 && (!d_packed || !d_out))) { h->err = "cc4_unpack_rows_device: rows < 0, or no buffers"; return -2; }
+  static const uintptr_t align[4] = {1, 2, 2, 4};
+  if (reinterpret_cast<uintptr_t>(d_out) % align[obs_dtype]) { h->err = "cc4_unpack_rows_device: the output buffer is not aligned to its element size"; return -2; }
+  if (rows == 0) return 0;
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  if (join_groups(h)) return -1;
+  const long long bytes = (long long)rows * OBS_PACKED;
+  const dim3 grid((unsigned)std::max(1LL, std::min((bytes + 255) / 256, 32LL * h->cus))), block(256);
+  switch (obs_dtype) {
+    case 0: hipLaunchKernelGGL(k_unpack_rows<0>, grid, block, 0, h->stream, d_packed, d_out, (long long)rows); break;
+    case 1: hipLaunchKernelGGL(k_unpack_rows<1>, grid, block, 0, h->stream, d_packed, d_out, (long long)rows); break;
+    case 2: hipLaunchKernelGGL(k_unpack_rows<2>, grid, block, 0, h->stream, d_packed, d_out, (long long)rows); break;
+    default: hipLaunchKernelGGL(k_unpack_rows<3>, grid, block, 0, h->stream, d_packed, d_out, (long long)rows); break;
+  }
+  HIPCHK(h, hipGetLastError());
   return 0;
 }
 // ---- rollouts with the policy in the loop (include/cc4.h).  ONE launch of the persistent kernel per k-step rollout; the caller's policy

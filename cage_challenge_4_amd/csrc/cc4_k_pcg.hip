@@ -510,6 +510,9 @@ __global__ __launch_bounds__(WAVE) void k_step(StepArgs a) {
 
 // the persistent schedule (cc4_persist.h) around the numpy-stream step: the bit-exact mode's large batches
 __global__ __launch_bounds__(WAVE, 6) void k_run_pcg(StepArgs a, RunArgs ra, XchgArgs x) { persist_loop<true>(a, ra, x); }
+// its plan build (cc4_run_plan_device: the actions of step j from row j of the caller's plan, PlanArgs): an entry of its own, in this unit because the
+// numpy-stream step body and the jump table it reads (g_pcg_jump) are this unit's
+__global__ __launch_bounds__(WAVE, 6) void k_run_pcgp(StepArgs a, RunArgs ra, PlanArgs pl) { persist_loop<true, false, false, true>(a, ra, XchgArgs{}, pl); }
 
 
 // the kernels the host side launches (cc4_kernel_decls.h)

@@ -27,6 +27,17 @@ __global__ void k_run_philox1(StepArgs a, RunArgs ra, XchgArgs x);
 __global__ void k_run_philox1x(StepArgs a, RunArgs ra, XchgArgs x);
 __global__ void k_run_philox1r(StepArgs a, RunArgs ra, XchgArgs x);
 __global__ void k_run_pcg(StepArgs a, RunArgs ra, XchgArgs x);
+// cc4_run_plan_device (cc4_k_plan.hip; k_run_pcgp: cc4_k_pcg.hip)
+__global__ void k_run_philox1p(StepArgs a, RunArgs ra, PlanArgs pl);
+__global__ void k_run_pcgp(StepArgs a, RunArgs ra, PlanArgs pl);
+__global__ void k_plan_collect(int n, const EnvState* st, const int32_t* obs, const float* reward, const uint8_t* done, const uint32_t* err,
+                               float* row_reward, uint8_t* row_done, uint8_t* row_packed, uint32_t* err_or);
+__global__ void k_plan_finish(int n, uint32_t* err, uint32_t* err_or, uint8_t* mask_stale, float* reward, const float* last_reward, uint8_t* done, const uint8_t* last_done);
+template <int DT> __global__ void k_unpack_rows(const uint8_t* __restrict__ packed, void* __restrict__ out, long long rows);
+extern template __global__ void k_unpack_rows<0>(const uint8_t*, void*, long long);
+extern template __global__ void k_unpack_rows<1>(const uint8_t*, void*, long long);
+extern template __global__ void k_unpack_rows<2>(const uint8_t*, void*, long long);
+extern template __global__ void k_unpack_rows<3>(const uint8_t*, void*, long long);
 // reset and helpers (cc4_k_misc.hip)
 __global__ void k_reset(ResetArgs a);
 __global__ void k_xchg_gate(uint32_t* gcnt, int ring, int groups, int n, int P, int k_lo, int k_hi, long long ticks, uint32_t* fail, int max_naps);

@@ -6,6 +6,8 @@
 //   cc4_k_philox1.hip  counter mode, one wavefront per episode: k_step_philox1<LOG>, k_run_philox1m (cc4_philox1_body.h: the step's body)
 //   cc4_k_run1.hip     the persistent kernel of large batches: k_run_philox1 (cc4_persist.h: its schedule, shared with k_run_pcg)
 //   cc4_k_run1x.hip    its other builds: k_run_philox1x (beside RCCL), k_run_philox1r (rollouts with the policy in the loop)
+//   cc4_k_plan.hip     the plan build of the persistent kernel, k_run_philox1p (cc4_run_plan_device), and the plan call's helpers; the numpy-stream
+//                      plan build k_run_pcgp sits beside k_run_pcg (the numpy-stream step body and its jump table are private to cc4_k_pcg.hip)
 //   cc4_k_misc.hip     k_reset and the small helpers (exchange gate, CU discovery, stand-in policies, digest, ...)
 //   cc4_k_copy.hip     episode copies: k_copy_claim, k_copy_episodes (cc4_copy_episodes_device)
 // No MFMA anywhere: the path is integer / indexing.
@@ -332,6 +334,16 @@ struct RunArgs {
   int PG;
   long long act_wait_ticks;    // watchdog: a step that waits longer for its actions gives up, raises XchgArgs.timeout, and every later wait returns at once
 };
+// cc4_run_plan_device in one launch (persist_loop<.., PLAN>): the caller's plan and trajectory, all on the device, one row of the whole batch per step
+struct PlanArgs {
+  const int32_t* actions;      // [K][n][5] wrapper indices: step j reads row j
+  const uint8_t* msgs;         // [K][n][5][8], or null
+  float* rewards;              // [K][n], or null: every step writes the handle's reward buffer as always
+  uint8_t* dones;              // [K][n], or null
+  uint8_t* obs_packed;         // [K][n][OBS_PACKED], or null: the packed observation row after every step
+  uint32_t* err_or;            // [n] the error flags any step of the call raised (zero between calls: k_plan_finish moves them into the handle's error words)
+};
+constexpr uint32_t PLAN_REGEN = 0x80000000u;   // ... and, beside the E_* flags, "a step of the call regenerated the episode" (autoreset): k_plan_finish marks its mask row stale
 // lane 0: the actions of step j for policy group g are published.  Polls a device word at a growing interval (see xchg_wait_slab).
 __device__ __forceinline__ void rollout_wait_actions(const RunArgs& ra, const XchgArgs& x, int line, int g, uint32_t j) {
   const uint32_t* w = ra.act_ready + (size_t)line * 32 + g;

@@ -1,4 +1,4 @@
-// cc4_persist.h -- the schedule of the persistent kernels (k_run_philox1 / k_run_philox1x / k_run_pcg): one wave per residency slot pulling runs of
+// cc4_persist.h -- the schedule of the persistent kernels (k_run_philox1 / k_run_philox1x / k_run_philox1r / k_run_pcg and the plan builds k_run_philox1p / k_run_pcgp): one wave per residency slot pulling runs of
 // steps of episodes from its CU's partition.  See cc4_kernels.h (RunArgs) and DESIGN 3.3.
 #pragma once
 #include "cc4_kernels.h"
@@ -33,8 +33,11 @@ __device__ __forceinline__ bool rollout_wait_progress(const RunArgs& ra, const X
 // cost the headline kernel 30 more spilled registers)
 // XCHG: the build serves the exchange (the packed rows of every step into the slab ring, counted for the communication stream's gates).  The
 // headline kernel k_run_philox1 is built without it: handles with a communicator launch k_run_philox1x.
-template <bool PCG, bool ROLLOUT = false, bool XCHG = true>
-__device__ __forceinline__ void persist_loop(StepArgs a, RunArgs ra, const XchgArgs x) {
+// PLAN: the build serves cc4_run_plan_device (k_run_philox1p / k_run_pcgp; PlanArgs) -- step j of the call reads its blue actions and messages from row j
+// of the caller's plan and writes reward / done / packed observation row into row j of the caller's trajectory.  The plan was complete before the launch
+// and the trajectory is read behind its end: plain loads, no gate, no counter, no watchdog.  In every other build `pl` is dead and folds away.
+template <bool PCG, bool ROLLOUT = false, bool XCHG = true, bool PLAN = false>
+__device__ __forceinline__ void persist_loop(StepArgs a, RunArgs ra, const XchgArgs x, const PlanArgs pl = PlanArgs{}) {
   // (the item travels from lane 0 to the wave through v_readfirstlane, not through LDS)
   const int lane = threadIdx.x;
   const int my_slot = cu_slot();
@@ -171,6 +174,7 @@ __device__ __forceinline__ void persist_loop(StepArgs a, RunArgs ra, const XchgA
     if (ra.timeline && !tl_items) tl_first = wall_clock64();
     if (shared || ra.order >= 1) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");      // (buffer_inv sc1: the CU's L1 dropped.  buffer_inv sc0 does NOT drop it: profiles/r06_l1_inv_scope.txt)
     uint32_t item_k = (uint32_t)run_k0;
+    uint32_t err_acc = 0;          // PLAN, lane 0: the error flags of the run's steps (a regeneration inside the run clears the row's word)
     for (int q = 0; q < run_len; ++q, ++item_k) {
     if (q > 0) {
       if (XCHG && x.slab) {
@@ -191,6 +195,15 @@ __device__ __forceinline__ void persist_loop(StepArgs a, RunArgs ra, const XchgA
     int lane_i = (int)threadIdx.x;
     asm volatile("" : "+v"(lane_i));
     if (ROLLOUT && ra.act_ready) { a.actions = ra.act + (size_t)(item_k & 1u) * (size_t)a.n * NBLUE; a.rand_out = nullptr; a.act_sys = 1; }
+    if constexpr (PLAN) {
+      // row item_k of the plan in, row item_k of the trajectory out (the handle's own reward / done buffers where the caller gave none).  The packed
+      // row is written by the step body itself behind a drain of its own (StepArgs.obs8, as in the per-step launches): every step of a run gets one
+      const size_t row = (size_t)item_k * (size_t)a.n;
+      a.actions = pl.actions + row * NBLUE; a.msgs = pl.msgs ? pl.msgs + row * (NBLUE * MSG_LEN) : nullptr; a.rand_out = nullptr;
+      if (pl.rewards) a.reward = pl.rewards + row;
+      if (pl.dones) a.done = pl.dones + row;
+      a.obs8 = pl.obs_packed ? pl.obs_packed + row * OBS_PACKED : nullptr;
+    }
     if constexpr (PCG) {
       StepArgs b = a;
       b.rand_t = ra.t0 + item_k; b.full_obs = (a.full_obs && item_k == 0) ? 1 : 0;
@@ -198,6 +211,11 @@ __device__ __forceinline__ void persist_loop(StepArgs a, RunArgs ra, const XchgA
       pcg_body<false>(b, e, lane_i, q == 0, q == run_len - 1);
     } else {
       philox1_body<false, true>(a, e, ra.t0 + item_k, item_k, lane_i, q == 0, q == run_len - 1);      // (a.obs8 is null: the packed row is written below, behind the drain)
+    }
+    if constexpr (PLAN) {          // (the agent part is still in LDS; the body's last barrier is behind the step's last set_err)
+      extern __shared__ uint4 plan_lds[];
+      const EnvState* const sp = reinterpret_cast<const EnvState*>(plan_lds);
+      if (lane == 0) err_acc |= sp->err | (sp->step_count == 0 ? PLAN_REGEN : 0u);     // (regenerated by this step: the caller's action-mask row is stale)
     }
     }
     --item_k;        // the run's last step
@@ -229,6 +247,9 @@ __device__ __forceinline__ void persist_loop(StepArgs a, RunArgs ra, const XchgA
           pend_e = -1;
         }
       }
+    }
+    if constexpr (PLAN) {          // what some step of the run flagged, for the call's error word (k_plan_finish ORs it into the handle's): rare, nothing waits for it
+      if (lane == 0 && err_acc) (void)__hip_atomic_fetch_or(pl.err_or + e, err_acc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     if (lane == 0) __hip_atomic_store(&ra.progress[e], (ra.base + item_k + 1u) | (my_id << 23), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (ra.timeline) { tl_last = wall_clock64(); ++tl_items; }

@@ -122,6 +122,45 @@ class CC4TorchVecEnv:
             self._outputs(sp)
         return self.obs, self.reward, self.done, self._info()
 
+    def step_plan(self, actions, messages=None, record_obs=False):
+        """k steps with the blue actions known in advance (cc4_run_plan_device: one launch of the persistent kernel where it serves the batch,
+        venv.plan_kernel_for(k)): actions integer tensor [k, N, 5] on the env's device, messages optional [k, N, 5, 8] of 0 / 1.
+        Returns (obs, rewards [k, N] float32, dones [k, N] bool, info): obs, info['action_mask'], info['err'] are the env's reused tensors after the
+        LAST step (masks refreshed for every episode the plan regenerated; err: every flag some step raised), rewards / dones fresh tensors,
+        info['obs_seq'] [k, N, 578] obs_dtype -- the observations after every step -- with record_obs.  Ordered on the current stream both
+        ways like step(); no host copy, no host wait."""
+        n = self.num_envs
+        if (not torch.is_tensor(actions) or actions.dim() != 3 or actions.shape[0] < 1 or tuple(actions.shape[1:]) != (n, L.NUM_BLUE)
+                or actions.dtype.is_floating_point or actions.dtype == torch.bool or actions.device != self.device):
+            raise ValueError(f'actions must be an integer tensor [k, {n}, {L.NUM_BLUE}] (k >= 1) on {self.device}')
+        k = int(actions.shape[0])
+        if messages is not None and (not torch.is_tensor(messages) or tuple(messages.shape) != (k, n, L.NUM_BLUE, L.MSG_LEN)
+                                     or messages.dtype.is_floating_point or messages.device != self.device):
+            raise ValueError(f'messages must be an integer or bool tensor [{k}, {n}, {L.NUM_BLUE}, {L.MSG_LEN}] on {self.device}')
+        with torch.cuda.device(self.device):
+            s = torch.cuda.current_stream(self.device)
+            vp = ctypes.c_void_p
+            # on s: casts (no copy when the plan is int32 / uint8 and contiguous already) and the trajectory's tensors; the allocator keeps them
+            # on s, whose later work cc4_stream_signal orders behind the plan
+            plan = actions.to(torch.int32).contiguous()
+            msgs = messages.to(torch.uint8).contiguous() if messages is not None else None
+            rewards = torch.empty((k, n), dtype=torch.float32, device=self.device)
+            dones = torch.empty((k, n), dtype=torch.bool, device=self.device)
+            packed = torch.empty((k, n, L.OBS_PACKED_BYTES), dtype=torch.uint8, device=self.device) if record_obs else None
+            lib, h, sp = self.lib, self._h, vp(s.cuda_stream)
+            rc = lib.cc4_stream_wait(h, sp) or lib.cc4_run_plan_device(h, k, vp(plan.data_ptr()), vp(msgs.data_ptr()) if msgs is not None else None,
+                                                                       vp(rewards.data_ptr()), vp(dones.data_ptr()),
+                                                                       vp(packed.data_ptr()) if record_obs else None)
+            if rc:
+                self.venv._chk(rc, 'cc4_run_plan_device')
+            info = self._info()
+            if record_obs:
+                seq = torch.empty((k, n, L.OBS_PER_ENV), dtype=self.obs_dtype, device=self.device)
+                self.venv._chk(lib.cc4_unpack_rows_device(h, k * n, vp(packed.data_ptr()), self._dt, vp(seq.data_ptr())), 'cc4_unpack_rows_device')
+                info['obs_seq'] = seq
+            self._outputs(sp)       # (signals s: what the caching allocator hands out on s once plan / msgs / packed die is ordered behind their readers)
+        return self.obs, rewards, dones, info
+
     @property
     def snapshot_bytes(self):
         """cc4_snapshot_bytes: bytes of one snapshot slot (header, hot row, cold row, the outputs of the last step)."""

@@ -73,6 +73,7 @@ class CC4VecEnv:
         self.lib = L.load()
         self.num_envs = int(num_envs)
         self.steps = int(steps)
+        self._dev = int(device_id)
         cfg = L.CC4Config(self.num_envs, self.steps, int(device_id), int(rng_mode), int(bool(autoreset)),
                           int(red_policy), int(green_policy), int(topology_seed), int(blue_policy))
         h = ctypes.c_void_p()
@@ -382,6 +383,64 @@ class CC4VecEnv:
         raise_on_copy_faults(faults.value)
         return self._check_err()[0]
 
+    def plan_kernel_for(self, k):
+        """cc4_plan_kernel_for: the kernel a run_plan / step_plan call of k steps launches ('k_run_philox1p' / 'k_run_pcgp': one launch for the
+        whole plan; else the step kernel, once per step)."""
+        return self.lib.cc4_plan_kernel_for(self._h, int(k)).decode()
+
+    def run_plan(self, actions, messages=None, record_obs=False):
+        """k steps with the blue actions known in advance (cc4_run_plan_device, include/cc4.h): actions [k, N, 5] wrapper indices (any integer
+        dtype; negative = no action), messages optional [k, N, 5, 8] of 0 / 1.  One upload of the plan, one call, one download of the trajectory.
+        Returns (obs_last [N, 578], rewards [k, N] float32, dones [k, N] bool, info); info['obs_seq'] [k, N, 578] uint8 -- the observations
+        after every step -- with record_obs.  The handle ends where k calls of step() would have left it; info['err'] holds every flag some
+        step of the plan raised, and strict mode raises for them as step() does (a step past an episode's end raises ValueError in either
+        mode); the exception's `plan_outputs` attribute is the tuple the call would have returned."""
+        actions = np.ascontiguousarray(actions, dtype=np.int32)
+        if actions.ndim != 3 or actions.shape[0] < 1 or actions.shape[1:] != (self.num_envs, L.NUM_BLUE):
+            raise ValueError(f'actions must be [k, {self.num_envs}, {L.NUM_BLUE}] with k >= 1')
+        k, n = int(actions.shape[0]), self.num_envs
+        if messages is not None:
+            messages = np.ascontiguousarray(messages, dtype=np.uint8)
+            if messages.shape != (k, n, L.NUM_BLUE, L.MSG_LEN):
+                raise ValueError(f'messages must be [{k}, {n}, {L.NUM_BLUE}, {L.MSG_LEN}]')
+        hip, vp = _hip(), ctypes.c_void_p
+        b_act, b_msg = actions.nbytes, (messages.nbytes if messages is not None else 0)
+        b_rew, b_pk, b_done = 4 * k * n, (L.OBS_PACKED_BYTES * k * n if record_obs else 0), k * n
+        _hip_chk(hip.hipSetDevice(self._dev), 'hipSetDevice')
+        d_in, d_out = vp(), vp()
+        _hip_chk(hip.hipMalloc(ctypes.byref(d_in), b_act + b_msg), 'hipMalloc')
+        try:
+            _hip_chk(hip.hipMalloc(ctypes.byref(d_out), b_rew + b_pk + b_done), 'hipMalloc')
+            staged = np.empty(b_act + b_msg, np.uint8)                 # [actions | messages]: one copy up
+            staged[:b_act] = actions.reshape(-1).view(np.uint8)
+            if messages is not None:
+                staged[b_act:] = messages.reshape(-1)
+            _hip_chk(hip.hipMemcpy(d_in, staged.ctypes.data_as(vp), staged.nbytes, 1), 'hipMemcpy')
+            rc = self.lib.cc4_run_plan_device(self._h, k, d_in, vp(d_in.value + b_act) if messages is not None else None, d_out,
+                                              vp(d_out.value + b_rew + b_pk), vp(d_out.value + b_rew) if record_obs else None)
+            rc2 = self.lib.cc4_synchronize(self._h)
+            if rc or rc2:
+                self._chk(rc or rc2, 'cc4_run_plan_device')
+            out = np.empty(b_rew + b_pk + b_done, np.uint8)           # [rewards | packed observations | dones]: one copy down
+            _hip_chk(hip.hipMemcpy(out.ctypes.data_as(vp), d_out, out.nbytes, 2), 'hipMemcpy')
+        finally:
+            hip.hipFree(d_in)
+            if d_out:
+                hip.hipFree(d_out)
+        rewards = out[:b_rew].view(np.float32).reshape(k, n).copy()
+        dones = out[b_rew + b_pk:].reshape(k, n).astype(bool)
+        info = {}
+        if record_obs:
+            info['obs_seq'] = unpack_obs_rows(out[b_rew:b_rew + b_pk].reshape(k, n, L.OBS_PACKED_BYTES))
+        self._chk(self.lib.cc4_fetch(self._h, *self._p_out), 'cc4_fetch')
+        info['err'] = self._err
+        try:
+            obs = self._check_err()[0]
+        except (ValueError, CC4EngineError) as e:       # (the plan has run: the exception carries what it produced)
+            e.plan_outputs = (self._obs, rewards, dones, info)
+            raise
+        return obs, rewards, dones, info
+
     # device-resident loop used by bench.py
     def run_random_steps(self, seed0, t0, k, timed=True):
         ms = ctypes.c_float(0.0)
@@ -466,6 +525,36 @@ class CC4VecEnv:
 
     def synchronize(self):
         self._chk(self.lib.cc4_synchronize(self._h), 'cc4_synchronize')
+
+
+def unpack_obs_rows(packed):
+    """[..., 148] packed observation rows (2 bits per value, low bits first: CC4_OBS_PACKED_BYTES) -> [..., 578] uint8 values."""
+    packed = np.asarray(packed, dtype=np.uint8)
+    vals = (packed[..., None] >> np.array([0, 2, 4, 6], np.uint8)) & np.uint8(3)
+    return vals.reshape(packed.shape[:-1] + (4 * packed.shape[-1],))[..., :L.OBS_PER_ENV]
+
+
+_hip_lib = None
+
+
+def _hip():
+    """The HIP runtime libcc4.so is linked against, reached through libcc4.so's own handle (a symbol lookup there searches its dependencies: no
+    second search of the loader's path), for the host-array surface's staging buffers (run_plan)."""
+    global _hip_lib
+    if _hip_lib is None:
+        lib = ctypes.CDLL(L.LIB_PATH)
+        vp = ctypes.c_void_p
+        lib.hipSetDevice.argtypes, lib.hipSetDevice.restype = [ctypes.c_int], ctypes.c_int
+        lib.hipMalloc.argtypes, lib.hipMalloc.restype = [ctypes.POINTER(vp), ctypes.c_size_t], ctypes.c_int
+        lib.hipFree.argtypes, lib.hipFree.restype = [vp], ctypes.c_int
+        lib.hipMemcpy.argtypes, lib.hipMemcpy.restype = [vp, vp, ctypes.c_size_t, ctypes.c_int], ctypes.c_int
+        _hip_lib = lib
+    return _hip_lib
+
+
+def _hip_chk(rc, what):
+    if rc != 0:
+        raise L.CC4Error(f'{what} failed (hipError_t {rc})')
 
 
 def split_obs(obs):
