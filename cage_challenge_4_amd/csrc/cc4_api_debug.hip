@@ -1,0 +1,158 @@
+// cc4_api_debug.hip -- the host side of libcc4.so: the debug and measurement hooks (include/cc4_debug.h) and the two debug reports of cc4_run_random_steps.
+// (The functions of the C ABI take their linkage from their declarations in include/cc4.h and include/cc4_debug.h.)
+#include "cc4_host.h"
+
+// debug (CC4_PERSIST_TIMELINE): where a persistent call's time goes between the kernel's entry and its last item (ticks of the 100 MHz wall clock); frees
+// the call's time stamps.  timed: the call carried the timing events evs[0], evs[1].
+int timeline_report(cc4_handle* h, int k, bool timed) {
+  std::vector<unsigned long long> tl(4 * (size_t)h->run_grid);
+  HIPCHK(h, hipMemcpy(tl.data(), h->d_timeline, tl.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  (void)hipFree(h->d_timeline); h->d_timeline = nullptr;
+  unsigned long long e0 = ~0ull, e1 = 0, f1 = 0, l0 = ~0ull, l1 = 0; double fs = 0, ls = 0, items = 0; int nw = 0, idle = 0;
+  for (int w = 0; w < h->run_grid; ++w) { const unsigned long long* t = &tl[4 * (size_t)w]; if (!t[0]) continue; ++nw; e0 = t[0] < e0 ? t[0] : e0; e1 = t[0] > e1 ? t[0] : e1; if (!(uint32_t)t[3]) { ++idle; continue; } f1 = t[1] > f1 ? t[1] : f1; l0 = t[2] < l0 ? t[2] : l0; l1 = t[2] > l1 ? t[2] : l1; fs += (double)t[1]; ls += (double)t[2]; items += (double)(uint32_t)t[3]; }
+  const int busy = nw - idle;
+  float ms = 0.f; if (timed) (void)hipEventElapsedTime(&ms, h->evs[0], h->evs[1]);
+  fprintf(stderr, "[cc4 timeline] k=%d: %d waves reported (%d without an item); entry spread %.1f us; first item starts: mean +%.1f us, last +%.1f us after the first entry; "
+                  "last item ends: earliest +%.1f us, mean +%.1f us, latest +%.1f us; items per busy wave %.1f; kernel (events) %.1f us\n",
+          k, nw, idle, (e1 - e0) / 100.0, busy ? (fs / busy - (double)e0) / 100.0 : 0.0, (f1 - e0) / 100.0, (l0 - e0) / 100.0, busy ? (ls / busy - (double)e0) / 100.0 : 0.0, (l1 - e0) / 100.0, busy ? items / busy : 0.0, ms * 1000.0);
+  // per CU: when its LAST wave ran dry, and how many items its waves executed (more than its own partition's = it helped out)
+  { std::map<int, std::pair<unsigned long long, double>> cu;
+    for (int w = 0; w < h->run_grid; ++w) { const unsigned long long* t = &tl[4 * (size_t)w]; if (!t[0] || !(uint32_t)t[3]) continue; auto& c = cu[(int)((t[3] >> 32) - 1)]; if (t[2] > c.first) c.first = t[2]; c.second += (double)(uint32_t)t[3]; }
+    std::vector<double> last, its; for (auto& kv : cu) { last.push_back((kv.second.first - e0) / 100.0); its.push_back(kv.second.second); }
+    std::sort(last.begin(), last.end()); std::sort(its.begin(), its.end());
+    if (!last.empty()) { const size_t m = last.size(); fprintf(stderr, "[cc4 timeline]   per CU (%zu): last wave dry at min %.1f / 10%% %.1f / median %.1f / 90%% %.1f / max %.1f us; items executed min %.0f / median %.0f / max %.0f\n", m,
+                               last[0], last[m / 10], last[m / 2], last[m * 9 / 10], last[m - 1], its[0], its[m / 2], its[m - 1]); } }
+  // per XCD: when its waves ran dry (intra-XCD sharing evens a tail out inside an XCD; what is left between XCDs is not shareable)
+  { double xs[8] = {0}, xi[8] = {0}; unsigned long long xl[8] = {0}, xf[8]; int xn[8] = {0}; for (int i = 0; i < 8; ++i) xf[i] = ~0ull;
+    for (int w = 0; w < h->run_grid; ++w) { const unsigned long long* t = &tl[4 * (size_t)w]; if (!t[0] || !(uint32_t)t[3]) continue; const int xc = (int)(((t[3] >> 32) - 1) >> 8) & 7;
+      xs[xc] += (double)t[2]; xi[xc] += (double)(uint32_t)t[3]; ++xn[xc]; if (t[2] > xl[xc]) xl[xc] = t[2]; if (t[2] < xf[xc]) xf[xc] = t[2]; }
+    for (int i = 0; i < 8; ++i) if (xn[i]) fprintf(stderr, "[cc4 timeline]   XCD %d: %d busy waves, %.0f items; waves ran dry: earliest +%.1f, mean +%.1f, latest +%.1f us\n", i, xn[i], xi[i],
+                                                  (xf[i] - e0) / 100.0, (xs[i] / xn[i] - (double)e0) / 100.0, (xl[i] - e0) / 100.0); }
+  return 0;
+}
+// debug (CC4_EXCHANGE_PROF): where the host's time goes around a one-launch call with the exchange; t = before xchg_begin, before the launch, before
+// xchg_enqueue, before and after the wait for the kernel, after xchg_end
+void exchange_prof_report(int k, const std::chrono::steady_clock::time_point (&t)[6]) {
+  static double xp[6] = {0}; static long xpn = 0;
+  auto us = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
+  xp[0] += us(t[0], t[1]); xp[1] += us(t[1], t[2]); xp[2] += us(t[2], t[3]); xp[3] += us(t[3], t[4]); xp[4] += us(t[4], t[5]); xp[5] += us(t[0], t[5]);
+  if (++xpn % 200 == 0) {
+    fprintf(stderr, "[cc4 exchange prof] k=%d, mean of 200 calls (us): begin %.1f, launch %.1f, enqueue of the chunks %.1f, wait for the kernel %.1f, then for the communication stream %.1f; call %.1f\n",
+            k, xp[0] / 200, xp[1] / 200, xp[2] / 200, xp[3] / 200, xp[4] / 200, xp[5] / 200);
+    for (double& v : xp) v = 0;
+  }
+}
+// debug: where a rollout stands / stood -- out[0..1] gate-failed flag and the kernel's timeout flag, out[2 + g] the groups' published step counts,
+// out[6 + 4 * slot + g] = sum over the partitions of the count of (policy group g, ring slot), slots 0..3
+int cc4_debug_rollout_state(cc4_handle* h, int64_t* out /* [22] */) {
+  if (!h->d_rcnt) { h->err = "cc4_debug_rollout_state: no rollout was begun on this handle"; return -2; }
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  std::vector<uint32_t> rd(32), cnt((size_t)h->run_P * RPG_MAX * cc4_handle::XRING);
+  uint32_t fail = 0;
+  HIPCHK(h, hipMemcpy(rd.data(), h->d_rready, rd.size() * 4, hipMemcpyDeviceToHost));
+  HIPCHK(h, hipMemcpy(cnt.data(), h->d_rcnt, cnt.size() * 4, hipMemcpyDeviceToHost));
+  HIPCHK(h, hipMemcpy(&fail, h->d_rfail, 4, hipMemcpyDeviceToHost));
+  out[0] = fail; out[1] = *reinterpret_cast<volatile uint32_t*>(h->h_xtimeout);
+  for (int g = 0; g < h->rpg; ++g) out[2 + g] = rd[g];
+  for (int slot = 0; slot < 4; ++slot) for (int g = 0; g < h->rpg; ++g) {
+    int64_t sum = 0;
+    for (int p = 0; p < h->run_P; ++p) sum += cnt[((size_t)p * h->rpg + g) * cc4_handle::XRING + slot];
+    out[6 + 4 * slot + g] = sum;
+  }
+  return 0;
+}
+
+// debug: enable (buf != NULL first call allocates) / read per-episode cycle counters [N][64] (16 phase slots, then 8 per red agent)
+int cc4_debug_profile(cc4_handle* h, int enable, unsigned long long* out) {
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  if (join_groups(h)) return -1;
+  size_t bytes = (size_t)h->cfg.num_envs * PROF_SLOTS * sizeof(unsigned long long);
+  if (enable && !h->d_prof) { HIPCHK(h, hipMalloc(&h->d_prof, bytes)); HIPCHK(h, hipMemsetAsync(h->d_prof, 0, bytes, h->stream)); }
+  if (out && h->d_prof) { HIPCHK(h, hipMemcpyAsync(out, h->d_prof, bytes, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream)); }
+  if (!enable && h->d_prof) { (void)hipFree(h->d_prof); h->d_prof = nullptr; }
+  return 0;
+}
+
+// measurement (tools/valu_phases.py): from now on the per-step launches of k_step_philox1 (its full build) end behind phase `phase` of the step (1..13,
+// csrc/cc4_philox1_body.h CC4_STOP) and write no row back; 14 = whole steps of the full build; 0 = whole steps of the usual build again.  The caller restores the batch (cc4_set_state / cc4_set_cold) after such a step.
+int cc4_debug_stop_phase(cc4_handle* h, int phase) {
+  if (join_groups(h)) return -1;
+  if (phase < 0 || phase > 14 || !h->philox_lean) { h->err = "cc4_debug_stop_phase: phase 0..14, on a handle whose step kernel is k_step_philox1"; return -2; }
+  h->dbg_stop = phase;
+  return 0;
+}
+
+// debug: the red policy phase of every episode with G episodes' agents per wave; out[0] = mean launch duration in us, out[1] = mean cycles
+// of a wave in the phase, out[2] = waves per launch.  Reads the batch as it stands, writes nothing back.
+int cc4_debug_policy_probe(cc4_handle* h, int32_t G, int32_t reps, double* out) {
+#ifndef CC4_POLICY_PROBE
+  (void)G; (void)reps; (void)out;
+  h->err = "cc4_debug_policy_probe: this library was built without -DCC4_POLICY_PROBE (the experiment of DESIGN 3.4 is concluded; tools/policy_group_probe.py says how to build it)";
+  return -2;
+#else
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  if (h->cfg.rng_mode != 1) { h->err = "cc4_debug_policy_probe: counter mode only"; return -2; }
+  if (join_groups(h)) return -1;
+  const int n = h->cfg.num_envs, waves = (n + G - 1) / G;
+  unsigned long long* d_cyc = nullptr;
+  HIPCHK(h, hipMalloc(&d_cyc, (size_t)waves * sizeof(unsigned long long)));
+  StepArgs a = step_args(h);
+  a.autoreset = 0;
+  a.full_obs = 0;
+  hipEvent_t e0, e1;
+  HIPCHK(h, hipEventCreate(&e0)); HIPCHK(h, hipEventCreate(&e1));
+  const size_t dyn = (size_t)G * offsetof(EnvState, hd);
+  auto launch = [&]() {
+    switch (G) {
+      case 1: hipLaunchKernelGGL(k_policy_probe<1>, dim3(waves), dim3(WAVE), dyn, h->stream, a, d_cyc); break;
+      case 2: hipLaunchKernelGGL(k_policy_probe<2>, dim3(waves), dim3(WAVE), dyn, h->stream, a, d_cyc); break;
+      case 4: hipLaunchKernelGGL(k_policy_probe<4>, dim3(waves), dim3(WAVE), dyn, h->stream, a, d_cyc); break;
+      default: hipLaunchKernelGGL(k_policy_probe<8>, dim3(waves), dim3(WAVE), dyn, h->stream, a, d_cyc); break;
+    }
+  };
+  if (G != 1 && G != 2 && G != 4 && G != 8) { h->err = "cc4_debug_policy_probe: G is 1, 2, 4 or 8"; (void)hipFree(d_cyc); return -2; }
+  if (G == 8) HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_policy_probe<8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
+  launch();                                                     // warm-up
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipEventRecord(e0, h->stream));
+  for (int i = 0; i < reps; ++i) launch();
+  HIPCHK(h, hipEventRecord(e1, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  float ms = 0.f; HIPCHK(h, hipEventElapsedTime(&ms, e0, e1));
+  std::vector<unsigned long long> cyc((size_t)waves);
+  HIPCHK(h, hipMemcpy(cyc.data(), d_cyc, cyc.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  double sum = 0; for (auto c : cyc) sum += (double)c;
+  out[0] = (double)ms * 1000.0 / (reps > 0 ? reps : 1); out[1] = sum / waves; out[2] = waves;
+  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipFree(d_cyc);
+  return 0;
+#endif
+}
+// test hook: the persistent schedule's progress words as if `base` steps had run since they were last cleared (every episode's word = base, no
+// runner; pool_base = base) -- the wrap of persist_launch within a few steps' reach
+int cc4_debug_persist_base(cc4_handle* h, uint32_t base) {
+  if (h->rollout_k > 0) { h->err = "cc4_debug_persist_base: a rollout is in flight on this handle"; return -2; }
+  if (base > 0x700000u) { h->err = "cc4_debug_persist_base: base 0 .. 0x700000"; return -2; }
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  if (join_groups(h)) return -1;
+  if (h->persist_state == 0) { if (persist_setup(h)) return -1; }
+  if (h->persist_state != 1) { h->err = "cc4_debug_persist_base: this handle has no persistent kernel"; return -2; }
+  HIPCHK(h, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->d_run + 2 * (size_t)h->run_G), (int)base, (size_t)h->cfg.num_envs, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->pool_base = base;
+  return 0;
+}
+int cc4_debug_copy_from_device(cc4_handle* h, void* host_dst, const void* device_src, size_t bytes) {
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  if (join_groups(h)) return -1;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  for (int g = 0; g < 4; ++g) if (h->gpolicy[g]) HIPCHK(h, hipStreamSynchronize(h->gpolicy[g]));
+  HIPCHK(h, hipMemcpy(host_dst, device_src, bytes, hipMemcpyDeviceToHost));
+  return 0;
+}
+// debug / test hook: every all-gather is preceded by a kernel that keeps the communication stream busy for about `us`
+// microseconds -- an exchange slower than the step, which is what makes the observation ring's reuse guard work for its living
+int cc4_debug_comm_delay_us(cc4_handle* h, int us) {
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  h->comm_delay_ticks = (long long)us * wall_khz(h) / 1000;
+  return 0;
+}

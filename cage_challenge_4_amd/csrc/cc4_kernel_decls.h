@@ -1,4 +1,4 @@
-// cc4_kernel_decls.h -- the kernels of libcc4.so as the host side (cc4_api.hip) sees them: declarations only; each is defined -- and, where it is a
+// cc4_kernel_decls.h -- the kernels of libcc4.so as the host side (cc4_api*.hip) sees them: declarations only; each is defined -- and, where it is a
 // template, explicitly instantiated -- in the translation unit cc4_kernels.h names.
 #pragma once
 #include "cc4_kernels.h"

@@ -1,6 +1,6 @@
 // cc4_kernels.h -- what the translation units of libcc4.so share: the argument blocks of the kernels (StepArgs, XchgArgs, RunArgs, ResetArgs),
 // the device helpers every step kernel uses (row staging, packed observation rows, the exchange's slab protocol, the schedule of the persistent
-// kernel), and the declarations of the kernels for the host side (csrc/cc4_api.hip).  The kernels themselves:
+// kernel), and the declarations of the kernels for the host side (csrc/cc4_api*.hip, cc4_host.h).  The kernels themselves:
 //   cc4_k_pcg.hip      numpy-stream mode: k_step<LOG>, k_run_pcg
 //   cc4_k_philox4.hip  counter mode, four wavefronts per episode: k_step_philox<LOG, MINW>, k_run_philox, k_run_philox8
 //   cc4_k_philox1.hip  counter mode, one wavefront per episode: k_step_philox1<LOG>, k_run_philox1m (cc4_philox1_body.h: the step's body)

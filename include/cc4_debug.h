@@ -28,7 +28,7 @@ int cc4_debug_comm_delay_us(cc4_handle* h, int us);
  * row back; 14 = whole steps, still of the full build; 0 = off.  Restore the batch (cc4_set_state / cc4_set_cold) after such a step. */
 int cc4_debug_stop_phase(cc4_handle* h, int phase);
 
-/* debug: where a rollout stands (see csrc/cc4_api.hip) */
+/* debug: where a rollout stands (see csrc/cc4_api_debug.hip) */
 int cc4_debug_rollout_state(cc4_handle* h, int64_t* out /* [22] */);
 /* test hook: the persistent schedule's progress words as if `base` steps had run since they were last cleared (they are cleared when a call would take
  * them past 0x700000): every episode's word = base, no last runner.  Sets up the persistent path if that was not done yet.  -2: no persistent

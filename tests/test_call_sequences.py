@@ -13,7 +13,7 @@ from rollout_util import hash_policy, pack_rows
 
 pytestmark = pytest.mark.gpu
 
-WRAP = 0x700000          # persist_launch clears the progress words when a call would take them past this many steps (csrc/cc4_api.hip)
+WRAP = 0x700000          # persist_launch clears the progress words when a call would take them past this many steps (csrc/cc4_api_run.hip)
 RING = 32                # slabs of packed observation rows a rollout keeps (cc4_rollout_obs_packed)
 
 

@@ -285,6 +285,42 @@ def test_enqueue_threads_change_nothing(threads, monkeypatch):
         dev.close(); ora.close()
 
 
+_PER_STEP = {'CC4_MULTISTEP': '0', 'CC4_RUN1': '0', 'CC4_PERSIST': '0'}
+
+
+@pytest.mark.parametrize('n,env,comm,run_kernel', [(1024, {}, False, 'k_run_philox'),
+                                                   (1024, dict(_PER_STEP, CC4_ENQ_THREADS='1'), False, 'k_step_philox'),
+                                                   (1024, dict(_PER_STEP, CC4_ENQ_THREADS='0'), False, 'k_step_philox'),
+                                                   (1024, {'CC4_EXCHANGE_INKERNEL': '0'}, True, 'k_step_philox'),
+                                                   (6656, {}, False, 'k_run_philox1')],
+                         ids=['one-launch', 'threaded-groups', 'per-step-attached-events', 'per-step-markers', 'persistent'])
+def test_timed_call_reports_a_time_inside_its_wall_time(n, env, comm, run_kernel, monkeypatch):
+    """The value cc4_run_random_steps reports for a timed call, in every schedule that computes it: one launch (the launch's own events),
+    one enqueue thread per group (a pair of events per group, the slowest group), per-step launches with the events riding on the first and
+    the last launch, per-step launches with marker events around chunks of 25 steps (a communicator; 60 steps = three chunks, summed), the
+    persistent kernel.  The call ends in a host synchronisation behind its last launch, so the on-stream time it reports lies inside the
+    host's wall time around the call: 0 < ms <= wall, by construction and not by measurement."""
+    import time
+    for k_, v in env.items():
+        monkeypatch.setenv(k_, v)
+    K, seed0 = 60, 606
+    dev = _dev(n, steps=100, rng_mode=1, autoreset=True)
+    dev.reset(seeds=seed0)
+    if comm:
+        _one_rank_comm(dev)
+        assert not dev.exchange_info()['in_kernel']
+    assert dev.run_kernel_for(K) == run_kernel
+    if env.get('CC4_ENQ_THREADS'):
+        assert dev.launches_per_step > 1                      # (the enqueue threads serve the groups beyond the first)
+    dev.run_random_steps(seed0, 0, K, timed=True)             # warm-up: the timing events, the persistent kernel's set-up, the worker threads
+    w0 = time.perf_counter()
+    ms = dev.run_random_steps(seed0, K, K, timed=True)
+    wall = (time.perf_counter() - w0) * 1e3
+    print(f'timed call of {K} steps, {n} episodes, {run_kernel}: reported {ms:.3f} ms, wall {wall:.3f} ms')
+    assert 0 < ms <= wall, (ms, wall)
+    dev.close()
+
+
 @pytest.mark.parametrize('mode,kernel', [(1, 'k_run_philox1'), (0, 'k_run_pcg')], ids=['counter', 'numpy-stream'])
 def test_persistent_kernel_and_its_shared_tail(mode, kernel):
     """The persistent run kernel of large batches: many short calls -- every call ends in a tail whose items the CUs of an XCD share
