@@ -53,6 +53,27 @@ StepArgs step_args(const cc4_handle* h) {
   a.reset_ws = h->d_reset_ws;
   return a;
 }
+// The same for the persistent kernels' RunArgs of a k-step call: the schedule's tables and the runs its k steps are cut into -- nB runs of SB steps and
+// `single` single steps close the call, runs of SA fill the rest (what is left over goes to the single steps).  persist_launch sets by name what is
+// per call: the ticket counters' parity, base, the rollout's fields, the timeline.
+RunArgs run_args(const cc4_handle* h, int k, uint32_t t0) {
+  RunArgs ra{};
+  ra.progress = h->d_run; ra.slot_part = h->d_slot_part;
+  ra.P = h->run_P; ra.K = k; ra.G = h->run_G; ra.t0 = t0;
+  memcpy(ra.xcc_lo, h->xcc_lo, 8); memcpy(ra.xcc_n, h->xcc_n, 8);
+  ra.thr = h->run_thr;
+  ra.SA = 1; ra.nA = k; ra.SB = 1; ra.nB = 0; ra.nph = k;      // every step a run of its own (CC4_PERSIST_RUNS with SA = 1; a rollout)
+  const int SA = h->run_SA > 0 ? h->run_SA : (k >= 64 ? 8 : 4);
+  if (SA > 1) {
+    int single = h->run_single < k ? h->run_single : k;
+    int nB = h->run_SB > 1 ? h->run_nB : 0;
+    while (nB > 0 && single + nB * h->run_SB > k) --nB;
+    const int nA = (k - single - nB * h->run_SB) / SA;
+    single = k - nA * SA - nB * h->run_SB;
+    ra.SA = SA; ra.nA = nA; ra.SB = h->run_SB > 1 ? h->run_SB : 1; ra.nB = nB; ra.nph = nA + nB + single;
+  }
+  return ra;
+}
 
 // How a step of this handle is cut into launches, and which build of the counter-mode kernel they run (the kernels are
 // chosen from what one LAUNCH puts on a CU and from what the whole batch does).
@@ -147,9 +168,6 @@ void launch_range(cc4_handle* h, StepArgs a, int e0, int e1, hipStream_t st, boo
     else if (full) hipExtLaunchKernelGGL((k_step_philox<true, 1>), grid, dim3(PT), sizeof(EnvState), st, start, stop, 0, a);
     else if (h->philox_minw == 8) hipExtLaunchKernelGGL((k_step_philox<false, 8>), grid, dim3(PT), sizeof(EnvState), st, start, stop, 0, a);
     else if (h->philox_minw == 7) hipExtLaunchKernelGGL((k_step_philox<false, 7>), grid, dim3(PT), sizeof(EnvState), st, start, stop, 0, a);
-#ifndef CC4_SMALL_MINW
-#define CC4_SMALL_MINW 1
-#endif
     else hipExtLaunchKernelGGL((k_step_philox<false, CC4_SMALL_MINW>), grid, dim3(PT), sizeof(EnvState), st, start, stop, 0, a);
   } else {
     if (full || h->d_prof) hipExtLaunchKernelGGL(k_step<true>, grid, dim3(WAVE), lds1, st, start, stop, 0, a);
@@ -382,7 +400,6 @@ int cc4_create(const cc4_config* cfg, cc4_handle** out) {
   HIPCHK(h, hipStreamSynchronize(h->stream));
   if (choose_run_form(h, 0)) return -1;
   if (const char* v = getenv("CC4_PERSIST_MIN_K")) h->persist_min_k = atoi(v);
-  if (const char* v = getenv("CC4_PERSIST_ORDER")) h->persist_order = atoi(v);
   if (const char* v = getenv("CC4_WHOLE_BATCH_STEPS")) h->whole_batch_steps = atoi(v) != 0;
   if (const char* v = getenv("CC4_PERSIST_VERIFY")) h->verify = atoi(v) != 0;
   if (const char* v = getenv("CC4_PERSIST_VERIFY_EVERY")) h->verify_every = atoi(v) > 0 ? atoi(v) : 0;

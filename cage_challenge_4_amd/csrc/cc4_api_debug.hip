@@ -82,51 +82,6 @@ int cc4_debug_stop_phase(cc4_handle* h, int phase) {
   return 0;
 }
 
-// debug: the red policy phase of every episode with G episodes' agents per wave; out[0] = mean launch duration in us, out[1] = mean cycles
-// of a wave in the phase, out[2] = waves per launch.  Reads the batch as it stands, writes nothing back.
-int cc4_debug_policy_probe(cc4_handle* h, int32_t G, int32_t reps, double* out) {
-#ifndef CC4_POLICY_PROBE
-  (void)G; (void)reps; (void)out;
-  h->err = "cc4_debug_policy_probe: this library was built without -DCC4_POLICY_PROBE (the experiment of DESIGN 3.4 is concluded; tools/policy_group_probe.py says how to build it)";
-  return -2;
-#else
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  if (h->cfg.rng_mode != 1) { h->err = "cc4_debug_policy_probe: counter mode only"; return -2; }
-  if (join_groups(h)) return -1;
-  const int n = h->cfg.num_envs, waves = (n + G - 1) / G;
-  unsigned long long* d_cyc = nullptr;
-  HIPCHK(h, hipMalloc(&d_cyc, (size_t)waves * sizeof(unsigned long long)));
-  StepArgs a = step_args(h);
-  a.autoreset = 0;
-  a.full_obs = 0;
-  hipEvent_t e0, e1;
-  HIPCHK(h, hipEventCreate(&e0)); HIPCHK(h, hipEventCreate(&e1));
-  const size_t dyn = (size_t)G * offsetof(EnvState, hd);
-  auto launch = [&]() {
-    switch (G) {
-      case 1: hipLaunchKernelGGL(k_policy_probe<1>, dim3(waves), dim3(WAVE), dyn, h->stream, a, d_cyc); break;
-      case 2: hipLaunchKernelGGL(k_policy_probe<2>, dim3(waves), dim3(WAVE), dyn, h->stream, a, d_cyc); break;
-      case 4: hipLaunchKernelGGL(k_policy_probe<4>, dim3(waves), dim3(WAVE), dyn, h->stream, a, d_cyc); break;
-      default: hipLaunchKernelGGL(k_policy_probe<8>, dim3(waves), dim3(WAVE), dyn, h->stream, a, d_cyc); break;
-    }
-  };
-  if (G != 1 && G != 2 && G != 4 && G != 8) { h->err = "cc4_debug_policy_probe: G is 1, 2, 4 or 8"; (void)hipFree(d_cyc); return -2; }
-  if (G == 8) HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_policy_probe<8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
-  launch();                                                     // warm-up
-  HIPCHK(h, hipGetLastError());
-  HIPCHK(h, hipEventRecord(e0, h->stream));
-  for (int i = 0; i < reps; ++i) launch();
-  HIPCHK(h, hipEventRecord(e1, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  float ms = 0.f; HIPCHK(h, hipEventElapsedTime(&ms, e0, e1));
-  std::vector<unsigned long long> cyc((size_t)waves);
-  HIPCHK(h, hipMemcpy(cyc.data(), d_cyc, cyc.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-  double sum = 0; for (auto c : cyc) sum += (double)c;
-  out[0] = (double)ms * 1000.0 / (reps > 0 ? reps : 1); out[1] = sum / waves; out[2] = waves;
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipFree(d_cyc);
-  return 0;
-#endif
-}
 // test hook: the persistent schedule's progress words as if `base` steps had run since they were last cleared (every episode's word = base, no
 // runner; pool_base = base) -- the wrap of persist_launch within a few steps' reach
 int cc4_debug_persist_base(cc4_handle* h, uint32_t base) {
@@ -136,7 +91,7 @@ int cc4_debug_persist_base(cc4_handle* h, uint32_t base) {
   if (join_groups(h)) return -1;
   if (h->persist_state == 0) { if (persist_setup(h)) return -1; }
   if (h->persist_state != 1) { h->err = "cc4_debug_persist_base: this handle has no persistent kernel"; return -2; }
-  HIPCHK(h, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->d_run + 2 * (size_t)h->run_G), (int)base, (size_t)h->cfg.num_envs, h->stream));
+  HIPCHK(h, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->d_run), (int)base, (size_t)h->cfg.num_envs, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->pool_base = base;
   return 0;

@@ -198,7 +198,7 @@ int persist_setup(cc4_handle* h) {
   if (!h->d_slot_part) HIPCHK(h, hipMalloc(&h->d_slot_part, CC4_SLOTS * sizeof(int32_t)));
   HIPCHK(h, hipMemcpy(h->d_slot_part, table.data(), CC4_SLOTS * sizeof(int32_t), hipMemcpyHostToDevice));
   if (h->d_run) { (void)hipFree(h->d_run); h->d_run = nullptr; }
-  h->run_words = 2 * (size_t)h->run_G + n;                                            // [P ticket | P owner | n progress]: one memset per call
+  h->run_words = (size_t)n;                                                           // the progress words
   HIPCHK(h, hipMalloc(&h->d_run, h->run_words * sizeof(uint32_t)));
   HIPCHK(h, hipMemset(h->d_run, 0, h->run_words * sizeof(uint32_t)));
   h->persist_state = 1;
@@ -306,24 +306,14 @@ int persist_launch(cc4_handle* h, StepArgs a, int k, uint32_t t0, const XchgArgs
   unsigned long long* d_tl = nullptr;
   if (getenv("CC4_PERSIST_TIMELINE")) { HIPCHK(h, hipMalloc(&d_tl, 4 * sizeof(unsigned long long) * (size_t)h->run_grid)); HIPCHK(h, hipMemsetAsync(d_tl, 0, 4 * sizeof(unsigned long long) * (size_t)h->run_grid, h->stream)); }
   h->d_timeline = d_tl;
-  RunArgs ra{h->d_run, h->d_run + 2 * h->run_G, reinterpret_cast<int32_t*>(h->d_run + h->run_G), h->d_slot_part, h->run_P, k, h->run_G, t0, d_tl, h->persist_order,
-             1, k, 1, 0, k, 0, 0u, nullptr, {0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF}, {0}, {0}, h->run_thr};
-  const int SA = rollout ? 1 : (h->run_SA > 0 ? h->run_SA : (k >= 64 ? 8 : 4));
-  if (SA > 1) {
-    // runs of steps: nB runs of SB and tail_single single steps close the call, runs of SA fill the rest (what is left over goes to the single steps)
-    int single = h->run_single < k ? h->run_single : k;
-    int nB = h->run_SB > 1 ? h->run_nB : 0;
-    while (nB > 0 && single + nB * h->run_SB > k) --nB;
-    const int nA = (k - single - nB * h->run_SB) / SA;
-    single = k - nA * SA - nB * h->run_SB;
-    ra.SA = SA; ra.nA = nA; ra.SB = h->run_SB > 1 ? h->run_SB : 1; ra.nB = nB; ra.nph = nA + nB + single;
-  }
-  ra.pool = 2; ra.base = h->pool_base;      // (2: the per-CU partitions balanced inside the XCD, the only schedule since r06)
+  RunArgs ra = run_args(h, k, t0);
   ra.ticket = h->d_pool + (size_t)h->pool_parity * CC4_SLOTS * TK_STRIDE;
   ra.ticket_next = h->d_pool + (size_t)(h->pool_parity ^ 1) * CC4_SLOTS * TK_STRIDE;
-  memcpy(ra.xcc_pool, h->xcc_pool, 8); memcpy(ra.xcc_lo, h->xcc_lo, 8); memcpy(ra.xcc_n, h->xcc_n, 8);
+  ra.base = h->pool_base;
+  ra.timeline = d_tl;
   h->pool_parity ^= 1; h->pool_base += (uint32_t)k;
   if (rollout) {
+    ra.SA = 1; ra.nA = k; ra.SB = 1; ra.nB = 0; ra.nph = k;      // every step a run of its own
     ra.act_ready = h->d_rready; ra.act = h->d_ract; ra.PG = h->rpg;
     ra.act_wait_ticks = (long long)h->rollout_watchdog_ms * wall_khz(h);
   }

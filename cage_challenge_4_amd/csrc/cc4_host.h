@@ -1,8 +1,26 @@
 // cc4_host.h -- what the host-side translation units of libcc4.so share (cc4_api*.hip; no kernel unit includes it): the handle, the enqueue
 // threads' block, and the helpers that are called across units.  Those are part of no ABI: hidden, so that libcc4.so exports the C ABI only.
 #pragma once
-#include "cc4_kernels.h"
+#include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
+#include <rccl/rccl.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <string>
+#include <chrono>
+#include <vector>
+#include <map>
+#include <algorithm>
+#include <thread>
+#include <mutex>
+#include <condition_variable>
+#include <atomic>
+
+#include "../../include/cc4_debug.h"
+#include "cc4_args.h"
 #include "cc4_kernel_decls.h"
+#include "cc4_export.h"
 #define CC4_HOST __attribute__((visibility("hidden")))
 
 struct cc4_handle {
@@ -72,25 +90,22 @@ struct cc4_handle {
   // externally submitted red / green actions (cc4_step_ex).  Once a handle has taken any, its steps run the full builds of the
   // kernels (an action queued for several ticks carries its own rates into later steps), with d_ext all XA_NONE for the steps
   // that submit nothing
-  // the persistent run kernel (k_run_philox1: K steps of the batch in one launch; RunArgs): per-partition ticket
-  // counters, per-episode progress, partition owners in ONE buffer (cleared by one memset per call), the CU table
-  uint32_t* d_run = nullptr;      // [P ticket | P owner | n progress]
+  // the persistent run kernel (k_run_philox1: K steps of the batch in one launch; RunArgs): per-episode progress, the CU table, the ticket counters
+  uint32_t* d_run = nullptr;      // [n] progress words
   int32_t* d_slot_part = nullptr; // [CC4_SLOTS] CU slot id -> 1 + partition (persist_setup)
   unsigned long long* d_timeline = nullptr;   // CC4_PERSIST_TIMELINE: per-wave time stamps of the current persistent launch
   size_t run_words = 0;           // words of d_run
-  int run_P = 0, run_grid = 0;    // partitions (= CUs that take waves; XCD pools: = XCDs), waves per launch; 0: the persistent path is off
+  int run_P = 0, run_grid = 0;    // partitions (= CUs that take waves), waves per launch; 0: the persistent path is off
   int run_G = 0;                  // exchange groups of the persistent kernel (episode e counts in group e % run_G): the device's CUs
   uint8_t xcc_lo[8] = {0}, xcc_n[8] = {0};
-  int run_thr = 16;               // schedule 2: a wave helps the partition that lags most once its own is more than this many tickets ahead (CC4_PERSIST_THR)
-  uint8_t xcc_pool[8] = {0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF};
-  uint32_t* d_pool = nullptr;     // [2][8][TK_STRIDE] the pools' ticket counters, one set per call parity
+  int run_thr = 16;               // a wave helps the partition that lags most once its own is more than this many tickets ahead (CC4_PERSIST_THR)
+  uint32_t* d_pool = nullptr;     // [2][CC4_SLOTS][TK_STRIDE] the partitions' ticket counters, one set per call parity
   int run_SA = 0, run_SB = 1, run_nB = 0, run_single = 0;   // runs of steps (RunArgs.SA ..; CC4_PERSIST_RUNS="SA,SB,nB,single"; SA = 1: every step an item, as in r05;
                                                             // SA = 0: chosen per call -- 4 steps, 8 in calls of 64 steps and more: profiles/r06_runs_ab.txt, r06_sched_ab2.txt)
-  uint32_t pool_base = 0;         // steps every episode's progress word stands at (XCD pools: the words are not cleared between calls)
+  uint32_t pool_base = 0;         // steps every episode's progress word stands at (the words are not cleared between calls)
   int pool_parity = 0;
   int persist_state = -1;         // -1 off / unavailable, 0 not set up yet (persist_setup on first use), 1 on
   bool whole_batch_steps = true;  // CC4_WHOLE_BATCH_STEPS=0: the step entry points always launch per group (A/B)
-  int persist_order = 0;          // RunArgs.order (CC4_PERSIST_ORDER)
   int run_margin = 0;             // episode blocks per CU the one-launch forms leave free (choose_run_form)
   // the per-step hand-off out of the one-launch kernels (XchgArgs): with a communicator, cc4_run_random_steps stays ONE launch and the
   // communication stream follows the kernel's per-step counters (xchg_*)
@@ -194,6 +209,7 @@ CC4_HOST int sync_all(cc4_handle* h);
 CC4_HOST int wall_khz(cc4_handle* h);
 CC4_HOST int ensure_watchdog_word(cc4_handle* h);
 CC4_HOST StepArgs step_args(const cc4_handle* h);
+CC4_HOST RunArgs run_args(const cc4_handle* h, int k, uint32_t t0);
 CC4_HOST void launch_group(cc4_handle* h, StepArgs a, int g, bool full, hipEvent_t start, hipEvent_t stop);
 CC4_HOST void launch_range(cc4_handle* h, StepArgs a, int e0, int e1, hipStream_t st, bool full, hipEvent_t start, hipEvent_t stop);
 CC4_HOST int launch_step(cc4_handle* h, const int32_t* d_actions, const uint8_t* d_msgs, bool rand = false, uint64_t seed0 = 0, uint32_t t = 0, bool ext_uploaded = false, bool api_step = false);

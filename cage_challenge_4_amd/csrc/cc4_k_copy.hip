@@ -7,6 +7,7 @@
 //   k_copy_episodes  one workgroup per entry.  Entries with an index out of range, a duplicated destination, a source that is also a
 //                    destination of the call, or a bank slot that was never written / comes from another configuration are skipped and
 //                    say so in the fault word (CF_*).  The others copy; no two of them write the same row, and none reads a row another writes.
+#include "cc4_kernels.h"
 #include "cc4_kernel_decls.h"
 
 constexpr int CT = 256;                          // threads per entry (four waves)

@@ -1,4 +1,5 @@
 // cc4_k_misc.hip -- k_reset and the small kernels of libcc4.so (exchange gate, CU discovery, stand-in policies, seeds, digest, event-log helpers).
+#include "cc4_persist.h"      // (cu_slot: k_discover)
 #include "cc4_kernel_decls.h"
 
 // The gate of a chunk of steps [k_lo, k_hi] on the communication stream: returns when every group has counted all its episodes in every
@@ -46,25 +47,9 @@ __global__ __launch_bounds__(WAVE) void k_reset(ResetArgs a) {
   HostDyn* const hd = s->hd;
   for (int i = lane; i < (int)(sizeof(StepWork) / 4); i += WAVE) reinterpret_cast<uint32_t*>(&work)[i] = 0;
   __syncthreads();
-  if (a.rng_mode == 1) {   // counter-based mode: the phases of env_reset_counter_mode, hosts on lanes (the row stays in HBM here)
+  if (a.rng_mode == 1) {   // counter-based mode: hosts on lanes, the main stream walked in place (the row stays in HBM here)
     __shared__ uint32_t ws[RESET_WS_WORDS];
-    Ctx xm{s, cold_e, &s->rng, hd, &work};
-    ResetCarry carry; carry.env_key = 0;
-    reset_zero(s, hd, cold_e, lane, WAVE);
-    __syncthreads();
-    if (lane == 0) carry = reset_topology(xm, a.seeds ? a.seeds[e] : 0, a.steps, a.seeds == nullptr, a.policy, a.topo, ws, false);
-    __syncthreads();
-    Rng rh; rng_fork(&rh, &s->rng, ST_GEN_HOST); rh.mode = 1;
-    Ctx xh{s, cold_e, &rh, hd, &work};
-    for (int h = lane; h < MAXH; h += WAVE) reset_gen_host(xh, h);
-    __syncthreads();
-    if (lane == 0) { reset_pid_serial(xm, reset_used_set(s)); reset_agents(xm); }     // pid uniqueness in the reference's order (one lane; once per episode)
-    __syncthreads();
-    reset_used_clear(s, lane, WAVE);
-    __syncthreads();
-    for (int h = lane; h < MAXH; h += WAVE) reset_host_sessions(xh, h);
-    __syncthreads();
-    if (lane == 0) reset_finish(xm, carry, a.steps, a.topo, false);
+    reset_counter_mode_block<WAVE, false>(s, hd, cold_e, &work, lane, ws, a.seeds ? a.seeds[e] : 0, a.seeds == nullptr, a.steps, a.policy, a.topo);
     __syncthreads();
   } else if (lane == 0) {
     Ctx x{s, cold_e, &s->rng, hd, &work};

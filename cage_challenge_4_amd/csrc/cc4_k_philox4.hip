@@ -12,10 +12,7 @@
 // episode is the build; 5 and 6 (fewer red agents sharing a wave) run 25-30 % slower at 1024 episodes, DESIGN.md 7.
 // Cross-thread effects are event-bit ORs and the reward sum (LDS atomics); the rare order-dependent spawns (PhishingEmail,
 // cross-subnet session reassignment) are collected and replayed by thread 0 in agent order.
-#ifndef CC4_PW
-#define CC4_PW 4
-#endif
-constexpr int PW = CC4_PW;         // waves per episode block; red agent r runs on wave r % PW, lane r / PW
+constexpr int PW = 4;              // waves per episode block; red agent r runs on wave r % PW, lane r / PW
 static_assert(PW >= 4 && PW <= 8, "waves 0/1 run the two green action lists, waves PW-2 and PW-1 the green draws, wave PW-1 the blue submissions");
 constexpr int PT = PW * WAVE;      // threads per episode block (256)
 
@@ -55,9 +52,6 @@ __device__ __forceinline__ void dma_wait() { asm volatile("s_waitcnt vmcnt(0)" :
 // size.  Measured on MI355X (r02, M agent-env steps/s, MINW 1 / 7 / 8): 1536 episodes 185 / 229 / 215, 2048: 222 / 233 / 261
 // (exactly one round of 8), 3072: 253 / 295 / 281, 4096: 275 / 320 / 318, 8192: 320 / 393 / 389, 16384: 332 / 414 / 399;
 // 1024 episodes: 167 with MINW 1 vs 156 with 8.
-#ifndef CC4_PHILOX_BIG_MINW
-#define CC4_PHILOX_BIG_MINW 7
-#endif
 // one step of one episode on a block of four wavefronts: the body of k_step_philox and of its multi-step form k_run_philox
 // RUN (k_run_philox): the row stays in LDS from one step of the episode to the next -- run_flags bit 0: not the first step of the
 // launch (nothing is staged in), bit 1: the last one (the whole row goes back; before it, none of it)
@@ -109,24 +103,9 @@ __device__ __forceinline__ void philox4_body(StepArgs a, const int run_flags = 0
   if (do_reset) {
     dma_wait();
     __syncthreads();
-    // new episode on the same key (CybORG.reset(seed=None)): the phases of env_reset_counter_mode, hosts on threads
-    reset_zero(s, hd, cold_e, tid, PT);
-    __syncthreads();
-    Rng rr; ResetCarry carry; carry.env_key = 0;     // thread 0: main reset stream in registers, across the phases
-    Ctx xm{s, cold_e, &rr, hd, &work};
-    if (tid == 0) { rr = s->rng; rr.mode = 1; carry = reset_topology(xm, 0, a.steps, true, a.policy, a.topo, reset_ws, true); }
-    __syncthreads();
-    Rng rh; rng_fork(&rh, &s->rng, ST_GEN_HOST); rh.mode = 1;
-    Ctx xh{s, cold_e, &rh, hd, &work};
-    if (tid < MAXH) reset_gen_host(xh, tid);
-    __syncthreads();
-    if (tid == 0) { reset_pid_serial(xm, reset_used_set(s)); reset_agents(xm); }      // pid uniqueness in the reference's order (one thread; once per episode)
-    __syncthreads();
-    reset_used_clear(s, tid, PT);
-    __syncthreads();
-    if (tid < MAXH) reset_host_sessions(xh, tid);
-    __syncthreads();
-    if (tid == 0) { reset_finish(xm, carry, a.steps, a.topo, true); a.reward[e] = s->reward; a.done[e] = s->done; }
+    // new episode on the same key (CybORG.reset(seed=None)), hosts on threads
+    reset_counter_mode_block<PT, true>(s, hd, cold_e, &work, tid, reset_ws, 0, true, a.steps, a.policy, a.topo);
+    if (tid == 0) { a.reward[e] = s->reward; a.done[e] = s->done; }
     __syncthreads();
   } else {
     // the mission phase of this step, evaluated by every thread (four words of the row); thread 0 alone stores what
@@ -155,10 +134,7 @@ __device__ __forceinline__ void philox4_body(StepArgs a, const int run_flags = 0
       const ExtAct* const xt = (LOG && a.ext) ? a.ext + (size_t)e * EXT_PER_ENV : nullptr;   // this episode's submitted red / green actions
       Ctx x0{s, cold_e, &rl, hd, &work, tid == 0 ? prof : nullptr};         // thread 0
       x0.lg = lg; x0.ext = xt;
-#ifndef CC4_RED_WAVES
-#define CC4_RED_WAVES 2
-#endif
-      constexpr int RW = CC4_RED_WAVES;                                           // red agent r on wave r % RW, lane r / RW
+      constexpr int RW = 2;                                                       // red agent r on wave r % RW, lane r / RW
       const int ragent = lane * RW + wave;
       const bool is_red = wave < RW && lane < (NRED + RW - 1) / RW && ragent < NRED;
       unsigned long long* ap = (a.prof && is_red) ? a.prof + PROF_SLOTS * (size_t)e + 16 + 8 * ragent : nullptr;
@@ -167,10 +143,7 @@ __device__ __forceinline__ void philox4_body(StepArgs a, const int run_flags = 0
       // with the agents on 2 / 3 / 4 waves in these phases): 1024 episodes 177.4 / 179.3 / 180.8, 2048: 297.2 / 309.1 / 312.1,
       // 4096: 440 / 444 / 443.  (The policy phase stays on two waves, three agents side by side: its other two waves carry the
       // blue submissions and the green draws; all four there: 176.8 / 293.3 / 426.7.)
-#ifndef CC4_RED_WAVES_EXEC
-#define CC4_RED_WAVES_EXEC 4
-#endif
-      constexpr int RWX = CC4_RED_WAVES_EXEC;
+      constexpr int RWX = 4;
       const int xagent = lane * RWX + wave;
       const bool is_redx = wave < RWX && lane < (NRED + RWX - 1) / RWX && xagent < NRED;
       unsigned long long* apx = (a.prof && is_redx) ? a.prof + PROF_SLOTS * (size_t)e + 16 + 8 * xagent : nullptr;
@@ -233,10 +206,7 @@ __device__ __forceinline__ void philox4_body(StepArgs a, const int run_flags = 0
       // ---- P3b blue execution
       if (blue_exec_independent(s)) {      // uniform: every thread reads the same five action types
         if (tid == 0) CC4_TICK(x0, 3);
-#ifndef CC4_BLUE_WAVES
-#define CC4_BLUE_WAVES PW
-#endif
-        constexpr int BW = CC4_BLUE_WAVES;
+        constexpr int BW = PW;
         const int bagent = lane * BW + wave;                                      // blue agent b on wave b % BW, lane b / BW
         if (wave < BW && lane < (NBLUE + BW - 1) / BW && bagent < NBLUE) {
           Ctx xb{s, cold_e, &rl, hd, &work, nullptr, nullptr, lg};
@@ -372,19 +342,12 @@ __device__ __forceinline__ void run_philox_loop(StepArgs a, int K, uint32_t t0, 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (x.slab && threadIdx.x < WAVE) {
-      // As in the one-wave loops: the row of step k - 1 is in memory by now (this step's drain covered its store) and is counted; this step's
-      // row goes out from the byte row in LDS -- no global loads, nothing waited for (a system-scope store takes ~1.5 us to land: inside the
-      // drain it was 1.4 us of every step; read back from the int32 row, the loads were).  The slab must be free: its previous occupant, step
-      // k - ring, gathered -- checked here, by the one wave that writes it, not by the block at the top of the step.
-      const int e = a.e0 + (int)blockIdx.x;
-      if (threadIdx.x == 0) { if (k > 0) xchg_count(x, (uint32_t)(k - 1), e >> 5); xchg_wait_slab(x, (uint32_t)k, seen); }
-      store_packed_row(x.slab + ((size_t)(k % x.ring) * (size_t)a.n + (size_t)e) * OBS_PACKED, xrow, (int)threadIdx.x, WAVE);
+      // this step's row goes out from the byte row in LDS -- no global loads, nothing waited for (a system-scope store takes ~1.5 us to land: inside the
+      // drain it was 1.4 us of every step; read back from the int32 row, the loads were)
+      xchg_step_out<true>(x, a.n, a.e0 + (int)blockIdx.x, k, seen, [&](uint8_t* row) { store_packed_row(row, xrow, (int)threadIdx.x, WAVE); });
     }
   }
-  if (x.slab && K > 0) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (threadIdx.x == 0) xchg_count(x, (uint32_t)(K - 1), (a.e0 + (int)blockIdx.x) >> 5);
-  }
+  xchg_last_out(x, a.e0 + (int)blockIdx.x, K);
 }
 __global__ __launch_bounds__(PT, 5) void k_run_philox(StepArgs a, int K, uint32_t t0, XchgArgs x) { run_philox_loop<5>(a, K, t0, x); }
 // the same with the register budget of eight blocks per CU: batches of up to 8 x CUs episodes (2048 on MI355X) resident at once

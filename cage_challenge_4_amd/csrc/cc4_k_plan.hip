@@ -4,9 +4,6 @@
 #include "cc4_philox1_body.h"
 #include "cc4_persist.h"
 
-#ifndef CC4_PERSIST_MINW
-#define CC4_PERSIST_MINW 6
-#endif
 // k steps of the batch in one launch with the blue actions of step j from row j of a plan the caller wrote before the launch (PlanArgs): no exchange,
 // no rollout protocol -- nothing outside the kernel is waited for.  Register budget as k_run_philox1 (six waves per SIMD).
 __global__ __launch_bounds__(WAVE, CC4_PERSIST_MINW) void k_run_philox1p(StepArgs a, RunArgs ra, PlanArgs pl) { persist_loop<false, false, false, true>(a, ra, XchgArgs{}, pl); }

@@ -1,12 +1,9 @@
 // cc4_kernel_decls.h -- the kernels of libcc4.so as the host side (cc4_api*.hip) sees them: declarations only; each is defined -- and, where it is a
 // template, explicitly instantiated -- in the translation unit cc4_kernels.h names.
 #pragma once
-#include "cc4_kernels.h"
+#include "cc4_args.h"
 
 constexpr int PT = 4 * WAVE;       // threads per episode block of the four-wave kernels (cc4_k_philox4.hip: PW = 4)
-#ifndef CC4_SMALL_MINW
-#define CC4_SMALL_MINW 1
-#endif
 // per-step kernels
 template <bool LOG> __global__ void k_step(StepArgs a);
 template <bool LOG, int MINW> __global__ void k_step_philox(StepArgs a);
@@ -64,8 +61,5 @@ __global__ void k_digest(const EnvState* st, const EnvCold* cold, size_t cold_ro
                          const uint8_t* done, const uint32_t* err, const int32_t* actions, uint64_t* out, int n);
 extern "C" __global__ void k_set_evlog(EnvCold* cold, size_t row_bytes, int n, uint32_t on);
 extern "C" __global__ void k_copy_evlog(EnvCold* dst, const EnvCold* src, size_t row_bytes, int n);
-#ifdef CC4_POLICY_PROBE
-template <int G> __global__ void k_policy_probe(StepArgs a, unsigned long long* cyc);
-#endif
 // the numpy-stream kernels' jump table (cc4_k_pcg.hip)
 hipError_t cc4_upload_pcg_tables();

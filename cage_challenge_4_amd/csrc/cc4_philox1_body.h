@@ -12,32 +12,11 @@
 // host table in HBM / L2, so 16 episodes are resident per CU (LDS) instead of 7-8.  The build for throughput-bound batches;
 // k_step_philox keeps the shorter single-launch latency of small ones (cc4_create picks; CC4_PHILOX_LEAN overrides).
 // the one-wave kernel's in-kernel scenario generation (an episode regenerates once in steps-per-episode launches)
-#if defined(CC4_EXP_RESET_CALL)
-__device__ __attribute__((noinline))
-#else
-__device__ __forceinline__
-#endif
-void philox1_autoreset(const StepArgs& a, const int e, const int lane, EnvState* s, HostDyn* const hd, EnvCold* const cold_e, StepWork& work) {
-    // new episode on the same key (CybORG.reset(seed=None)): the phases of env_reset_counter_mode, hosts on lanes; the pid
-    // bitmaps of the generation live in HBM here (LDS bounds this kernel's residency, and this path runs once per episode)
-    uint32_t* const ws = a.reset_ws + (size_t)e * RESET_WS_WORDS;
-    reset_zero(s, hd, cold_e, lane, WAVE);
-    __syncthreads();
-    Rng rr; ResetCarry carry; carry.env_key = 0;     // lane 0: main reset stream in registers, across the phases
-    Ctx xm{s, cold_e, &rr, hd, &work};
-    if (lane == 0) { rr = s->rng; rr.mode = 1; carry = reset_topology(xm, 0, a.steps, true, a.policy, a.topo, ws, true); }
-    __syncthreads();
-    Rng rh; rng_fork(&rh, &s->rng, ST_GEN_HOST); rh.mode = 1;
-    Ctx xh{s, cold_e, &rh, hd, &work};
-    for (int h = lane; h < MAXH; h += WAVE) reset_gen_host(xh, h);
-    __syncthreads();
-    if (lane == 0) { reset_pid_serial(xm, reset_used_set(s)); reset_agents(xm); }     // pid uniqueness in the reference's order (one lane; once per episode)
-    __syncthreads();
-    reset_used_clear(s, lane, WAVE);
-    __syncthreads();
-    for (int h = lane; h < MAXH; h += WAVE) reset_host_sessions(xh, h);
-    __syncthreads();
-    if (lane == 0) { reset_finish(xm, carry, a.steps, a.topo, true); a.reward[e] = s->reward; a.done[e] = s->done; }
+__device__ __forceinline__ void philox1_autoreset(const StepArgs& a, const int e, const int lane, EnvState* s, HostDyn* const hd, EnvCold* const cold_e, StepWork& work) {
+    // new episode on the same key (CybORG.reset(seed=None)), hosts on lanes; the pid bitmaps of the generation live in HBM here (LDS bounds this
+    // kernel's residency, and this path runs once per episode)
+    reset_counter_mode_block<WAVE, true>(s, hd, cold_e, &work, lane, a.reset_ws + (size_t)e * RESET_WS_WORDS, 0, true, a.steps, a.policy, a.topo);
+    if (lane == 0) { a.reward[e] = s->reward; a.done[e] = s->done; }
     __syncthreads();
 }
 
@@ -53,9 +32,12 @@ void philox1_autoreset(const StepArgs& a, const int e, const int lane, EnvState*
 #endif
 #define CC4_STOP_ON (LOG || CC4_STOP_IN_FAST)
 #define CC4_STOP(n) do { if (CC4_STOP_ON && a.dbg_stop == (n)) return; } while (0)
+// LOG: the full build of a step kernel -- it records the HostEvents entries of the step (cc4_enable_event_log) and takes externally
+// submitted red / green actions (cc4_step_ex: StepArgs.ext).  A template parameter rather than a run-time flag: even a never-taken
+// logging branch at the eleven event sites costs the serial walk 10 %.
 template <bool LOG, bool PERSIST>
 __device__ __forceinline__ void philox1_body(StepArgs a, const int e, const uint32_t rand_t, const uint32_t item_k, const int lane,
-                                             const bool first, const bool last) {
+                                             const bool first = true, const bool last = true) {
   extern __shared__ uint4 lds[];
   // Static LDS is kept under 512 bytes: agent part (7168 B) + statics then fit SIX 1280-byte LDS granules, 21 waves per CU by LDS and 20
   // by registers; a seventh granule would leave 18 (profiles/r05_lds_residency.txt: the occupancy query, which divides 160 KB by the

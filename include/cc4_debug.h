@@ -1,6 +1,5 @@
 /* cc4_debug.h -- debug, experiment and test hooks of libcc4.so.  Not part of the drop-in boundary (include/cc4.h): nothing a user of the reference's
- * API needs; tools/ and tests/ call them.  The experiment cc4_debug_policy_probe exists only in libraries built with -DCC4_POLICY_PROBE
- * (tools/policy_group_probe.py; DESIGN 3.4: a concluded experiment of r05). */
+ * API needs; tools/ and tests/ call them. */
 #ifndef CC4_DEBUG_H
 #define CC4_DEBUG_H
 #include "cc4.h"
@@ -11,9 +10,6 @@ extern "C" {
 /* debug: per-episode cycle counters of the step kernels ([N][128] u64: 16 phase slots, 8 per red agent, then (cycles, count) per red action type; see
  * tools/phase_profile.py, tools/tail_profile.py) */
 int cc4_debug_profile(cc4_handle* h, int enable, unsigned long long* out);
-/* debug / experiment: the red policy phase of every episode with the agents of G = 1 / 2 / 4 / 8 episodes side by side on one wave, on the
- * batch as it stands (nothing is written back).  out[0] = mean launch duration (us), out[1] = mean cycles of a wave in the phase, out[2] = waves per launch. */
-int cc4_debug_policy_probe(cc4_handle* h, int32_t G, int32_t reps, double* out);
 
 /* test hooks: keep the gathered rows of the next `steps` steps exchanged from inside a one-launch kernel (0 frees the log); read `count`
  * of them from step `first` as [count][world*N][CC4_OBS_PACKED_BYTES]; returns the number of steps logged so far. */

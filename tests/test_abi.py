@@ -24,7 +24,6 @@ def test_every_declared_symbol_is_exported():
     lib = ctypes.CDLL(_lib.LIB_PATH)
     for s in syms:
         assert hasattr(lib, s), f'{s} declared under include/ but not exported by libcc4.so'
-    # (cc4_debug_policy_probe: a concluded experiment, compiled only with -DCC4_POLICY_PROBE -- declared, not exported by the product library)
     assert set(syms) == set(_lib.SIGNATURES), 'python binding and header disagree on the ABI'
     assert not [s for s in header_symbols(('cc4.h',)) if s.startswith('cc4_debug_')], 'debug hooks belong in include/cc4_debug.h'
 

@@ -257,6 +257,56 @@ def test_timed_bench_path_matches_oracle(n, kernel, run_kernel):
     dev.close()
 
 
+def _assert_same_packed_states(dev, ora, n):
+    assert np.array_equal(dev.rng_state(), ora.rng_state())
+    for i in range(n):
+        a_, b_ = dev.get_state(i), ora.get_state(i)
+        assert np.array_equal(a_, b_), f'packed state differs env {i} at byte offsets {np.nonzero(a_ != b_)[0][:20].tolist()}'
+
+
+def test_counter_mode_regeneration_is_the_same_in_every_kernel(philox_kernel):
+    """The counter-mode scenario generation is ONE sequence (reset_counter_mode_block) that k_reset, the per-step kernels and the one-launch
+    kernels call with 64 or 256 threads: 12 episodes of 30 steps against the oracle, every episode regenerating twice.  137 hosts on 64 or
+    256 threads is independent of the batch size, so this is the smallest shape at which a wrong stride or a missing barrier in the shared
+    sequence shows.  Part A: k_reset and the per-step kernel, 70 calls of step().  Part B: a fresh handle, run_random_steps in bursts of
+    7 / 40 / 23 steps on the one-launch kernel of the same family (k_run_philox / k_run_philox1m, which a handle of 12 episodes selects
+    by itself)."""
+    n, steps, seed0 = 12, 30, 9000
+    run_kernel = {'k_step_philox': 'k_run_philox', 'k_step_philox1': 'k_run_philox1m'}[philox_kernel]
+    # ---- A
+    dev = _dev(n, steps=steps, rng_mode=1, autoreset=True)
+    assert dev.step_kernel == philox_kernel
+    ora = OracleVecEnv(n, steps=steps, rng_mode=1, autoreset=True)
+    assert np.array_equal(dev.reset(seeds=seed0), ora.reset(seeds=seed0))
+    for t in range(70):
+        a = random_actions(seed0, t, n)
+        d = dev.step(a)
+        o = ora.step_batch(a)
+        assert np.array_equal(d[0], o[0]) and np.array_equal(d[1], o[1]) and np.array_equal(d[2], o[2]), t
+        assert np.array_equal(d[3]['err'], o[3]['err']), t
+    _assert_same_packed_states(dev, ora, n)
+    dev.close(); ora.close()
+    # ---- B
+    dev = _dev(n, steps=steps, rng_mode=1, autoreset=True)
+    assert dev.run_kernel_for(7) == run_kernel, dev.run_kernel_for(7)
+    ora = OracleVecEnv(n, steps=steps, rng_mode=1, autoreset=True)
+    assert np.array_equal(dev.reset(seeds=seed0), ora.reset_batch(seed0))
+    t = 0
+    for K in (7, 40, 23):
+        dev.run_random_steps(seed0, t, K)
+        for k in range(K):
+            a = random_actions(seed0, t + k, n)
+            o = ora.step_batch(a)
+        t += K
+        dev.synchronize()
+        dev._fetch()
+        bad = np.nonzero((dev._obs != o[0]).any(axis=1) | (dev._rew != o[1]) | (dev._done.astype(bool) != o[2]) | (dev._err != o[3]['err']))[0]
+        assert bad.size == 0, (K, t, bad[:10].tolist())
+        assert np.array_equal(dev.device_actions(), a), (K, t)
+    _assert_same_packed_states(dev, ora, n)
+    dev.close(); ora.close()
+
+
 @pytest.mark.parametrize('threads', ['0', '1'])
 def test_enqueue_threads_change_nothing(threads, monkeypatch):
     """cc4_run_random_steps with one enqueue thread per group stream (the default where the host has eight hardware threads)
