@@ -18,6 +18,7 @@ OBS_PACKED_BYTES = 148     # CC4_OBS_PACKED_BYTES: a flat observation at 2 bits 
 NUM_BLUE = 5
 MSG_LEN = 8
 TOPOLOGY_BYTES = 27 + 2 * 137
+FEAT_HOSTS, FEAT_PER_HOST, FEAT_GLOBAL = 137, 16, 32     # CC4_FEAT_*: the state-feature tensors (state_features.py)
 OBS_LEN = (92, 92, 92, 92, 210)
 ACT_LEN = (82, 82, 82, 82, 242)
 OBS_OFF = (0, 92, 184, 276, 368)
@@ -81,6 +82,8 @@ SIGNATURES = {
     'cc4_copy_episodes_device': (ctypes.c_int, [_P, ctypes.c_int32, _P, ctypes.c_int32, _P, _P, ctypes.c_int32, _P, _P]),
     'cc4_copy_faults': (ctypes.c_int, [_P, _P]),
     'cc4_clone_episodes': (ctypes.c_int, [_P, ctypes.c_int32, _P, _P, _P]),
+    'cc4_state_features_device': (ctypes.c_int, [_P, _P, ctypes.c_int32, _P, ctypes.c_int32, _P, _P]),
+    'cc4_state_features_from_row': (ctypes.c_int, [_P, _P, _P]),
     'cc4_rollout_begin': (ctypes.c_int, [_P, ctypes.c_int32]),
     'cc4_rollout_groups': (ctypes.c_int, [_P, _P, _P]),
     'cc4_rollout_policy_stream': (ctypes.c_int, [_P, _P]),

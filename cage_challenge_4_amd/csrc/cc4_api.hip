@@ -1,8 +1,9 @@
 // cc4_api.hip -- the host side of libcc4.so, its core: create / destroy, the episode groups and their streams, the launches of one step (launch_step),
-// reset, the step entry points and the getters, episode copies, state get / set, the event log and the replay.  The handle itself: cc4_host.h; k steps
+// reset, the step entry points and the getters, episode copies, state features, state get / set, the event log and the replay.  The handle itself: cc4_host.h; k steps
 // per call: cc4_api_run.hip; rollouts: cc4_api_rollout.hip; the communicator and the exchange: cc4_api_comm.hip; debug hooks: cc4_api_debug.hip.
 #include "cc4_host.h"
 #include "cc4_export.h"
+#include "cc4_features.h"
 
 static thread_local std::string g_create_err;
 
@@ -823,6 +824,36 @@ int cc4_clone_episodes(cc4_handle* h, int32_t n, const int32_t* src, const int32
   if (seeds) HIPCHK(h, hipMemcpyAsync(h->d_copy_seeds, seeds, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
   if (int rc = cc4_copy_episodes_device(h, n, nullptr, 0, h->d_copy_idx, nullptr, 0, h->d_copy_idx + N, seeds ? h->d_copy_seeds : nullptr)) return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));     // (the host arrays may go away once the call returns)
+  return 0;
+}
+// ---- the true state as tensors (cc4_k_feat.hip; the definition: cc4_features.h).  One launch on the main stream behind the group streams, no host
+// synchronisation; it only reads rows, so the next step launches need no ordering behind it beyond the main stream's own.
+int cc4_state_features_device(cc4_handle* h, const void* d_bank, int32_t capacity, const int32_t* d_ids, int32_t n, uint8_t* d_hosts, int32_t* d_global) {
+  const char* who = "cc4_state_features_device";
+  if (h->rollout_k > 0) { h->err = std::string(who) + ": a rollout is in flight on this handle: cc4_rollout_end first"; return -2; }
+  if (n < 0) { h->err = std::string(who) + ": n < 0"; return -2; }
+  if (n == 0) return 0;
+  if (!d_hosts || reinterpret_cast<uintptr_t>(d_hosts) % 16 || reinterpret_cast<uintptr_t>(d_global) % 4) {
+    h->err = std::string(who) + ": the host-feature buffer is required and must be 16-byte aligned (the episode words: 4-byte aligned or NULL)"; return -2;
+  }
+  if (d_bank && capacity < 1) { h->err = std::string(who) + ": a bank needs a capacity of at least one slot"; return -2; }
+  if (reinterpret_cast<uintptr_t>(d_bank) % 64) { h->err = std::string(who) + ": a bank must be 64-byte aligned"; return -2; }
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  if (join_groups(h)) return -1;
+  FeatArgs a{h->d_state, static_cast<const uint8_t*>(d_bank), slot_bytes(h->cold_row), d_ids, n, d_bank ? capacity : h->cfg.num_envs,
+             h->cfg.steps, h->cfg.rng_mode, d_hosts, d_global, h->d_copy_fault};
+  hipLaunchKernelGGL(k_state_features, dim3(n), dim3(WAVE), 0, h->stream, a);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+// The same definition on the host, from one hot row (cc4_get_state, a checkpoint): no device, no handle.
+int cc4_state_features_from_row(const void* hot_row, uint8_t* hosts, int32_t* global) {
+  if (!hot_row || !hosts) return -2;
+  EnvState* s = static_cast<EnvState*>(aligned_alloc(alignof(EnvState), sizeof(EnvState)));   // (the caller's bytes may sit at any address)
+  if (!s) return -1;
+  memcpy(s, hot_row, sizeof(EnvState));
+  feat_from_row(s, hosts, global);
+  free(s);
   return 0;
 }
 int cc4_synchronize(cc4_handle* h) {

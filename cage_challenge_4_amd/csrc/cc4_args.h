@@ -1,5 +1,5 @@
 // cc4_args.h -- what the host side and the kernels of libcc4.so share: the constants, the argument blocks of the kernels (StepArgs, XchgArgs, RunArgs,
-// PlanArgs, ResetArgs, CopyArgs), the snapshot-slot layout, and the register budgets of the kernels.  No device helper (cc4_kernels.h) and nothing of
+// PlanArgs, ResetArgs, CopyArgs, FeatArgs), the snapshot-slot layout, and the register budgets of the kernels.  No device helper (cc4_kernels.h) and nothing of
 // the C++ host library (cc4_host.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -182,5 +182,17 @@ struct CopyArgs {
   const int32_t* src; const int32_t* dst; const uint64_t* seeds;
   int count, n, src_cap, dst_cap, steps, rng_mode, evlog_on;
   uint32_t stamp;                                        // this call's claims: 2 * stamp (one entry names it), 2 * stamp + 1 (several)
+  uint32_t* fault;
+};
+
+// ---- state features (cc4_state_features_device, cc4_k_feat.hip; the definition: cc4_features.h).  Entry i reads episode ids[i] (null: i) of the handle,
+// or the hot row inside slot ids[i] of a snapshot bank, and writes hosts[i] / glob[i].
+struct FeatArgs {
+  const EnvState* st;                                    // the handle's hot rows (bank == null)
+  const uint8_t* bank; size_t slot;                      // or a snapshot bank and the bytes per slot
+  const int32_t* ids;                                    // [count] or null
+  int count, cap, steps, rng_mode;                       // cap: episodes of the handle / slots of the bank
+  uint8_t* hosts;                                        // [count][137][16], 16-byte aligned
+  int32_t* glob;                                         // [count][32] or null
   uint32_t* fault;
 };

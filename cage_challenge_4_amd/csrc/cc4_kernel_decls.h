@@ -49,6 +49,8 @@ __global__ void k_policy_outputs(const EnvState* __restrict__ st, const int32_t*
 // episode copies (cc4_k_copy.hip): phase 1 claims the destinations, phase 2 copies the live extents
 __global__ void k_copy_claim(CopyArgs a);
 __global__ void k_copy_episodes(CopyArgs a);
+// state features (cc4_k_feat.hip): one wavefront per requested episode or bank slot
+__global__ void k_state_features(FeatArgs a);
 __global__ void k_set_seed(EnvState* st, EnvCold* cold, size_t cold_row, const uint64_t* seeds, int n, int rng_mode);
 __global__ void k_set_rng_state(EnvState* st, const uint64_t* w, int n);
 __global__ void k_rng_state(const EnvState* st, uint64_t* out, int n);

@@ -46,9 +46,12 @@ class CC4TorchVecEnv:
         Faulty entries (an index out of range, a duplicated destination, a source that is also a destination, a slot never written or written
         by another configuration) are skipped; check_errors() raises CC4EngineError for them.
 
+    The privileged global state for a centralised critic (include/cc4.h cc4_state_features_device; cage_challenge_4_amd.state_features):
+    state_features(ids=None, bank=None, out=None) -> (hosts [n, 137, 16] uint8, glob [n, 32] int32)   of the env's episodes, or of the slots of a bank
+
     No call synchronises except check_errors(), which reads the error flags and raises what CC4VecEnv raises (ValueError for a step past
     the episode's end -- the reference's own error -- and CC4EngineError for any other flag; strict=False: the ValueError only), and raises
-    CC4EngineError for the faults of the copies since the last call."""
+    CC4EngineError for the faults of the copies and state_features calls since the last call."""
 
     def __init__(self, num_envs, *, obs_dtype=torch.uint8, **kw):
         if obs_dtype not in _OBS_DTYPES:
@@ -213,6 +216,38 @@ class CC4TorchVecEnv:
 
     def load_episodes(self, bank, slots, env_ids, seeds=None):
         return self._copy(slots, env_ids, src_bank=bank, seeds=seeds)
+
+    def state_features(self, ids=None, bank=None, out=None):
+        """The privileged global state (cc4_state_features_device, include/cc4.h; columns and words: state_features.HOST_COLUMNS / GLOBAL_WORDS)
+        as tensors on the env's device: (hosts [n, 137, 16] uint8, glob [n, 32] int32).  ids: 1-D integer tensor on the device -- episodes of
+        the env, or with bank= (a new_bank tensor) the slots of saved episodes, read where they lie; None: all episodes / all slots.
+        out=(hosts, glob) reuses the caller's tensors.  Ordered on the current stream both ways like step(); no host copy, no host wait.  A
+        faulty entry (an index out of range, a slot never written or written by another configuration) gives an all-zero row, and
+        check_errors() raises CC4EngineError for it."""
+        with torch.cuda.device(self.device):
+            s = torch.cuda.current_stream(self.device)
+            vp = ctypes.c_void_p
+            bp, cap = self._bank(bank) if bank is not None else (None, 0)
+            if ids is not None:
+                ids = self._index(ids, 'ids')
+                n, ip = int(ids.numel()), vp(ids.data_ptr())
+            else:
+                n, ip = (cap if bank is not None else self.num_envs), None
+            shapes = ((n, L.FEAT_HOSTS, L.FEAT_PER_HOST), (n, L.FEAT_GLOBAL))
+            if out is None:
+                hosts = torch.empty(shapes[0], dtype=torch.uint8, device=self.device)
+                glob = torch.empty(shapes[1], dtype=torch.int32, device=self.device)
+            else:
+                hosts, glob = out
+                for x, shp, dt in ((hosts, shapes[0], torch.uint8), (glob, shapes[1], torch.int32)):
+                    if not torch.is_tensor(x) or tuple(x.shape) != shp or x.dtype != dt or x.device != self.device or not x.is_contiguous():
+                        raise ValueError(f'out must be contiguous tensors (uint8 {list(shapes[0])}, int32 {list(shapes[1])}) on {self.device}')
+            lib, h, sp = self.lib, self._h, vp(s.cuda_stream)
+            rc = lib.cc4_stream_wait(h, sp) or lib.cc4_state_features_device(h, bp, cap, ip, n, vp(hosts.data_ptr()), vp(glob.data_ptr()))
+            if rc:
+                self.venv._chk(rc, 'cc4_state_features_device')
+            self.venv._chk(lib.cc4_stream_signal(h, sp), 'cc4_stream_signal')
+        return hosts, glob
 
     def check_errors(self):
         """The one synchronising call: reads the error flags of the last step / reset and raises what CC4VecEnv.step would have raised

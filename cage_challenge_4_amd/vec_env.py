@@ -383,6 +383,39 @@ class CC4VecEnv:
         raise_on_copy_faults(faults.value)
         return self._check_err()[0]
 
+    def state_features(self, env_ids=None):
+        """The privileged global state of the batch (cc4_state_features_device, include/cc4.h; columns and words: state_features.HOST_COLUMNS /
+        GLOBAL_WORDS): (hosts [n, 137, 16] uint8, glob [n, 32] int32) of episodes env_ids (None: all), as NumPy arrays.  Synchronises, like
+        the other getters.  An index out of range gives an all-zero row and raises CC4EngineError after the call."""
+        ids = None if env_ids is None else np.ascontiguousarray(env_ids, dtype=np.int32).ravel()
+        n = self.num_envs if ids is None else int(ids.size)
+        hosts = np.zeros((n, L.FEAT_HOSTS, L.FEAT_PER_HOST), np.uint8)
+        glob = np.zeros((n, L.FEAT_GLOBAL), np.int32)
+        if n == 0:
+            return hosts, glob
+        hip, vp = _hip(), ctypes.c_void_p
+        b_ids = ((4 * n + 15) & ~15) if ids is not None else 0          # [ids | hosts | glob]: every part 16-byte aligned
+        _hip_chk(hip.hipSetDevice(self._dev), 'hipSetDevice')
+        d = vp()
+        _hip_chk(hip.hipMalloc(ctypes.byref(d), b_ids + hosts.nbytes + glob.nbytes), 'hipMalloc')
+        try:
+            if ids is not None:
+                _hip_chk(hip.hipMemcpy(d, ids.ctypes.data_as(vp), ids.nbytes, 1), 'hipMemcpy')
+            d_hosts, d_glob = vp(d.value + b_ids), vp(d.value + b_ids + hosts.nbytes)
+            rc = self.lib.cc4_state_features_device(self._h, None, 0, d if ids is not None else None, n, d_hosts, d_glob)
+            rc2 = self.lib.cc4_synchronize(self._h)
+            if rc or rc2:
+                self._chk(rc or rc2, 'cc4_state_features_device')
+            _hip_chk(hip.hipMemcpy(hosts.ctypes.data_as(vp), d_hosts, hosts.nbytes, 2), 'hipMemcpy')
+            _hip_chk(hip.hipMemcpy(glob.ctypes.data_as(vp), d_glob, glob.nbytes, 2), 'hipMemcpy')
+        finally:
+            hip.hipFree(d)
+        if ids is not None and ((ids < 0) | (ids >= self.num_envs)).any():
+            faults = ctypes.c_uint32(0)
+            self._chk(self.lib.cc4_copy_faults(self._h, ctypes.byref(faults)), 'cc4_copy_faults')
+            raise_on_copy_faults(faults.value)
+        return hosts, glob
+
     def plan_kernel_for(self, k):
         """cc4_plan_kernel_for: the kernel a run_plan / step_plan call of k steps launches ('k_run_philox1p' / 'k_run_pcgp': one launch for the
         whole plan; else the step kernel, once per step)."""
@@ -539,7 +572,7 @@ _hip_lib = None
 
 def _hip():
     """The HIP runtime libcc4.so is linked against, reached through libcc4.so's own handle (a symbol lookup there searches its dependencies: no
-    second search of the loader's path), for the host-array surface's staging buffers (run_plan)."""
+    second search of the loader's path), for the host-array surface's staging buffers (run_plan, state_features)."""
     global _hip_lib
     if _hip_lib is None:
         lib = ctypes.CDLL(L.LIB_PATH)
