@@ -227,6 +227,24 @@ void cc4o_rng_script(uint64_t seed, int mode, int n, const int32_t* ops, const u
   }
 }
 
+// cc4o_rng_script on the numpy stream, started from the six state words cc4o_set_rng_state takes (s_hi s_lo inc_hi inc_lo has_uint32 uinteger)
+// instead of a seed: a caller that chose the state knows which output the script meets where.  final (or null) receives the seven words of
+// cc4o_rng_state after the last op.
+void cc4o_rng_script_state(const uint64_t* w, int n, const int32_t* ops, const uint32_t* args, uint64_t* out, uint64_t* final) {
+  Rng r; rng_seed(&r, 0, 0);
+  r.s_hi = w[0]; r.s_lo = w[1]; r.inc_hi = w[2]; r.inc_lo = w[3]; r.has32 = (uint32_t)w[4]; r.u32 = (uint32_t)w[5];
+  for (int i = 0; i < n; ++i) {
+    switch (ops[i]) {
+      case 0: { double d = rng_random(&r); memcpy(&out[i], &d, 8); break; }
+      case 1: out[i] = rng_below(&r, args[i]); break;
+      case 2: rng_shuffle_consume(&r, (int)args[i]); out[i] = 0; break;
+      case 3: out[i] = rng_next64(&r); break;
+      default: out[i] = rng_next32(&r); break;
+    }
+  }
+  if (final) { final[0] = r.s_hi; final[1] = r.s_lo; final[2] = r.inc_hi; final[3] = r.inc_lo; final[4] = r.has32; final[5] = r.u32; final[6] = r.ndraw; }
+}
+
 // counter mode: the threshold forms of a uniform draw (cc4_rng.h rng_random_lt / rng_random_le / rng_random_quarter) and the raw words, one op per entry:
 // 0: rng_random_lt(t[i])  1: rng_random_le(t[i])  2: rng_random_quarter  3: rng_next32  4: rng_set_stream((uint32)t[i])
 void cc4o_rng_script2(uint64_t seed, int mode, int n, const int32_t* ops, const double* t, uint64_t* out) {

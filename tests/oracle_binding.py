@@ -268,6 +268,24 @@ class OracleVecEnv:
         return buf.raw[:n].decode()
 
 
+def rng_script_state(words, ops, args):
+    """cc4o_rng_script_state: the draw script of cc4o_rng_script (ops 0 random() 1 below(arg) 2 shuffle_consume(arg) 3 next64 4 next32) on the numpy
+    stream started from six state words (pcg64_words of a Generator).  Returns (values uint64 [len(ops)], the seven words of rng_state() at the end)."""
+    lib = load()
+    n = len(ops)
+    w = np.array([int(x) for x in words], np.uint64)
+    assert w.shape == (6,)
+    ops = np.asarray(ops, np.int32)
+    args = np.asarray(args, np.uint32)
+    out = np.zeros(n, np.uint64)
+    final = np.zeros(7, np.uint64)
+    P = lambda v: v.ctypes.data_as(ctypes.c_void_p)   # noqa: E731
+    lib.cc4o_rng_script_state.argtypes = [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 4
+    lib.cc4o_rng_script_state.restype = None
+    lib.cc4o_rng_script_state(P(w), n, P(ops), P(args), P(out), P(final))
+    return out, final
+
+
 def random_actions(seed0, t, num_envs):
     """Host restatement of k_random_actions (csrc/cc4_k_misc.hip): Philox4x32-10 key (seed0+env), counter (t, agent, 0xB10E, 0)."""
     M0, M1, W0, W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
