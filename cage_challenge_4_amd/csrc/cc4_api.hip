@@ -54,25 +54,15 @@ StepArgs step_args(const cc4_handle* h) {
   a.reset_ws = h->d_reset_ws;
   return a;
 }
-// The same for the persistent kernels' RunArgs of a k-step call: the schedule's tables and the runs its k steps are cut into -- nB runs of SB steps and
-// `single` single steps close the call, runs of SA fill the rest (what is left over goes to the single steps).  persist_launch sets by name what is
-// per call: the ticket counters' parity, base, the rollout's fields, the timeline.
+// The same for the persistent kernels' RunArgs of a k-step call: the schedule's tables and the runs its k steps are cut into (run_split, cc4_sched.h).
+// persist_launch sets by name what is per call: the ticket counters' parity, base, the rollout's fields, the timeline.
 RunArgs run_args(const cc4_handle* h, int k, uint32_t t0) {
   RunArgs ra{};
   ra.progress = h->d_run; ra.slot_part = h->d_slot_part;
   ra.P = h->run_P; ra.K = k; ra.G = h->run_G; ra.t0 = t0;
   memcpy(ra.xcc_lo, h->xcc_lo, 8); memcpy(ra.xcc_n, h->xcc_n, 8);
   ra.thr = h->run_thr;
-  ra.SA = 1; ra.nA = k; ra.SB = 1; ra.nB = 0; ra.nph = k;      // every step a run of its own (CC4_PERSIST_RUNS with SA = 1; a rollout)
-  const int SA = h->run_SA > 0 ? h->run_SA : (k >= 64 ? 8 : 4);
-  if (SA > 1) {
-    int single = h->run_single < k ? h->run_single : k;
-    int nB = h->run_SB > 1 ? h->run_nB : 0;
-    while (nB > 0 && single + nB * h->run_SB > k) --nB;
-    const int nA = (k - single - nB * h->run_SB) / SA;
-    single = k - nA * SA - nB * h->run_SB;
-    ra.SA = SA; ra.nA = nA; ra.SB = h->run_SB > 1 ? h->run_SB : 1; ra.nB = nB; ra.nph = nA + nB + single;
-  }
+  ra.runs = run_split(k, h->run_SA, h->run_SB, h->run_nB, h->run_single);
   return ra;
 }
 

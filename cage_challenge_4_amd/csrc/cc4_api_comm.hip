@@ -9,7 +9,8 @@
 // slabs, publish gathered = k + 1.  After the main stream's synchronisation: the communication stream drained, the watchdog flag read.
 int xchg_begin(cc4_handle* h, int k, XchgArgs* x) {
   (void)k;
-  const size_t groups = (size_t)h->cfg.num_envs / 32 + 1 > (size_t)h->cus ? (size_t)h->cfg.num_envs / 32 + 1 : (size_t)h->cus;
+  // counter rows for either kind of group: the partitions of the persistent kernel (one per CU) or groups of 32 neighbouring episodes
+  const size_t groups = (size_t)(xchg_groups32_alloc(h->cfg.num_envs) > h->cus ? xchg_groups32_alloc(h->cfg.num_envs) : h->cus);
   {
     const size_t nb = (size_t)h->cfg.num_envs * OBS_PACKED;
     if (!h->d_xslab) HIPCHK(h, hipMalloc(&h->d_xslab, nb * cc4_handle::XRING));
@@ -35,7 +36,7 @@ int xchg_begin(cc4_handle* h, int k, XchgArgs* x) {
 int xchg_enqueue(cc4_handle* h, int k, const XchgArgs& x, int form) {
   const size_t row = (size_t)h->cfg.num_envs * OBS_PACKED;
   const int C = h->xchg_chunk, n = h->cfg.num_envs;
-  const int P = form == 3 ? h->run_G : 0, groups = form == 3 ? h->run_G : (n + 31) / 32;
+  const int P = form == 3 ? h->run_G : 0, groups = form == 3 ? h->run_G : xchg_groups32(n);
   const long long gate_ticks = 30000LL * wall_khz(h);         // 30 s: a step kernel that never gets there (the host would wait for it forever anyway)
   for (int c0 = 0, hi = 0; c0 < k; c0 = hi + 1) {
     hi = (c0 + C < k ? c0 + C : k) - 1;

@@ -86,7 +86,7 @@ int cc4_debug_stop_phase(cc4_handle* h, int phase) {
 // runner; pool_base = base) -- the wrap of persist_launch within a few steps' reach
 int cc4_debug_persist_base(cc4_handle* h, uint32_t base) {
   if (h->rollout_k > 0) { h->err = "cc4_debug_persist_base: a rollout is in flight on this handle"; return -2; }
-  if (base > 0x700000u) { h->err = "cc4_debug_persist_base: base 0 .. 0x700000"; return -2; }
+  if (base > PROGRESS_CLEAR_AT) { char msg[64]; snprintf(msg, sizeof msg, "cc4_debug_persist_base: base 0 .. %#x", PROGRESS_CLEAR_AT); h->err = msg; return -2; }
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   if (join_groups(h)) return -1;
   if (h->persist_state == 0) { if (persist_setup(h)) return -1; }

@@ -11,7 +11,7 @@ static int rollout_ready(cc4_handle* h, const char* who) {
 int cc4_rollout_begin(cc4_handle* h, int32_t k) {
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   if (h->rollout_k > 0) { h->err = "cc4_rollout_begin: a rollout is in flight (cc4_rollout_end)"; return -2; }
-  if (k <= 0 || k > 0x100000) { h->err = "cc4_rollout_begin: 1 .. 2^20 steps"; return -2; }
+  if (k <= 0 || k > ROLLOUT_MAX_K) { h->err = "cc4_rollout_begin: 1 .. 2^20 steps"; return -2; }
   if (h->cfg.rng_mode != 1 || h->comm || h->evlog_on || h->ext_seen || h->d_prof) { h->err = "cc4_rollout_begin: for counter-mode handles without a communicator, event log or submitted red / green actions"; return -2; }
   if (h->persist_state == 0) { if (persist_setup(h)) return -1; }
   if (h->persist_state != 1) { h->err = "cc4_rollout_begin: this handle has no persistent kernel (a batch the chip holds at once, or a device picture the schedule refuses): step it with cc4_step_device"; return -2; }
@@ -111,7 +111,7 @@ int cc4_rollout_random_policy(cc4_handle* h, int32_t g, int32_t j, uint64_t seed
   if (g < 0 || g >= h->rpg || j < 0 || j >= h->rollout_k) { h->err = "cc4_rollout_random_policy: group or step out of range"; return -2; }
   hipStream_t st = hip_stream ? (hipStream_t)hip_stream : h->gpolicy[g];
   const int tot = h->cfg.num_envs * NBLUE;
-  const int grp = ((h->cfg.num_envs + h->run_P - 1) / h->run_P + h->rpg - 1) / h->rpg * h->run_P * NBLUE;      // threads over the group's episodes (whole blocks of P)
+  const int grp = pgroup_threads(h->cfg.num_envs, h->run_P, h->rpg) * NBLUE;      // threads over the group's episodes (whole blocks of P), one per agent
   hipLaunchKernelGGL(k_rollout_random_policy, dim3((grp + WAVE - 1) / WAVE), dim3(WAVE), 0, st, h->d_ract + (size_t)(j & 1) * (size_t)tot, h->cfg.num_envs, h->run_P, h->rpg, (int)g, seed0, t);
   HIPCHK(h, hipGetLastError());
   return 0;
@@ -122,7 +122,7 @@ int cc4_rollout_hash_policy(cc4_handle* h, int32_t g, int32_t j, void* hip_strea
   hipStream_t st = hip_stream ? (hipStream_t)hip_stream : h->gpolicy[g];
   const int n = h->cfg.num_envs;
   const uint8_t* rows = h->d_xslab + (size_t)((j + cc4_handle::XRING - 1) % cc4_handle::XRING) * (size_t)n * OBS_PACKED;
-  const int grp = ((n + h->run_P - 1) / h->run_P + h->rpg - 1) / h->rpg * h->run_P;
+  const int grp = pgroup_threads(n, h->run_P, h->rpg);
   hipLaunchKernelGGL(k_rollout_hash_policy, dim3((grp + WAVE - 1) / WAVE), dim3(WAVE), 0, st, h->d_ract + (size_t)(j & 1) * (size_t)n * NBLUE, rows, n, h->run_P, h->rpg, (int)g, (uint32_t)j);
   HIPCHK(h, hipGetLastError());
   return 0;

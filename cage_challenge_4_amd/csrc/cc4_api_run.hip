@@ -182,13 +182,13 @@ int persist_setup(cc4_handle* h) {
   for (int xc = 0; xc < 8; ++xc) {
     int lo = -1, cnt = 0;
     for (int sl = xc << 8; sl < (xc + 1) << 8; ++sl) if (table[sl] > 0) { if (lo < 0) lo = table[sl] - 1; ++cnt; }
-    if (cnt > WAVE || lo > 255) ok = false;          // (one lane per partition of the XCD; the range's start travels as a byte)
-    h->xcc_lo[xc] = (uint8_t)(lo < 0 ? 0 : lo); h->xcc_n[xc] = (uint8_t)(cnt > WAVE ? 0 : cnt);
+    if (cnt > MAX_XCD_PARTITIONS || lo > MAX_XCD_FIRST) ok = false;          // (one lane per partition of the XCD; the range's start travels as a byte)
+    h->xcc_lo[xc] = (uint8_t)(lo < 0 ? 0 : lo); h->xcc_n[xc] = (uint8_t)(cnt > MAX_XCD_PARTITIONS ? 0 : cnt);
   }
   for (int sl = 8 << 8; sl < CC4_SLOTS; ++sl) if (count[sl] > 0) ok = false;          // an XCC id beyond 7: not a device this schedule knows
-  if (P > 510) ok = false;                            // the runner's id in the progress words: 9 bits
+  if (P > MAX_PARTITIONS) ok = false;                 // the runner's id in the progress words (runner_of, cc4_sched.h)
   if (!ok) {
-    fprintf(stderr, "[cc4] the persistent run kernel stays OFF for this handle (per-step launches instead): more than 64 CUs in an XCD, or more than 510 CUs\n");
+    fprintf(stderr, "[cc4] the persistent run kernel stays OFF for this handle (per-step launches instead): more than %d CUs in an XCD, or more than %d CUs\n", MAX_XCD_PARTITIONS, MAX_PARTITIONS);
     h->persist_refused = true;
     return 0;
   }
@@ -299,7 +299,7 @@ int cc4_verify_stats(cc4_handle* h, int64_t* out /* [2] */) { out[0] = h->verify
 // an item of its own, the actions from the rollout's slots behind the caller's publishes).
 // pl: a plan call (cc4_run_plan_device) -- the plan builds k_run_philox1p / k_run_pcgp on the same schedule, tickets and progress words.
 int persist_launch(cc4_handle* h, StepArgs a, int k, uint32_t t0, const XchgArgs& x, hipEvent_t e0, hipEvent_t e1, bool rollout, const PlanArgs* pl) {
-  if (h->pool_base + (uint32_t)k > 0x700000u) {      // (the progress words count steps since they were last cleared)
+  if (h->pool_base + (uint32_t)k > PROGRESS_CLEAR_AT) {      // (the progress words count steps since they were last cleared)
     HIPCHK(h, hipMemsetAsync(h->d_run, 0, h->run_words * sizeof(uint32_t), h->stream));
     h->pool_base = 0;
   }
@@ -313,7 +313,7 @@ int persist_launch(cc4_handle* h, StepArgs a, int k, uint32_t t0, const XchgArgs
   ra.timeline = d_tl;
   h->pool_parity ^= 1; h->pool_base += (uint32_t)k;
   if (rollout) {
-    ra.SA = 1; ra.nA = k; ra.SB = 1; ra.nB = 0; ra.nph = k;      // every step a run of its own
+    ra.runs = run_split_steps(k);
     ra.act_ready = h->d_rready; ra.act = h->d_ract; ra.PG = h->rpg;
     ra.act_wait_ticks = (long long)h->rollout_watchdog_ms * wall_khz(h);
   }

@@ -1,11 +1,12 @@
 // cc4_args.h -- what the host side and the kernels of libcc4.so share: the constants, the argument blocks of the kernels (StepArgs, XchgArgs, RunArgs,
 // PlanArgs, ResetArgs, CopyArgs, FeatArgs), the snapshot-slot layout, and the register budgets of the kernels.  No device helper (cc4_kernels.h) and nothing of
-// the C++ host library (cc4_host.h).
+// the C++ host library (cc4_host.h).  The index arithmetic of the persistent schedule -- partitions, tickets, runs, the progress word -- is in cc4_sched.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "../../include/cc4.h"
 #include "cc4_engine.h"
+#include "cc4_sched.h"
 
 using namespace cc4;
 
@@ -100,18 +101,20 @@ struct XchgArgs {
 //  * No memset between calls.  The ticket counters exist twice, one set per call parity: the wave that draws a partition's last ticket
 //    clears its counter of the other parity; progress[] counts steps since the handle last cleared it (`base` = where every episode
 //    stands when the call starts).
+// The mappings themselves -- episode <-> partition and policy group, ticket -> (run, episode), the runs of K steps, the fields of a progress word and their
+// limits -- are defined ONCE, in cc4_sched.h: kernels, gates, host and the CPU oracle compile the same functions (tests/test_sched_cpu.py).
 // (The schedules before this one -- owned partitions with stealing, per-XCD pools -- are in docs/HISTORY.md.)
 struct RunArgs {
   // ---- constant for a handle (run_args)
-  uint32_t* progress;          // [n] bits 0..22: steps episode e has completed since the words were cleared; bits 23..31: 1 + the partition of the CU
-                               // that ran its last run (0: none yet)
+  uint32_t* progress;          // [n] progress_pack (cc4_sched.h): the steps episode e has completed since the words were cleared | the runner of its last
+                               // run (1 + the partition of that CU; RUNNER_NONE: none yet)
   const int32_t* slot_part;    // [CC4_SLOTS] CU slot id -> 1 + its partition, 0 = no such CU on this device (k_discover at first use: partitions in
                                // slot order, so the CUs of an XCD own neighbouring partitions and their ticket / progress words share cache lines
                                // only with each other -- handed out in arrival order they interleave the XCDs, and a 20-step call was 6 % slower)
   int P, K;
   int G;                       // the exchange counts episode e in group e % G (the gate kernel's groups: G = the CUs of the device)
   uint32_t t0;                 // action time of step 0 (random_blue_action)
-  int SA, nA, SB, nB, nph;     // the runs of this call's K steps
+  RunSplit runs;               // the runs of this call's K steps: SA, nA, SB, nB, nph (run_split)
   uint8_t xcc_lo[8], xcc_n[8]; // XCC id -> first partition / number of partitions of that XCD
   int thr;
   // ---- per call (persist_launch)

@@ -100,7 +100,7 @@ struct cc4_handle {
   uint8_t xcc_lo[8] = {0}, xcc_n[8] = {0};
   int run_thr = 16;               // a wave helps the partition that lags most once its own is more than this many tickets ahead (CC4_PERSIST_THR)
   uint32_t* d_pool = nullptr;     // [2][CC4_SLOTS][TK_STRIDE] the partitions' ticket counters, one set per call parity
-  int run_SA = 0, run_SB = 1, run_nB = 0, run_single = 0;   // runs of steps (RunArgs.SA ..; CC4_PERSIST_RUNS="SA,SB,nB,single"; SA = 1: every step an item, as in r05;
+  int run_SA = 0, run_SB = 1, run_nB = 0, run_single = 0;   // runs of steps (run_split -> RunArgs.runs; CC4_PERSIST_RUNS="SA,SB,nB,single"; SA = 1: every step an item, as in r05;
                                                             // SA = 0: chosen per call -- 4 steps, 8 in calls of 64 steps and more: profiles/r06_runs_ab.txt, r06_sched_ab2.txt)
   uint32_t pool_base = 0;         // steps every episode's progress word stands at (the words are not cleared between calls)
   int pool_parity = 0;

@@ -5,7 +5,7 @@
 // The gate of a chunk of steps [k_lo, k_hi] on the communication stream: returns when every group has counted all its episodes in every
 // step of the chunk (counts of one episode's consecutive steps may arrive out of order: each wave counts where ITS stores have drained),
 // and hands the counters back (zero) for steps k + ring.  P > 0: the groups are the P partitions of the persistent kernel (episodes
-// g, g + P, ..), else groups of 32 neighbouring episodes.  Gives up after `ticks` and says so in *fail (the host reports it).
+// g, g + P, ..: part_episodes), else groups of 32 neighbouring episodes (xchg_group32_size).  Gives up after `ticks` and says so in *fail (the host reports it).
 // ONE wave, polling at a growing interval (4 us .. 31 us; the gate of a call's LAST step, behind which the host waits, stays at 4 us): the gate shares a CU with blocks of the step kernel, and in the multi-step kernels
 // a block is an episode -- whatever slows one CU's blocks sets the pace of the launch (four busily polling waves cost 1024 episodes 1.2 us per step).
 __global__ __launch_bounds__(WAVE) void k_xchg_gate(uint32_t* gcnt, int ring, int groups, int n, int P, int k_lo, int k_hi, long long ticks, uint32_t* fail, int max_naps) {
@@ -13,7 +13,7 @@ __global__ __launch_bounds__(WAVE) void k_xchg_gate(uint32_t* gcnt, int ring, in
   const long long t0 = wall_clock64();
   for (int i = t; i < groups * steps; i += (int)blockDim.x) {
     const int g = i / steps, k = k_lo + i % steps;
-    const int size = P > 0 ? (n - g + P - 1) / P : (n - (g << 5) < 32 ? n - (g << 5) : 32);
+    const int size = P > 0 ? part_episodes(n, P, g) : xchg_group32_size(n, g);
     if (size <= 0) continue;
     uint32_t* c = gcnt + (size_t)g * (size_t)ring + (k % ring);
     int naps = 1;
@@ -197,12 +197,10 @@ __global__ void k_rng_state(const EnvState* st, uint64_t* out, int n) {
 // ---------------------------------------------------------------- rollouts: the caller-side kernels (cc4_rollout_*)
 // gate of a policy pass: returns when every episode of policy group g has its packed row of the step in slot `slot` in memory (the step kernel
 // counts them per partition, RunArgs.act_ready), and hands the counters back zeroed.  One wave, partitions on lanes; gives up after `ticks`.
-__global__ __launch_bounds__(WAVE) void k_rollout_gate(uint32_t* cnt, int P, int PG, int ring, int g, int slot, int n, long long ticks, uint32_t* fail) {
-  __builtin_amdgcn_s_setprio(3);      // these waves run in what the persistent kernel leaves of a CU, beside 23 of its waves per CU: ahead of them in the SIMDs' issue arbitration
+__device__ __forceinline__ void rollout_gate_wait(uint32_t* cnt, int P, int PG, int ring, int g, int slot, int n, long long ticks, uint32_t* fail) {
   const long long t0 = wall_clock64();
   for (int p = (int)threadIdx.x; p < P; p += (int)blockDim.x) {
-    const int ne = (n - p + P - 1) / P;                       // episodes p, p + P, ..: index i is of group i % PG
-    const int want = (ne - g + PG - 1) / PG;
+    const int want = pgroup_episodes(part_episodes(n, P, p), PG, g);      // of episodes p, p + P, ..: number i is of group i % PG
     if (want <= 0) continue;
     uint32_t* c = cnt + ((size_t)p * PG + (size_t)g) * (size_t)ring + slot;
     int naps = 1;
@@ -213,6 +211,10 @@ __global__ __launch_bounds__(WAVE) void k_rollout_gate(uint32_t* cnt, int P, int
     }
     __hip_atomic_store(c, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
+}
+__global__ __launch_bounds__(WAVE) void k_rollout_gate(uint32_t* cnt, int P, int PG, int ring, int g, int slot, int n, long long ticks, uint32_t* fail) {
+  __builtin_amdgcn_s_setprio(3);      // these waves run in what the persistent kernel leaves of a CU, beside 23 of its waves per CU: ahead of them in the SIMDs' issue arbitration
+  rollout_gate_wait(cnt, P, PG, ring, g, slot, n, ticks, fail);
 }
 // publish and gate in one launch (cc4_rollout_sync): first the publish of a pass whose policy kernels precede this kernel on the stream (their stores
 // are in memory: a kernel boundary lies between), then the gate of the next pass.  Half the stream operations of the separate calls.
@@ -220,31 +222,16 @@ __global__ __launch_bounds__(WAVE) void k_rollout_sync(uint32_t* ready, int pub_
   __builtin_amdgcn_s_setprio(3);      // these waves run in what the persistent kernel leaves of a CU, beside 23 of its waves per CU: ahead of them in the SIMDs' issue arbitration
   // the publish: every CU partition's copy of the group's word (RunArgs.act_ready)
   if (pub_g >= 0) for (int p = (int)threadIdx.x; p < P; p += (int)blockDim.x) __hip_atomic_store(ready + (size_t)p * 32 + pub_g, pub_val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  if (g < 0) return;
-  const long long t0 = wall_clock64();
-  for (int p = (int)threadIdx.x; p < P; p += (int)blockDim.x) {
-    const int ne = (n - p + P - 1) / P;
-    const int want = (ne - g + PG - 1) / PG;
-    if (want <= 0) continue;
-    uint32_t* c = cnt + ((size_t)p * PG + (size_t)g) * (size_t)ring + slot;
-    int naps = 1;
-    while (__hip_atomic_load(c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < (uint32_t)want) {
-      for (int q = 0; q < naps; ++q) __builtin_amdgcn_s_sleep(8);
-      if (naps < 8) naps <<= 1;
-      if (wall_clock64() - t0 > ticks) { __hip_atomic_store(fail, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); break; }
-    }
-    __hip_atomic_store(c, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  if (g >= 0) rollout_gate_wait(cnt, P, PG, ring, g, slot, n, ticks, fail);
 }
 // stand-in policies for one policy group (bench.py, tests): uniform random indices (the draws of k_random_actions), or indices computed FROM the
 // packed observations of the step before (a policy that ignores its input proves nothing about the hand-over)
-// (threads over the GROUP's episodes only -- episode i of group g is e = ((i / P) * PG + g) * P + i % P --: a launch is a quarter of the batch's waves,
-// one dispatch round into the slots the persistent kernel leaves free)
-__device__ __forceinline__ int rollout_group_episode(int i, int P, int PG, int g) { return ((i / P) * PG + g) * P + i % P; }
+// (threads over the GROUP's episodes only -- thread i < pgroup_threads is episode pgroup_episode(i, ..) of group g, cc4_sched.h --: a launch is a quarter of the
+// batch's waves, one dispatch round into the slots the persistent kernel leaves free)
 __global__ __launch_bounds__(WAVE) void k_rollout_random_policy(int32_t* act, int n, int P, int PG, int g, uint64_t seed0, uint32_t t) {
   __builtin_amdgcn_s_setprio(3);      // these waves run in what the persistent kernel leaves of a CU, beside 23 of its waves per CU: ahead of them in the SIMDs' issue arbitration
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  const int e = rollout_group_episode(i / NBLUE, P, PG, g), b = i % NBLUE;
+  const int e = pgroup_episode(i / NBLUE, P, PG, g), b = i % NBLUE;
   if (e >= n) return;
   act[e * NBLUE + b] = random_blue_action(seed0, t, e, b);
 }
@@ -255,7 +242,7 @@ __device__ __host__ inline uint32_t rollout_obs_hash(const uint32_t* row) {     
 }
 __global__ __launch_bounds__(WAVE) void k_rollout_hash_policy(int32_t* act, const uint8_t* packed, int n, int P, int PG, int g, uint32_t j) {
   __builtin_amdgcn_s_setprio(3);
-  const int e = rollout_group_episode(blockIdx.x * blockDim.x + threadIdx.x, P, PG, g);
+  const int e = pgroup_episode(blockIdx.x * blockDim.x + threadIdx.x, P, PG, g);
   if (e >= n) return;
   const uint32_t hsh = rollout_obs_hash(reinterpret_cast<const uint32_t*>(packed + (size_t)e * OBS_PACKED));
   for (int b = 0; b < NBLUE; ++b) act[e * NBLUE + b] = (int32_t)((hsh + 2654435761u * (uint32_t)(b + 1) + 40503u * j) % (uint32_t)(b == 4 ? ACT_LONG : ACT_SHORT));

@@ -4,7 +4,8 @@
 //   cc4_k_pcg.hip      numpy-stream mode: k_step<LOG>, k_run_pcg
 //   cc4_k_philox4.hip  counter mode, four wavefronts per episode: k_step_philox<LOG, MINW>, k_run_philox, k_run_philox8
 //   cc4_k_philox1.hip  counter mode, one wavefront per episode: k_step_philox1<LOG>, k_run_philox1m (cc4_philox1_body.h: the step's body)
-//   cc4_k_run1.hip     the persistent kernel of large batches: k_run_philox1 (cc4_persist.h: its schedule, shared with k_run_pcg)
+//   cc4_k_run1.hip     the persistent kernel of large batches: k_run_philox1 (cc4_persist.h: its schedule, shared with k_run_pcg; cc4_sched.h: the index
+//                      arithmetic of that schedule, of the gates and of the host side -- partitions, tickets, runs, the progress word, the groups of 32)
 //   cc4_k_run1x.hip    its other builds: k_run_philox1x (beside RCCL), k_run_philox1r (rollouts with the policy in the loop)
 //   cc4_k_plan.hip     the plan build of the persistent kernel, k_run_philox1p (cc4_run_plan_device), and the plan call's helpers; the numpy-stream
 //                      plan build k_run_pcgp sits beside k_run_pcg (the numpy-stream step body and its jump table are private to cc4_k_pcg.hip)
@@ -94,6 +95,11 @@ __device__ __forceinline__ void pack_row_from_obs(uint8_t* o8, const int32_t* o,
   }
 }
 // ---- the exchange's slab protocol (XchgArgs)
+// lane 0: a wait gave up -- both timeout flags raised, every later wait of the launch returns at once
+__device__ __forceinline__ void raise_timeout(const XchgArgs& x) {
+  __hip_atomic_store(x.timeout, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __hip_atomic_store(x.timeout_host, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
 // lane / thread 0 only.  `seen` = the highest value of *gathered this wave has read so far (it only grows): the word is read again --
 // an uncached round trip to memory, ~2 us in the middle of the item hand-over -- only when the value at hand does not cover step k.
 __device__ __forceinline__ void xchg_wait_slab(const XchgArgs& x, uint32_t k, uint32_t& seen) {
@@ -110,22 +116,16 @@ __device__ __forceinline__ void xchg_wait_slab(const XchgArgs& x, uint32_t k, ui
   while ((seen = __hip_atomic_load(x.gathered, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)) < need) {
     for (int i = 0; i < naps; ++i) __builtin_amdgcn_s_sleep(127);
     if (naps < 16) naps <<= 1;
-    if (wall_clock64() - w0 > x.wait_ticks || __hip_atomic_load(x.timeout, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)) {
-      __hip_atomic_store(x.timeout, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      __hip_atomic_store(x.timeout_host, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      return;
-    }
+    if (wall_clock64() - w0 > x.wait_ticks || __hip_atomic_load(x.timeout, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)) { raise_timeout(x); return; }
   }
 }
 // One episode's packed row of step k is in memory (the stores that wrote it have drained): counted in the episode's group (a partition of
-// the persistent kernel, 32 neighbouring episodes of the multi-step kernels), slot k % ring.  A no-return agent-scope atomic: the wave
+// the persistent kernel: part_of(e, RunArgs.G); 32 neighbouring episodes of the multi-step kernels: xchg_group32(e) -- cc4_sched.h), slot k % ring.  A no-return agent-scope atomic: the wave
 // does not wait for it.  (r05 on the way here: one system-scope counter per step -- 8192 atomics on one word serialise at ~12 ns each,
 // twice the step --, then two levels with the group's last episode adding the group to it -- two dependent atomics, ~2 us per item.)
 __device__ __forceinline__ void xchg_count(const XchgArgs& x, uint32_t k, int group) {
   (void)__hip_atomic_fetch_add(x.gcnt + (size_t)group * (size_t)x.ring + (k % (uint32_t)x.ring), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-// ... and its group in the plain multi-step kernels (k_run_philox, k_run_philox8, k_run_philox1m): 32 neighbouring episodes (k_xchg_gate sizes them so)
-__device__ __forceinline__ int xchg_group32(int e) { return e >> 5; }
 // The hand-off of the plain multi-step loops, every block looping over the K steps of ITS episode e.  xchg_step_out: by the block's first wave, behind the
 // drain of step k (s_waitcnt vmcnt(0), barrier) -- the row of step k - 1 is in memory by now (this step's drain covered its store) and is counted; this
 // step's row goes out through store_row(its place in slab k % ring): from a byte row in LDS (store_packed_row) or read back from the int32 row

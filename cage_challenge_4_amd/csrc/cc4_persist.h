@@ -1,5 +1,6 @@
 // cc4_persist.h -- the schedule of the persistent kernels (k_run_philox1 / k_run_philox1x / k_run_philox1r / k_run_pcg and the plan builds k_run_philox1p / k_run_pcgp): one wave per residency slot pulling runs of
-// steps of episodes from its CU's partition.  See cc4_args.h (RunArgs) and DESIGN 3.3.
+// steps of episodes from its CU's partition.  See cc4_args.h (RunArgs) and DESIGN 3.3; the index arithmetic it rests on -- partitions, tickets, runs, the
+// progress word -- is cc4_sched.h's.
 #pragma once
 #include "cc4_kernels.h"
 
@@ -14,18 +15,7 @@ __device__ __forceinline__ int cu_slot() {
   const uint32_t xcc = __builtin_amdgcn_s_getreg(((4 - 1) << 11) | (0 << 6) | 20);    // HW_REG_XCC_ID bits 3:0
   return (int)(((xcc & 7u) << 8) | ((hw >> 8) & 0xFFu));
 }
-constexpr uint32_t PG_STEPS = 0x7FFFFFu;   // progress word: steps in bits 0..22, 1 + the last runner's partition in bits 23..31 (0: none yet)
-// run j of a call: its first step and its length (RunArgs.SA ..)
-__device__ __forceinline__ void run_span(const RunArgs& ra, int j, int& k0, int& len) {
-  if (j < ra.nA) { k0 = j * ra.SA; len = ra.SA; }
-  else if (j < ra.nA + ra.nB) { k0 = ra.nA * ra.SA + (j - ra.nA) * ra.SB; len = ra.SB; }
-  else { k0 = ra.nA * ra.SA + ra.nB * ra.SB + (j - ra.nA - ra.nB); len = 1; }
-}
-// lane 0: a wait gave up -- both timeout flags raised, every later wait of the launch returns at once
-__device__ __forceinline__ void raise_timeout(const XchgArgs& x) {
-  __hip_atomic_store(x.timeout, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  __hip_atomic_store(x.timeout_host, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
+static_assert(MAX_XCD_PARTITIONS == WAVE, "pick_balanced: one lane per partition of the wave's XCD");
 // lane 0: the actions of step j for policy group g are published.  Polls a device word at a growing interval (see xchg_wait_slab).
 __device__ __forceinline__ void rollout_wait_actions(const RunArgs& ra, const XchgArgs& x, int line, int g, uint32_t j) {
   const uint32_t* w = ra.act_ready + (size_t)line * 32 + g;
@@ -48,7 +38,7 @@ __device__ __forceinline__ uint32_t wait_progress(const RunArgs& ra, const XchgA
   const long long w0 = watchdog ? wall_clock64() : 0;
   uint32_t w;
   ok = true;
-  while ((((w = __hip_atomic_load(&ra.progress[ee], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) & PG_STEPS) - ra.base) < k) {
+  while ((progress_steps(w = __hip_atomic_load(&ra.progress[ee], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) - ra.base) < k) {
     if (watchdog && wall_clock64() - w0 > ra.act_wait_ticks) { raise_timeout(x); ok = false; break; }
     __builtin_amdgcn_s_sleep(8);
   }
@@ -57,15 +47,13 @@ __device__ __forceinline__ uint32_t wait_progress(const RunArgs& ra, const XchgA
 // lane 0, the ticket draw: one ticket of counter idx of partition `line`'s ticket line.  The counter hands out the nph runs of the partition's episodes
 // number idx, idx + pg, .. (pg = 1, idx = 0: all of them; a rollout: policy group idx of pg) in run-major order; whoever draws its last ticket clears the
 // counter of the OTHER parity for the next call (exactly one wave per counter and call draws it, whoever runs the partition -- no memset between calls).
-// false: handed out meanwhile; else run j of episode ee.
+// false: handed out meanwhile; else run j of episode ee (ticket_item, cc4_sched.h).
 __device__ __forceinline__ bool draw_ticket(const RunArgs& ra, int n, int line, int idx, int pg, int& j, int& ee) {
-  const int ne = (n - line + ra.P - 1) / ra.P;                       // episodes line, line + P, ..
-  const uint32_t cnt = (uint32_t)((ne - idx + pg - 1) / pg), total = cnt * (uint32_t)ra.nph;
+  const uint32_t cnt = ticket_count(n, ra.P, line, idx, pg), total = ticket_total(cnt, ra.runs.nph);
   const uint32_t t = __hip_atomic_fetch_add(ra.ticket + line * TK_STRIDE + idx, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (t + 1u == total) __hip_atomic_store(ra.ticket_next + line * TK_STRIDE + idx, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (t >= total) return false;
-  j = (int)(t / cnt);
-  ee = line + ((int)(t % cnt) * pg + idx) * ra.P;
+  ticket_item(t, cnt, line, idx, pg, ra.P, j, ee);
   return true;
 }
 
@@ -75,18 +63,18 @@ template <bool PCG>
 __device__ __forceinline__ void persist_step_out(const StepArgs& a, const RunArgs& ra, const XchgArgs& x, const bool rollout, const int lane, const int e, const uint32_t k,
                                                  int& pend_e, uint32_t& pend_k) {
   if constexpr (PCG) {     // (the numpy-stream body stored the row itself, from its LDS byte row: drained by now)
-    if (lane == 0) xchg_count(x, k, e % ra.G);
+    if (lane == 0) xchg_count(x, k, part_of(e, ra.G));
   } else {
     // the row this wave stored LAST (a step ago, or with its previous item) is in memory -- the drain covered it: counted.  Then this episode's row of
     // step k, read back from the int32 row before the episode's next step may touch it (the loads feed the store, the store is issued ahead of
     // the progress word) -- not waited for: it drains with the wave's next step or item, or when the wave leaves.
-    if (lane == 0 && pend_e >= 0) xchg_count(x, pend_k, pend_e % ra.G);
+    if (lane == 0 && pend_e >= 0) xchg_count(x, pend_k, part_of(pend_e, ra.G));
     pack_row_from_obs(x.slab + ((size_t)(k % (uint32_t)x.ring) * (size_t)a.n + (size_t)e) * OBS_PACKED, a.obs + (size_t)e * OBS_TOTAL, lane);
     pend_e = e; pend_k = k;
     if (rollout) {
       // a rollout: the caller's next policy pass waits for this count -- not deferred to the wave's next item
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      if (lane == 0) xchg_count(x, k, (e % ra.P) * ra.PG + (e / ra.P) % ra.PG);
+      if (lane == 0) xchg_count(x, k, pgroup_slot(e, ra.P, ra.PG));
       pend_e = -1;
     }
   }
@@ -119,14 +107,14 @@ __device__ __forceinline__ void persist_loop(StepArgs a, RunArgs ra, const XchgA
   auto tl_flush = [&]() { if (ra.timeline && lane == 0) { unsigned long long* t = ra.timeline + 4 * (size_t)blockIdx.x; t[0] = tl_entry; t[1] = tl_first; t[2] = tl_last; t[3] = tl_items | ((unsigned long long)(my_slot + 1) << 32); } };
   int pend_e = -1; uint32_t pend_k = 0;  // the exchange: the item whose packed row this wave stored last and has not counted yet (its store drains with the next item)
   auto flush_pending = [&]() {
-    if (XCHG && x.slab && pend_e >= 0) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); if (lane == 0) xchg_count(x, pend_k, pend_e % ra.G); pend_e = -1; }
+    if (XCHG && x.slab && pend_e >= 0) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); if (lane == 0) xchg_count(x, pend_k, part_of(pend_e, ra.G)); pend_e = -1; }
   };
   const int my_xcc = my_slot >> 8;
   const int xlo = ra.xcc_lo[my_xcc], xn = ra.xcc_n[my_xcc];     // this XCD's partitions
   // the CU's own partition, from the table of the compute units this device showed at first use (-1: a CU that is not in it only helps out), and
   // its id in the progress words
   const int own = ra.slot_part[my_slot] - 1;
-  const uint32_t my_id = own >= 0 ? (uint32_t)own + 1u : 511u;
+  const uint32_t my_id = runner_of(own);
   const bool rollout = ROLLOUT && ra.act_ready;
   if (xn <= 0) { tl_flush(); return; }
 
@@ -136,14 +124,14 @@ __device__ __forceinline__ void persist_loop(StepArgs a, RunArgs ra, const XchgA
   auto claim = [&](int line, int idx, int pg, Item& it) -> int {
     int j, ee;
     if (!draw_ticket(ra, a.n, line, idx, pg, j, ee)) return 0;
-    int k, len; run_span(ra, j, k, len);
+    int k, len; run_span(ra.runs, j, k, len);
     bool ok;
     const uint32_t w = wait_progress(ra, x, ee, (uint32_t)k, rollout, ok);
     if (!ok) return -1;
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     if (XCHG && !rollout && x.slab) xchg_wait_slab(x, (uint32_t)k, seen_gathered);      // (a rollout has no `gathered` word: see xchg_wait_slab)
-    const uint32_t last = w >> 23;
-    it.e = ee; it.k = j; it.sh = (last != 0u && last != my_id) ? 1 : 0;     // the episode's last run was on another CU: its lines in this CU's L1 may be stale
+    const uint32_t last = progress_runner(w);
+    it.e = ee; it.k = j; it.sh = (last != RUNNER_NONE && last != my_id) ? 1 : 0;     // the episode's last run was on another CU: its lines in this CU's L1 may be stale
     return 1;
   };
   // A rollout (every step a run of its own: nph = K): every (partition, policy group) has a ticket counter of its own (words 0 .. PG-1 of the partition's
@@ -153,7 +141,7 @@ __device__ __forceinline__ void persist_loop(StepArgs a, RunArgs ra, const XchgA
   auto pick_rollout = [&]() -> Item {
     Item it{-4, 0, 0};
     if (own < 0 || lane != 0) return it;
-    const int ne = (a.n - own + ra.P - 1) / ra.P;
+    const int ne = part_episodes(a.n, ra.P, own);
     const uint32_t* rdy = ra.act_ready + (size_t)own * 32;
     const uint32_t* tkl = ra.ticket + (size_t)own * TK_STRIDE;
     int naps = 1;
@@ -161,12 +149,12 @@ __device__ __forceinline__ void persist_loop(StepArgs a, RunArgs ra, const XchgA
     for (;;) {
       int best_g = -1; uint32_t best_j = 0xFFFFFFFFu; bool left = false;
       for (int g = 0; g < ra.PG; ++g) {
-        const int ng = (ne - g + ra.PG - 1) / ra.PG;
+        const int ng = pgroup_episodes(ne, ra.PG, g);
         if (ng <= 0) continue;
         const uint32_t t = __hip_atomic_load(tkl + g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (t >= (uint32_t)(ng * ra.nph)) continue;
+        if (t >= ticket_total(ng, ra.runs.nph)) continue;
         left = true;
-        const uint32_t j = t / (uint32_t)ng;
+        const uint32_t j = ticket_run(t, ng);
         if (j < best_j && __hip_atomic_load(rdy + g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) > j) { best_j = j; best_g = g; }
       }
       if (!left) return it;                                         // every group of this partition is handed out: leave
@@ -183,7 +171,7 @@ __device__ __forceinline__ void persist_loop(StepArgs a, RunArgs ra, const XchgA
         raise_timeout(x);
         // give up on the policy: run what is left with whatever the slots hold (cc4_rollout_end reports it), behind an agent-scope acquire
         for (int g = 0; g < ra.PG; ++g) {
-          if ((ne - g + ra.PG - 1) / ra.PG <= 0) continue;
+          if (pgroup_episodes(ne, ra.PG, g) <= 0) continue;
           const int got = claim(own, g, ra.PG, it);
           if (got > 0) it.sh = 1;
           if (got != 0) return it;
@@ -199,7 +187,7 @@ __device__ __forceinline__ void persist_loop(StepArgs a, RunArgs ra, const XchgA
     uint32_t tk = 0xFFFFFFFFu, tot_q = 0;
     // (every partition's counter on a cache line of its own, TK_STRIDE words apart: 24 waves of one CU on a line, not the 768 of an XCD -- with the
     // XCD's 32 counters on ONE line, its atomics and these loads took the L2 ~50 ns each and the schedule ran at 556 M instead of 884 M)
-    if (lane < xn) { tk = __hip_atomic_load(&ra.ticket[q * TK_STRIDE], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); tot_q = (uint32_t)(((a.n - q + ra.P - 1) / ra.P) * ra.nph); }
+    if (lane < xn) { tk = __hip_atomic_load(&ra.ticket[q * TK_STRIDE], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); tot_q = ticket_total(part_episodes(a.n, ra.P, q), ra.runs.nph); }
     const bool has = lane < xn && tk < tot_q;
     uint32_t key = has ? ((tk << 6) | (uint32_t)lane) : 0xFFFFFFFFu;          // least tickets handed out = lags most (the partitions' sizes differ by one episode at most)
 #pragma unroll
@@ -223,7 +211,7 @@ __device__ __forceinline__ void persist_loop(StepArgs a, RunArgs ra, const XchgA
     if (e == -4) { flush_pending(); tl_flush(); return; }
     if (e == -5) continue;
     int run_k0, run_len;
-    run_span(ra, __builtin_amdgcn_readfirstlane(it.k), run_k0, run_len);
+    run_span(ra.runs, __builtin_amdgcn_readfirstlane(it.k), run_k0, run_len);
     if (ra.timeline && !tl_items) tl_first = wall_clock64();
     // ---- acquire, if the episode's last run was on another CU
     if (__builtin_amdgcn_readfirstlane(it.sh)) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");      // (buffer_inv sc1: the CU's L1 dropped.  buffer_inv sc0 does NOT drop it: profiles/r06_l1_inv_scope.txt)
@@ -284,7 +272,7 @@ __device__ __forceinline__ void persist_loop(StepArgs a, RunArgs ra, const XchgA
       if (lane == 0 && err_acc) (void)__hip_atomic_fetch_or(pl.err_or + e, err_acc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     // ---- publish progress
-    if (lane == 0) __hip_atomic_store(&ra.progress[e], (ra.base + item_k + 1u) | (my_id << 23), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (lane == 0) __hip_atomic_store(&ra.progress[e], progress_pack(ra.base + item_k + 1u, my_id), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (ra.timeline) { tl_last = wall_clock64(); ++tl_items; }
   }
 }

@@ -21,6 +21,7 @@
 #endif
 #include "../cage_challenge_4_amd/csrc/cc4_engine.h"
 #include "../cage_challenge_4_amd/csrc/cc4_export.h"
+#include "../cage_challenge_4_amd/csrc/cc4_sched.h"
 
 using namespace cc4;
 
@@ -265,6 +266,61 @@ uint32_t cc4o_blue_slot_shape(int b, int idx) { return blue_slot_shape(b, idx); 
 uint32_t cc4o_obs_fast_entry(int v) { return obs_fast_entry(v); }
 uint32_t cc4o_monitor_roll4(uint32_t ev4, int w) { return monitor_roll4(ev4, monitor_watch_mask(w)); }
 uint32_t cc4o_monitor_roll(int h, uint32_t ev) { return monitor_roll(h, (uint8_t)ev); }
+
+// ---- the index arithmetic of the persistent schedule (csrc/cc4_sched.h) as the kernels, the gates and the host compile it -- thin wrappers, in bulk so
+// that a test makes one call per shape (tests/test_sched_cpu.py)
+void cc4o_sched_limits(uint32_t* out /* [7] */) {
+  out[0] = (uint32_t)PROGRESS_STEP_BITS; out[1] = PG_STEPS; out[2] = RUNNER_NONE; out[3] = RUNNER_FOREIGN; out[4] = (uint32_t)MAX_PARTITIONS;
+  out[5] = PROGRESS_CLEAR_AT; out[6] = (uint32_t)ROLLOUT_MAX_K;
+}
+// per episode: its partition, its policy group, the (partition, group) counter that counts it
+void cc4o_sched_episode_maps(int n, int P, int PG, int32_t* part, int32_t* pgroup, int32_t* slot) {
+  for (int e = 0; e < n; ++e) { part[e] = part_of(e, P); pgroup[e] = pgroup_of(e, P, PG); slot[e] = pgroup_slot(e, P, PG); }
+}
+// what the gates wait for: the episodes of every partition [P] and of every (partition, policy group) [P][PG]
+void cc4o_sched_counts(int n, int P, int PG, int32_t* part_eps, int32_t* pgroup_eps) {
+  for (int p = 0; p < P; ++p) {
+    part_eps[p] = part_episodes(n, P, p);
+    for (int g = 0; g < PG; ++g) pgroup_eps[p * PG + g] = pgroup_episodes(part_eps[p], PG, g);
+  }
+}
+// the threads of a policy kernel over group g: out[i] = the episode of thread i (the kernel drops those >= n); returns their number, -1: more than cap
+int cc4o_sched_pgroup_enum(int n, int P, int PG, int g, int32_t* out, int cap) {
+  const int threads = pgroup_threads(n, P, PG);
+  if (threads > cap) return -1;
+  for (int i = 0; i < threads; ++i) out[i] = pgroup_episode(i, P, PG, g);
+  return threads;
+}
+// the exchange's groups of 32: group32[e] per episode, sizes[g] for the `alloc` counter rows the handle allocates (cap of them at most); returns the groups
+int cc4o_sched_xchg32(int n, int32_t* group32, int32_t* sizes, int* alloc, int cap) {
+  for (int e = 0; e < n; ++e) group32[e] = xchg_group32(e);
+  *alloc = xchg_groups32_alloc(n);
+  for (int g = 0; g < *alloc && g < cap; ++g) sizes[g] = xchg_group32_size(n, g);
+  return xchg_groups32(n);
+}
+// every ticket of every counter (partition `line`, word idx of its ticket line; PG = 1: the one counter of the balanced schedule), counter by counter in
+// the order the counter hands them out: the run and the episode it names.  totals[line * PG + idx]; returns the tickets written (stops at cap).
+int cc4o_sched_tickets(int n, int P, int PG, int nph, uint32_t* totals, int32_t* line, int32_t* idx, int32_t* j, int32_t* e, int cap) {
+  int m = 0;
+  for (int p = 0; p < P; ++p)
+    for (int g = 0; g < PG; ++g) {
+      const uint32_t cnt = ticket_count(n, P, p, g, PG), total = ticket_total(cnt, nph);
+      totals[p * PG + g] = total;
+      for (uint32_t t = 0; t < total && m < cap; ++t, ++m) { line[m] = p; idx[m] = g; ticket_item(t, cnt, p, g, PG, P, j[m], e[m]); }
+    }
+  return m;
+}
+// the runs of a k-step call under CC4_PERSIST_RUNS = "SA,SB,nB,single" (0,1,0,0: unset): split[5] = SA, nA, SB, nB, nph; first step and length of
+// runs j0 .. j0 + count - 1; returns nph
+int cc4o_sched_runs(int k, int cfgSA, int cfgSB, int cfgnB, int cfgsingle, int j0, int count, int32_t* split, int32_t* k0, int32_t* len) {
+  const RunSplit s = run_split(k, cfgSA, cfgSB, cfgnB, cfgsingle);
+  split[0] = s.SA; split[1] = s.nA; split[2] = s.SB; split[3] = s.nB; split[4] = s.nph;
+  for (int i = 0; i < count && j0 + i < s.nph; ++i) run_span(s, j0 + i, k0[i], len[i]);
+  return s.nph;
+}
+void cc4o_sched_progress(const uint32_t* steps, const uint32_t* runner, int m, uint32_t* w, uint32_t* steps_back, uint32_t* runner_back) {
+  for (int i = 0; i < m; ++i) { w[i] = progress_pack(steps[i], runner[i]); steps_back[i] = progress_steps(w[i]); runner_back[i] = progress_runner(w[i]); }
+}
 
 // "name offset" lines for EnvState members (maps a differing byte offset back to a field when bisecting)
 int cc4o_layout(char* buf, int cap) {

@@ -76,6 +76,20 @@ def load():
     lib.cc4o_dump.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]
     lib.cc4o_true_state.restype = ctypes.c_longlong
     lib.cc4o_true_state.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t]
+    # the persistent schedule's index arithmetic (csrc/cc4_sched.h), in bulk
+    i32, u32 = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint32)
+    lib.cc4o_sched_limits.argtypes = [u32]
+    lib.cc4o_sched_limits.restype = None
+    lib.cc4o_sched_episode_maps.argtypes = [ctypes.c_int] * 3 + [i32] * 3
+    lib.cc4o_sched_episode_maps.restype = None
+    lib.cc4o_sched_counts.argtypes = [ctypes.c_int] * 3 + [i32] * 2
+    lib.cc4o_sched_counts.restype = None
+    lib.cc4o_sched_pgroup_enum.argtypes = [ctypes.c_int] * 4 + [i32, ctypes.c_int]
+    lib.cc4o_sched_xchg32.argtypes = [ctypes.c_int, i32, i32, ctypes.POINTER(ctypes.c_int), ctypes.c_int]
+    lib.cc4o_sched_tickets.argtypes = [ctypes.c_int] * 4 + [u32] + [i32] * 4 + [ctypes.c_int]
+    lib.cc4o_sched_runs.argtypes = [ctypes.c_int] * 7 + [i32] * 3
+    lib.cc4o_sched_progress.argtypes = [u32, u32, ctypes.c_int, u32, u32, u32]
+    lib.cc4o_sched_progress.restype = None
     _LIB = lib
     return lib
 
