@@ -601,19 +601,32 @@ int cc4_run_plan_device(cc4_handle* h, int32_t k, const int32_t* d_actions, cons
   if (rc) { release(); h->err = "CC4_PERSIST_VERIFY: the shadow run failed: " + sh->err; return rc; }
   std::string bad;
   if (shadow_compare(h, bad)) { release(); return -1; }
-  // the trajectory, a step's row at a time (both streams are drained: shadow_compare waited for them)
+  // the trajectory, a step's row at a time (both streams are drained: shadow_compare waited for them) -- whether or not the final digests differ: the
+  // first step at which the recorded rows part is what places a disagreement in the call's runs, the digest's episode alone does not
   std::vector<uint8_t> ra, rb;
-  auto rows_differ = [&](const void* p, const void* q, size_t row_bytes, int32_t j) {
+  size_t differing = 0, first_e = 0;       // of the row that differs: how many episodes, and the first of them (0 episodes: the row could not be fetched)
+  auto rows_differ = [&](const void* p, const void* q, size_t per_episode, int32_t j) {
+    const size_t row_bytes = n * per_episode;
     ra.resize(row_bytes); rb.resize(row_bytes);
+    differing = 0; first_e = 0;
     if (hipMemcpy(ra.data(), static_cast<const uint8_t*>(p) + (size_t)j * row_bytes, row_bytes, hipMemcpyDeviceToHost) != hipSuccess ||
         hipMemcpy(rb.data(), static_cast<const uint8_t*>(q) + (size_t)j * row_bytes, row_bytes, hipMemcpyDeviceToHost) != hipSuccess) return true;
-    return memcmp(ra.data(), rb.data(), row_bytes) != 0;
+    if (memcmp(ra.data(), rb.data(), row_bytes) == 0) return false;
+    for (size_t e = 0; e < n; ++e)
+      if (memcmp(ra.data() + e * per_episode, rb.data() + e * per_episode, per_episode) != 0) { if (!differing) first_e = e; ++differing; }
+    return true;
   };
-  for (int32_t j = 0; j < k && bad.empty(); ++j) {
-    if (d_rewards && rows_differ(d_rewards, s_rew, n * sizeof(float), j)) bad = "rewards of step " + std::to_string(j);
-    else if (d_dones && rows_differ(d_dones, s_done, n, j)) bad = "dones of step " + std::to_string(j);
-    else if (d_obs_packed && rows_differ(d_obs_packed, s_packed, n * OBS_PACKED, j)) bad = "packed observations of step " + std::to_string(j);
+  std::string traj;
+  for (int32_t j = 0; j < k && traj.empty(); ++j) {
+    if (d_rewards && rows_differ(d_rewards, s_rew, sizeof(float), j)) traj = "rewards of step " + std::to_string(j);
+    else if (d_dones && rows_differ(d_dones, s_done, 1, j)) traj = "dones of step " + std::to_string(j);
+    else if (d_obs_packed && rows_differ(d_obs_packed, s_packed, OBS_PACKED, j)) traj = "packed observations of step " + std::to_string(j);
   }
+  if (!traj.empty()) {
+    traj = "first differing trajectory row: " + traj + (differing ? ", " + std::to_string(differing) + " episode(s) differ in it, first episode " + std::to_string(first_e)
+                                                                    : std::string(" (the row could not be fetched)"));
+    bad = bad.empty() ? traj : bad + "; " + traj;
+  } else if (!bad.empty()) bad += "; no recorded trajectory row differs";
   release();
   if (!bad.empty()) return verify_mismatch(h, std::string(cc4_plan_kernel_for(h, k)) + " and the per-step launches disagree after a plan of " + std::to_string(k) + " steps: " + bad);
   return 0;
