@@ -531,6 +531,20 @@ CC4_HD void rs_reserve(Ctx x) {
     x.w->rs_slot[r] = (uint8_t)slot;
   }
 }
+// rs_reserve's slot for agent r alone, from the set of agents whose action is an Exploit (bit r: agent r): the agents take the lowest free records
+// in agent order, so agent r's is the k-th free one, k = the number of exploiting agents below it; 0xFF for an agent without an Exploit or
+// when the pool has no k-th free record.  Reads spool_used as the serial form finds it (after the step's phishing).
+CC4_HD int rs_reserve_lane(const EnvState* s, uint32_t exploit_mask, int r) {
+  if (!((exploit_mask >> r) & 1u)) return 0xFF;
+  int k = popc32(exploit_mask & ((1u << r) - 1u));
+  int slot = 0xFF;
+  CC4_UNROLL for (int w = 0; w < RS_POOL / 32; ++w) {
+    const uint32_t fr = ~s->spool_used[w];
+    const int c = popc32(fr);
+    if (slot == 0xFF) { if (k < c) slot = w * 32 + nth_bit(fr, k); else k -= c; }
+  }
+  return slot;
+}
 // State.add_session (Simulator/State.py:305-324): ident = max(existing)+1 (0 if none); appended (dict order).
 // slot: the pool record to use (< 0: lowest free).  Returns the list index, or -1.
 CC4_HD int rs_add(Ctx x, int r, int host, int pid, int flags, int slot = -1) {
@@ -2164,6 +2178,54 @@ CC4_HD int fsm_choose_host_discovery(Ctx x, int r, RedHdr& H) {
   }
   return A.fsm_order[0];
 }
+// fsm_get_action's options in red_actions list order (ESG.py:764-768) with state_transitions_probability (:540-549).  All probabilities
+// are multiples of 1/4, so cdf.searchsorted(u, 'right') == #{i : 4*cdf[i] <= floor(4u)}.  Packed per state:
+// low 16 bits = option nibbles, high 16 bits = 4*cdf nibbles (unused slots = 15)
+CC4_HD constexpr uint32_t fsm_pk_switch(bool discovery, int host_state) {
+  if (!discovery) switch (host_state) {
+    case FS_K:  return 0xF432u << 16 | (RA_DRS | RA_AGGR << 4 | RA_STEALTH << 8);                          // .5 .25 .25
+    case FS_KD: return 0xFF42u << 16 | (RA_AGGR | RA_STEALTH << 4);                                         // .5 .5
+    case FS_S:  return 0xF431u << 16 | (RA_DRS | RA_EXPLOIT << 4 | RA_DECEPTION << 8);                     // .25 .5 .25
+    case FS_SD: return 0xFF43u << 16 | (RA_EXPLOIT | RA_DECEPTION << 4);                                    // .75 .25
+    case FS_U:  return 0xF442u << 16 | (RA_DRS | RA_PRIVESC << 4 | RA_WITHDRAW << 8);                      // .5 .5 0
+    case FS_UD: return 0xFF44u << 16 | (RA_PRIVESC | RA_WITHDRAW << 4);                                     // 1 0
+    case FS_R:  return 0x4432u << 16 | (RA_DRS | RA_DEGRADE << 4 | RA_IMPACT << 8 | RA_WITHDRAW << 12);    // .5 .25 .25 0
+    default:    return 0xF442u << 16 | (RA_DEGRADE | RA_IMPACT << 4 | RA_WITHDRAW << 8);                   // RD: .5 .5 0
+  } else switch (host_state) {  // DiscoveryFSRed.state_transitions_probability (FSMRedVariants.py:111-122)
+    case FS_K:  return 0xF441u << 16 | (RA_DRS | RA_AGGR << 4 | RA_STEALTH << 8);                          // .25 .75 0
+    case FS_KD: return 0xFF44u << 16 | (RA_AGGR | RA_STEALTH << 4);                                         // 1 0
+    case FS_S:  return 0xF441u << 16 | (RA_DRS | RA_EXPLOIT << 4 | RA_DECEPTION << 8);                     // .25 .75 0
+    case FS_SD: return 0xFF44u << 16 | (RA_EXPLOIT | RA_DECEPTION << 4);                                    // 1 0
+    case FS_U:  return 0xF440u << 16 | (RA_DRS | RA_PRIVESC << 4 | RA_WITHDRAW << 8);                      // 0 1 0
+    case FS_UD: return 0xFF44u << 16 | (RA_PRIVESC | RA_WITHDRAW << 4);                                     // 1 0
+    case FS_R:  return 0x4444u << 16 | (RA_DRS | RA_DEGRADE << 4 | RA_IMPACT << 8 | RA_WITHDRAW << 12);    // 1 0 0 0
+    default:    return 0xF442u << 16 | (RA_DEGRADE | RA_IMPACT << 4 | RA_WITHDRAW << 8);                   // RD: .5 .5 0
+  }
+}
+// ... and as sixteen words, entry discovery * 8 + min(host_state, 7) (every state above FS_R takes the switch's default): the host's state
+// differs from lane to lane, and the two switches become a tree of exec-mask branches that six agents in different states walk most of
+struct FsmPkTab { uint32_t v[16]; };
+CC4_HD constexpr int fsm_pk_index(bool discovery, int host_state) { return (discovery ? 8 : 0) + (host_state < 7 ? host_state : 7); }
+constexpr FsmPkTab make_fsm_pk_tab() {
+  FsmPkTab t{};
+  for (int d = 0; d < 2; ++d) for (int st = 0; st < 8; ++st) t.v[fsm_pk_index(d != 0, st)] = fsm_pk_switch(d != 0, st);
+  return t;
+}
+constexpr bool fsm_pk_tab_matches() {
+  const FsmPkTab t = make_fsm_pk_tab();
+  for (int d = 0; d < 2; ++d) {
+    for (int st = 0; st <= FS_F; ++st) if (t.v[fsm_pk_index(d != 0, st)] != fsm_pk_switch(d != 0, st)) return false;
+    if (t.v[fsm_pk_index(d != 0, FS_NONE)] != fsm_pk_switch(d != 0, FS_NONE)) return false;
+  }
+  return true;
+}
+static_assert(fsm_pk_tab_matches(), "fsm_get_action's option table == its switch");
+#if defined(__HIP_DEVICE_COMPILE__)
+static __device__ const FsmPkTab fsm_pk_tab = make_fsm_pk_tab();     // constant memory on the device
+#else
+static constexpr FsmPkTab fsm_pk_tab = make_fsm_pk_tab();
+#endif
+CC4_HD uint32_t fsm_pk(bool discovery, int host_state) { return fsm_pk_tab.v[fsm_pk_index(discovery, host_state)]; }
 // get_action (:58-122) incl. _choose_host (:252-293) and _choose_host_and_action (:296-336)
 // observed: fsm_observe (which draws nothing) has already run for this step (step_red_observe)
 CC4_HD Act fsm_get_action(Ctx x, int r, RedHdr& H, bool observed = false) {
@@ -2180,31 +2242,8 @@ CC4_HD Act fsm_get_action(Ctx x, int r, RedHdr& H, bool observed = false) {
   int host;
   if (!discovery) host = A.fsm_order[rng_below(x.r, (uint32_t)n)];
   else host = fsm_choose_host_discovery(x, r, H);
-  // options in red_actions list order (ESG.py:764-768) with state_transitions_probability (:540-549).  All probabilities
-  // are multiples of 1/4, so cdf.searchsorted(u, 'right') == #{i : 4*cdf[i] <= floor(4u)}.  Packed per state:
-  // low 16 bits = option nibbles, high 16 bits = 4*cdf nibbles (unused slots = 15)
   CC4_FT(x, r, 6);
-  uint32_t pk;
-  const int host_state = fsm_get(A, host);
-  if (!discovery) switch (host_state) {
-    case FS_K:  pk = 0xF432u << 16 | (RA_DRS | RA_AGGR << 4 | RA_STEALTH << 8); break;                          // .5 .25 .25
-    case FS_KD: pk = 0xFF42u << 16 | (RA_AGGR | RA_STEALTH << 4); break;                                         // .5 .5
-    case FS_S:  pk = 0xF431u << 16 | (RA_DRS | RA_EXPLOIT << 4 | RA_DECEPTION << 8); break;                     // .25 .5 .25
-    case FS_SD: pk = 0xFF43u << 16 | (RA_EXPLOIT | RA_DECEPTION << 4); break;                                    // .75 .25
-    case FS_U:  pk = 0xF442u << 16 | (RA_DRS | RA_PRIVESC << 4 | RA_WITHDRAW << 8); break;                      // .5 .5 0
-    case FS_UD: pk = 0xFF44u << 16 | (RA_PRIVESC | RA_WITHDRAW << 4); break;                                     // 1 0
-    case FS_R:  pk = 0x4432u << 16 | (RA_DRS | RA_DEGRADE << 4 | RA_IMPACT << 8 | RA_WITHDRAW << 12); break;    // .5 .25 .25 0
-    default:    pk = 0xF442u << 16 | (RA_DEGRADE | RA_IMPACT << 4 | RA_WITHDRAW << 8); break;                   // RD: .5 .5 0
-  } else switch (host_state) {  // DiscoveryFSRed.state_transitions_probability (FSMRedVariants.py:111-122)
-    case FS_K:  pk = 0xF441u << 16 | (RA_DRS | RA_AGGR << 4 | RA_STEALTH << 8); break;                          // .25 .75 0
-    case FS_KD: pk = 0xFF44u << 16 | (RA_AGGR | RA_STEALTH << 4); break;                                         // 1 0
-    case FS_S:  pk = 0xF441u << 16 | (RA_DRS | RA_EXPLOIT << 4 | RA_DECEPTION << 8); break;                     // .25 .75 0
-    case FS_SD: pk = 0xFF44u << 16 | (RA_EXPLOIT | RA_DECEPTION << 4); break;                                    // 1 0
-    case FS_U:  pk = 0xF440u << 16 | (RA_DRS | RA_PRIVESC << 4 | RA_WITHDRAW << 8); break;                      // 0 1 0
-    case FS_UD: pk = 0xFF44u << 16 | (RA_PRIVESC | RA_WITHDRAW << 4); break;                                     // 1 0
-    case FS_R:  pk = 0x4444u << 16 | (RA_DRS | RA_DEGRADE << 4 | RA_IMPACT << 8 | RA_WITHDRAW << 12); break;    // 1 0 0 0
-    default:    pk = 0xF442u << 16 | (RA_DEGRADE | RA_IMPACT << 4 | RA_WITHDRAW << 8); break;                   // RD: .5 .5 0
-  }
+  const uint32_t pk = fsm_pk(discovery, fsm_get(A, host));
   const int fl = rng_random_quarter(x.r);   // floor(4 u)
   int k = 0;
   for (int i = 0; i < 4; ++i) if ((int)((pk >> (16 + 4 * i)) & 0xF) <= fl) k++;
@@ -2790,16 +2829,24 @@ CC4_HD void step_messages(EnvState* s, const uint8_t* messages, int b) {
   if (messages) for (int i = 0; i < MSG_LEN; ++i) w |= (uint64_t)(messages[b * MSG_LEN + i] ? 1 : 0) << (8 * i);
   __builtin_memcpy(&s->msg[b][0], &w, 8);       // (no messages, the usual case of a vectorised batch: one store instead of eight byte stores)
 }
-CC4_HD void step_end(Ctx x, const uint8_t* messages, bool copy_msgs = true) {
+// step_end's Impact term of agent r alone (the one-wave kernel: agent r's lane adds it to EnvState.brm ahead of step_end, which then skips its loop)
+CC4_HD int step_impact_term(const EnvState* s, int r) {
+  const RedHdr& h = s->red[r].h;
+  return (h.exec_type == RA_IMPACT && h.nsess > 0) ? reward_table(s->phase, h_subnet(h.exec_host), RW_RIA) : 0;
+}
+// impact: add the six agents' Impact terms here (false: the caller has added them to brm already, step_impact_term)
+CC4_HD void step_end(Ctx x, const uint8_t* messages, bool copy_msgs = true, bool impact = true) {
   EnvState* s = x.s;
   s->step_count++;
   s->done = (uint8_t)(s->step_count >= s->steps - 1);
   int brm = s->brm;
-  int et[NRED], ns[NRED];
-  CC4_UNROLL for (int r = 0; r < NRED; ++r) { et[r] = s->red[r].h.exec_type; ns[r] = s->red[r].h.nsess; }
-  CC4_UNROLL for (int r = 0; r < NRED; ++r)
-    if (et[r] == RA_IMPACT && ns[r] > 0)
-      brm += reward_table(s->phase, h_subnet(s->red[r].h.exec_host), RW_RIA);  // charged for any executed Impact (App. B.2)
+  if (impact) {
+    int et[NRED], ns[NRED];
+    CC4_UNROLL for (int r = 0; r < NRED; ++r) { et[r] = s->red[r].h.exec_type; ns[r] = s->red[r].h.nsess; }
+    CC4_UNROLL for (int r = 0; r < NRED; ++r)
+      if (et[r] == RA_IMPACT && ns[r] > 0)
+        brm += reward_table(s->phase, h_subnet(s->red[r].h.exec_host), RW_RIA);  // charged for any executed Impact (App. B.2)
+  }
   s->action_cost = -(float)s->n_restore;
   s->reward = (float)brm + s->action_cost;
   if (x.ext) for (int g = 0; g < s->n_green; ++g) if (x.w->green_act[g] == 3) bit_set_shared(x.c->gfail, g);   // submitted green actions that were invalid

@@ -204,7 +204,17 @@ __device__ __forceinline__ void philox1_body(StepArgs a, const int e, const uint
       CC4_TICK(x0, 6);
       CC4_STOP(7);                                                               // + green actions
       // ---- P5 deferred phishing (ordered), then P6 red actions: side by side when they name distinct hosts
-      if (lane == 0) { step_phishing(x0); CC4_TICK(x0, 1); rs_reserve(x0); }
+      // On most steps neither has anything to do (0.17 phishing requests a step; an Exploit resolves once in four ticks), so the wave asks first:
+      // the requests by ballot of phish_mask's three words, the Exploits by ballot of the agents' own actions.  Phishing keeps its order (lane 0,
+      // ahead of the reservation: a spawned session takes the lowest free record); the reservation is rs_reserve's, each agent's slot found on its
+      // own lane (rs_reserve_lane).  rs_slot is written on every step -- 0xFF without an Exploit -- not left as the work area's clear has it.
+      {
+        const bool phish = __ballot(lane < 3 && work.phish_mask[lane] != 0) != 0ull;
+        const uint32_t exploit = (uint32_t)__ballot(is_red && s->rexec[lane].type == RA_EXPLOIT);
+        if (phish) { if (lane == 0) step_phishing(x0); __syncthreads(); }
+        if (lane == 0) CC4_TICK(x0, 1);
+        if (is_red) work.rs_slot[lane] = (uint8_t)(exploit ? rs_reserve_lane(s, exploit, lane) : 0xFF);
+      }
       __syncthreads();
       const uint32_t serial_red = red_conflict_wave(s, lane);                     // one pair of agents per lane, a ballot (was 15 pairs on lane 0)
       if (lane == 0 && prof && serial_red) prof[4] += 1000000;
@@ -245,15 +255,22 @@ __device__ __forceinline__ void philox1_body(StepArgs a, const int e, const uint
         }
       }
       CC4_STOP(9);                                                               // + red actions
-      if (lane == 0) { step_red_merge(x0); CC4_TICK(x0, 7); }
+      // the agents' pid-carrying events: each lane looks at its own slot, and lane 0 merges only when there is one (step_red_merge)
+      if (__ballot(is_red && work.pend_r[lane] != 0)) { if (lane == 0) step_red_merge(x0); }
+      if (lane == 0) CC4_TICK(x0, 7);
       __syncthreads();
       {
         // sessions outside their agent's zone: asked by the whole wave of the merged lists (red_foreign_wave) instead of 30 words on lane 0;
         // nearly always there are none, and the agents' lanes refresh their `active` flags (== step_reassign)
         const uint32_t foreign = red_foreign_wave(s, lane);
-        if (foreign) { if (lane == 0) red_reassign(x0, foreign); }
+        if (foreign) { if (lane == 0) red_reassign(x0, foreign); __syncthreads(); }   // (moves sessions between agents: the lanes below read nsess)
         else if (is_red) red_active_from_sessions(s, lane);
         if (lane == 0) CC4_TICK(x0, 8);
+        // step_end's Impact term, each agent's on its own lane (rare: an LDS atomic).  It reads the agent's exec_type, exec_host and nsess: the red
+        // actions and the reassignment above are the last to change them -- monitor_roll_all touches event bytes only, and step_rsc /
+        // red_session_check below reorders and promotes sessions but never adds or drops one (a change there that does must move this behind
+        // it).  The barrier behind the Monitor roll-over puts the sum in front of lane 63's step_end
+        if (is_red) { const int term = step_impact_term(s, lane); if (term) atomicAdd(&s->brm, term); }
       }
       // P7 end-turn Monitor roll-over: the hosts' event bytes are part of the staged row (EnvState.hev).  (Lane 0's reassignment above
       // moves sessions, not events.)
@@ -266,7 +283,7 @@ __device__ __forceinline__ void philox1_body(StepArgs a, const int e, const uint
       if (is_red) { unsigned long long t0 = ap ? clock64() : 0; step_rsc(xr, lane); if (ap) ap[2] += clock64() - t0; }
       if (lane == WAVE - 1) {
         step_monitor_pend(xg);
-        step_end(xg, nullptr, false);
+        step_end(xg, nullptr, false, false);
         a.reward[e] = s->reward; a.done[e] = s->done;
       }
       CC4_TICK(x0, 10);

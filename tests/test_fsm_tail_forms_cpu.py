@@ -1,0 +1,37 @@
+"""CPU: the table form of the red FSM's option switch (csrc/cc4_engine.h: fsm_pk / fsm_pk_switch) and the per-lane forms
+of the step's single-lane sections (rs_reserve_lane against rs_reserve, the pend_r ballot against step_red_merge, step_impact_term + step_end without
+its loop against step_end).  tests/cpp/fsm_tail_forms_check.cpp is a stand-alone program with its own main: built here with the host compiler at -O1
+with the address and undefined-behaviour sanitizers and run as a child process (never loaded into Python).  Exhaustive on the table (every state
+0..255, both policies); the reservation over all 64 Exploit sets x pools whose next free records straddle every
+word boundary, pools with 0..7 free records and random fills; the Impact sum over all phases x subnets x 64 sets.  Exit status 0: all agreed."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = os.path.join(ROOT, 'tests', 'cpp', 'fsm_tail_forms_check.cpp')
+
+
+def _compiler():
+    for cxx in (os.environ.get('CXX'), 'g++', 'c++', 'clang++'):
+        if cxx and shutil.which(cxx):
+            return shutil.which(cxx)
+    return None
+
+
+def test_fsm_tables_and_lane_forms_equal_their_serial_forms(tmp_path):
+    cxx = _compiler()
+    if cxx is None:
+        pytest.skip('no host C++ compiler found (CXX, g++, c++, clang++): the stand-alone check cannot be built')
+    exe = str(tmp_path / 'fsm_tail_forms_check')
+    flags = ['-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=undefined']
+    # the sanitizer runtimes inside the program itself (clang's default; gcc needs to be told), so that it depends on no shared runtime
+    if 'clang' not in subprocess.run([cxx, '--version'], capture_output=True, text=True).stdout:
+        flags += ['-static-libasan', '-static-libubsan']
+    cc = subprocess.run([cxx] + flags + ['-o', exe, SRC], capture_output=True, text=True)
+    assert cc.returncode == 0, cc.stdout + cc.stderr
+    run = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert run.returncode == 0, run.stdout + run.stderr
+    assert ' 0 mismatches' in run.stdout, run.stdout
