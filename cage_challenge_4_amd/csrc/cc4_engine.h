@@ -694,45 +694,23 @@ CC4_HD int route(int src, int dst, uint8_t* work) {
 }
 
 // ------------------------------------------------------------------ reset: EnterpriseScenarioGenerator + State.__init__
-// Draw order follows create_scenario (EnterpriseScenarioGenerator.py:123-169) then State.__init__ (State.py:66-148).
+// ONE generation, stated once as the phase functions below (reset_zero .. reset_finish), walked in two draw orders:
+//   numpy stream (RNG mode 0): one shared generator, so the order of the draws is the reference's own -- create_scenario
+//     (EnterpriseScenarioGenerator.py:123-169) then State.__init__ (State.py:66-148) -- and the walk is serial: env_reset_numpy_stream;
+//   counter mode (RNG mode 1): every host draws from its own streams, so the per-host phases run side by side: env_reset_counter_mode (the
+//     oracle, as loops) and reset_counter_mode_block (cc4_kernels.h: one host per thread, a barrier behind each phase).
+// The modes differ in four places only: which generator a draw comes from; the numpy stream draws a host's services right behind that
+// host's address (reset_topology's per-host hook) where counter mode draws them in a phase of their own; _generate_pid re-draws at once
+// against the running set on the numpy stream (gen_pid) where counter mode settles the pids afterwards (reset_pid_serial); and the starting
+// sessions come in agent order on the numpy stream (reset_sessions_agent_order) and per host in counter mode (reset_host_sessions).
+// The scenario is generated into the dynamic host rows (EnvState.hd: LDS on the device), and the backup images
+// (Host.create_backup -> EnvCold.hs, HBM) are written from them once, with stores only: generating into the cold row
+// made every read-modify-write of the build a global-memory round trip.
 CC4_HD int gen_pid(Ctx x, uint32_t* used) {  // _generate_pid (ESG.py:564-578)
   while (true) {
     int pid = rng_range(x.r, 1000, 10000);
     if (!bit_get(used, pid - 1000)) { bit_set(used, pid - 1000); return pid; }
   }
-}
-// The scenario is generated into the dynamic host rows (EnvState.hd: LDS on the device), and the backup images
-// (Host.create_backup -> EnvCold.hs, HBM) are written from them once, with stores only: generating into the cold row
-// made every read-modify-write of the build a global-memory round trip.
-CC4_HD void gen_host(Ctx x, int h, uint32_t* used) {  // _generate_linux_host (ESG.py:470-528)
-  EnvState* s = x.s;
-  HostDyn& st = x.hd[h];
-  st.nproc = 0; st.nsf = 0;
-  bit_set(s->exists, h);
-  st.gtmp = (uint8_t)rng_below(x.r, 2);  // OSDistribution choice (ESG.py:488-494): 0 UBUNTU, 1 KALI; parked in gtmp until the backup is written
-  if (h_is_router(h)) return;
-  // _generate_linux_host_services (ESG.py:530-562); services dict order = SSHD, [OTSERVICE], chosen add-ons
-  int n = 0;
-  auto put = [&](int kind, int pid) {
-    st.svcs[n].kind = (uint8_t)kind; st.svcs[n].pid = (uint16_t)pid; st.svcs[n].st = (uint8_t)(SV_ACTIVE | 5);
-    st.procs[n].kind = (uint8_t)kind; st.procs[n].pid = (uint16_t)pid; st.procs[n].flags = 0;
-    n++;
-  };
-  put(K_SSHD, gen_pid(x, used));
-  int sub = h_subnet(h);
-  if (sub == S_OZA || sub == S_OZB) put(K_OT, gen_pid(x, used));
-  int p_apache = gen_pid(x, used), p_mysql = gen_pid(x, used), p_smtp = gen_pid(x, used);  // all three are always drawn
-  int n_add = (int)rng_below(x.r, 4);  // integers(0, 3, endpoint=True)
-  uint32_t left = 7;                    // remaining add-on options {APACHE2, MYSQLD, SMTP} as a bit list
-  for (int k = 0; k < n_add; ++k) {
-    int c = (int)rng_below(x.r, (uint32_t)popc32(left));
-    int o = nth_bit(left, c);
-    left &= ~(1u << o);
-    put(o == 0 ? K_APACHE : (o == 1 ? K_MYSQL : K_SMTP), o == 0 ? p_apache : (o == 1 ? p_mysql : p_smtp));
-  }
-  // _generate_linux_host_processes (ESG.py:580-629): one random() per service, never below 1.0
-  for (int i = 0; i < n; ++i) (void)rng_random(x.r);
-  hd_set_nsvc(st, n); st.nproc = (uint16_t)n;
 }
 // Host.add_session for a starting session (Host.py:189-196): Process(pid=create_pid(), name=session_type)
 CC4_HD int start_session_proc(Ctx x, int h, int kind) {   // at generation time a host holds fewer than PIN processes
@@ -768,13 +746,13 @@ CC4_HD void host_restore(Ctx x, int h) {  // Host.restore (Host.py:373-429)
   pend_drop_host(x, h);
 }
 
-// ------------------------------------------------------------------ counter-mode scenario generation, in phases
-// The numpy-stream mode above is serial by definition (one shared generator).  In the counter-based mode every host draws
+// ------------------------------------------------------------------ the scenario generation, in phases
+// The numpy stream is serial by definition (one shared generator).  In the counter-based mode every host draws
 // from its own streams (ST_GEN_HOST / ST_GEN_REDRAW / ST_GEN_SESS + host id), so the generation is cut into phases whose
 // per-host parts are independent: the device runs them one host per thread, env_reset runs the same phases as loops (the
 // oracle), and both leave identical bytes.  Same scenario distribution as _generate_* (ESG.py:171-817); pids are unique
 // network-wide as in _generate_pid: a pid drawn by several services stays with the first of them in host order, the
-// others draw again.
+// others draw again.  RNG_MODE (a template parameter where a phase differs between the modes): 0 numpy stream, 1 counter mode.
 struct ResetCarry { uint64_t env_key; };
 enum : int { RESET_WS_SEEN = 0, RESET_WS_DUP = 288, RESET_WS_HOSTS = 576, RESET_WS_WORDS = 584 };   // work area (LDS on the device)
 
@@ -793,19 +771,68 @@ CC4_HD void reset_zero(EnvState* s, HostDyn* hd, EnvCold* c, int t, int nt) {
 static_assert(sizeof(RSess) * RS_POOL >= 4 * 282, "the idle session pool holds the 9000-bit pid set of the generation");
 CC4_HD uint32_t* reset_used_set(EnvState* s) { return reinterpret_cast<uint32_t*>(s->spool); }
 CC4_HD void reset_used_clear(EnvState* s, int t, int nt) { uint32_t* u = reset_used_set(s); for (int i = t; i < 282; i += nt) u[i] = 0; }
-// phase 1, one thread: generator, mission phases, subnets, host counts and addresses (main reset stream)
-CC4_HD ResetCarry reset_topology(Ctx x, uint64_t seed, int steps, bool continue_stream, int policy, uint32_t topo_seed, uint32_t* ws,
-                                 bool rng_is_copy) {
+// per host: OS, services and their pids (_generate_linux_host, ESG.py:470-528).  Counter mode (phase 2): from the host's own stream, every pid a
+// plain draw whose uniqueness reset_pid_serial settles afterwards.  Numpy stream: called by reset_topology right behind the host's address,
+// every pid drawn against the running set (gen_pid), as the reference does.
+template <int RNG_MODE>
+CC4_HD void reset_gen_host(Ctx x, int h) {
   EnvState* s = x.s;
-  if (!continue_stream) rng_seed(&s->rng, seed, 1u);   // a fresh seed needs x.r == &s->rng (see env_reset)
-  s->rng_mode = 1;
-  s->policy = (uint8_t)policy;
-  rng_begin_episode(x.r);
-  ResetCarry k; k.env_key = x.r->s_lo;
-  if (topo_seed) x.r->s_lo = (uint64_t)topo_seed;
+  if (!bit_get(s->exists, h)) return;
+  if (RNG_MODE == 1) rng_set_stream(x.r, ST_GEN_HOST + (uint32_t)h);
+  HostDyn& st = x.hd[h];
+  st.gtmp = (uint8_t)rng_below(x.r, 2);   // OSDistribution choice (ESG.py:488-494): 0 UBUNTU, 1 KALI; parked in gtmp until the backup is written
+  if (h_is_router(h)) return;
+  // _generate_linux_host_services (ESG.py:530-562); services dict order = SSHD, [OTSERVICE], chosen add-ons
+  int n = 0;
+  auto put = [&](int kind, int pid) {
+    st.svcs[n].kind = (uint8_t)kind; st.svcs[n].pid = (uint16_t)pid; st.svcs[n].st = (uint8_t)(SV_ACTIVE | 5);
+    st.procs[n].kind = (uint8_t)kind; st.procs[n].pid = (uint16_t)pid; st.procs[n].flags = 0;
+    n++;
+  };
+  auto pid = [&]() { return RNG_MODE == 1 ? rng_range(x.r, 1000, 10000) : gen_pid(x, reset_used_set(s)); };
+  put(K_SSHD, pid());
+  int sub = h_subnet(h);
+  if (sub == S_OZA || sub == S_OZB) put(K_OT, pid());
+  int p_apache = pid(), p_mysql = pid(), p_smtp = pid();   // all three are always drawn
+  int n_add = (int)rng_below(x.r, 4);   // integers(0, 3, endpoint=True)
+  uint32_t left = 7;                     // remaining add-on options {APACHE2, MYSQLD, SMTP} as a bit list
+  for (int k = 0; k < n_add; ++k) {
+    int o = nth_bit(left, (int)rng_below(x.r, (uint32_t)popc32(left)));
+    left &= ~(1u << o);
+    put(o == 0 ? K_APACHE : (o == 1 ? K_MYSQL : K_SMTP), o == 0 ? p_apache : (o == 1 ? p_mysql : p_smtp));
+  }
+  // _generate_linux_host_processes (ESG.py:580-629): one random() per service, never below 1.0
+  for (int i = 0; i < n; ++i) (void)rng_random(x.r);
+  hd_set_nsvc(st, n); st.nproc = (uint16_t)n;
+  // counter mode: the three add-on candidates in draw order, installed or not, for the uniqueness pass (reset_pid_serial clears them again): a
+  // freshly generated host has at most five services and five processes, slots 5 and 6 are free
+  if (RNG_MODE == 1) { st.procs[5].pid = (uint16_t)p_apache; st.procs[6].pid = (uint16_t)p_mysql; st.svcs[6].pid = (uint16_t)p_smtp; }
+}
+// reset_topology's per-host hook, called right after a host's address is placed: nothing (counter mode: the hosts are a phase of their own), or
+// this host's draws now (numpy stream: the reference draws address, then host, from the one generator).  The hook runs while the subnet's free
+// addresses live in StepWork.scratch: it must not touch that area (reset_gen_host and gen_pid do not: they use the row and the lent pid set).
+struct ResetHostLater { CC4_HD void operator()(Ctx, int) const {} };
+struct ResetHostNow { CC4_HD void operator()(Ctx x, int h) const { reset_gen_host<0>(x, h); } };
+CC4_HD void reset_mission_phases(EnvState* s, int steps) {   // _generate_mission_phases (ESG.py:854-860)
+  int q = steps / 3, rem = steps % 3;
   s->steps = steps;
-  { int q = steps / 3, rem = steps % 3; s->phase_len[0] = q + (rem >= 1 ? 1 : 0); s->phase_len[1] = q + (rem == 2 ? 1 : 0); s->phase_len[2] = q; }
-  for (int i = 0; i < RESET_WS_WORDS; ++i) ws[i] = 0;
+  s->phase_len[0] = q + (rem >= 1 ? 1 : 0); s->phase_len[1] = q + (rem == 2 ? 1 : 0); s->phase_len[2] = q;
+}
+// phase 1, one thread: generator, mission phases, subnets, host counts and addresses (main reset stream).  ws: counter mode's work area.
+template <int RNG_MODE, typename HostHook>
+CC4_HD ResetCarry reset_topology(Ctx x, uint64_t seed, int steps, bool continue_stream, int policy, uint32_t topo_seed, uint32_t* ws,
+                                 bool rng_is_copy, HostHook host_placed) {
+  EnvState* s = x.s;
+  if (!continue_stream) rng_seed(&s->rng, seed, (uint32_t)RNG_MODE);   // a fresh seed needs x.r == &s->rng; a continued stream may be walked on a copy of it
+  s->rng_mode = (uint8_t)RNG_MODE;
+  s->policy = (uint8_t)policy;
+  rng_begin_episode(x.r);   // counter mode: the reset stream uses its own (step, episode) counter words
+  ResetCarry k; k.env_key = x.r->s_lo;
+  if (RNG_MODE == 1 && topo_seed) x.r->s_lo = (uint64_t)topo_seed;
+  reset_mission_phases(s, steps);
+  if (RNG_MODE == 1) for (int i = 0; i < RESET_WS_WORDS; ++i) ws[i] = 0;
+  // _generate_subnets (ESG.py:171-266): choice(len(remaining /24 blocks)) per subnet, pop.  The remaining list stays
+  // ascending, so "pop(c)" is the c-th set bit of a 256-bit availability map
   {
     uint32_t* avail = x.w->scratch;
     for (int i = 0; i < 8; ++i) avail[i] = 0xFFFFFFFFu;
@@ -817,53 +844,27 @@ CC4_HD ResetCarry reset_topology(Ctx x, uint64_t seed, int steps, bool continue_
       n--;
     }
   }
+  // _generate_hosts (ESG.py:312-371): ip_addresses = hosts .1 .. .254 of the /24, ascending (bit v set <=> 10.0.X.v still unassigned); the router and
+  // the users take choice(remaining), the servers ip_addresses.pop()
   for (int sn = 0; sn < NSUB; ++sn) {
     uint32_t* ips = x.w->scratch;
     for (int i = 0; i < 8; ++i) ips[i] = 0xFFFFFFFFu;
     ips[0] &= ~1u; ips[7] &= 0x7FFFFFFFu;
     int n = 254;
-    auto place = [&](int h, int v) { bit_clr(ips, v); n--; bit_set(s->exists, h); x.hd[h].procs[PIN - 1].pid = (uint16_t)v; };   // ip parked in the last inline process slot until the backup
+    auto place = [&](int h, int v) {   // ip parked in the last inline process slot until the backup
+      bit_clr(ips, v); n--; bit_set(s->exists, h); x.hd[h].procs[PIN - 1].pid = (uint16_t)v;
+      host_placed(x, h);
+    };
     if (sn == S_INT) { place(H_INTERNET, nth_set(ips, 8, (int)rng_below(x.r, (uint32_t)n))); continue; }
     place(h_make(sn, 0), nth_set(ips, 8, (int)rng_below(x.r, (uint32_t)n)));
-    int nu = 3 + (int)rng_below(x.r, 8);
+    int nu = 3 + (int)rng_below(x.r, 8);   // integers(3, 10, endpoint=True)
     for (int i = 0; i < nu; ++i) place(h_make(sn, 1 + i), nth_set(ips, 8, (int)rng_below(x.r, (uint32_t)n)));
-    int ns = 1 + (int)rng_below(x.r, 6);
+    int ns = 1 + (int)rng_below(x.r, 6);   // integers(1, 6, endpoint=True)
     for (int i = 0; i < ns; ++i) place(h_make(sn, 11 + i), last_set(ips, 8));
     s->n_users[sn] = (uint8_t)nu; s->n_servers[sn] = (uint8_t)ns;
   }
-  if (rng_is_copy) s->rng = *x.r;   // the per-host generators fork from the row (key, episode, reset step word)
+  if (RNG_MODE == 1 && rng_is_copy) s->rng = *x.r;   // the per-host generators fork from the row (key, episode, reset step word)
   return k;
-}
-// phase 2, per host: services and candidate pids (_generate_linux_host, ESG.py:470-629) from the host's own stream
-CC4_HD void reset_gen_host(Ctx x, int h) {
-  EnvState* s = x.s;
-  if (!bit_get(s->exists, h)) return;
-  rng_set_stream(x.r, ST_GEN_HOST + (uint32_t)h);
-  HostDyn& st = x.hd[h];
-  st.gtmp = (uint8_t)rng_below(x.r, 2);   // OSDistribution, parked in gtmp until the backup
-  if (h_is_router(h)) return;
-  int n = 0;
-  auto put = [&](int kind, int pid) {
-    st.svcs[n].kind = (uint8_t)kind; st.svcs[n].pid = (uint16_t)pid; st.svcs[n].st = (uint8_t)(SV_ACTIVE | 5);
-    st.procs[n].kind = (uint8_t)kind; st.procs[n].pid = (uint16_t)pid; st.procs[n].flags = 0;
-    n++;
-  };
-  put(K_SSHD, rng_range(x.r, 1000, 10000));
-  int sub = h_subnet(h);
-  if (sub == S_OZA || sub == S_OZB) put(K_OT, rng_range(x.r, 1000, 10000));
-  int p_apache = rng_range(x.r, 1000, 10000), p_mysql = rng_range(x.r, 1000, 10000), p_smtp = rng_range(x.r, 1000, 10000);
-  int n_add = (int)rng_below(x.r, 4);
-  uint32_t left = 7;
-  for (int k = 0; k < n_add; ++k) {
-    int o = nth_bit(left, (int)rng_below(x.r, (uint32_t)popc32(left)));
-    left &= ~(1u << o);
-    put(o == 0 ? K_APACHE : (o == 1 ? K_MYSQL : K_SMTP), o == 0 ? p_apache : (o == 1 ? p_mysql : p_smtp));
-  }
-  for (int i = 0; i < n; ++i) (void)rng_random(x.r);
-  hd_set_nsvc(st, n); st.nproc = (uint16_t)n;
-  // the three add-on candidates in draw order, installed or not, for the uniqueness pass (reset_pid_serial clears them again): a
-  // freshly generated host has at most five services and five processes, slots 5 and 6 are free
-  st.procs[5].pid = (uint16_t)p_apache; st.procs[6].pid = (uint16_t)p_mysql; st.svcs[6].pid = (uint16_t)p_smtp;
 }
 // phase 3, one thread: the network-wide pid uniqueness of _generate_pid (ESG.py:564-578), in the REFERENCE'S ORDER.  The reference
 // draws the pids host after host -- SSHD, [OT service], then the three add-on candidates apache / mysql / smtp, installed or not
@@ -913,12 +914,12 @@ CC4_HD void reset_pid_serial(Ctx x, uint32_t* used) {
 // phase 4, one thread: blue parents, green agents, red start hosts (_generate_blue/green/red_agents; main reset stream)
 CC4_HD void reset_agents(Ctx x) {
   EnvState* s = x.s;
-  for (int b = 0; b < NBLUE; ++b) {
+  for (int b = 0; b < NBLUE; ++b) {   // _generate_blue_agents (ESG.py:631-698)
     int nsub = blue_nsub(b);
-    (void)rng_below(x.r, (uint32_t)nsub);
+    (void)rng_below(x.r, (uint32_t)nsub);   // starting_subnet = choice(allowed_subnets): unused
     int cnt = 0;
     for (int i = 0; i < nsub; ++i) { int sn = blue_subnet_alloc(b, i); cnt += 1 + s->n_users[sn] + s->n_servers[sn]; }
-    int c = (int)rng_below(x.r, (uint32_t)cnt);
+    int c = (int)rng_below(x.r, (uint32_t)cnt);   // parent_host = choice(allowed_hosts)
     int ph = -1;
     for (int i = 0; i < nsub && ph < 0; ++i) {   // existing slots of a subnet: 0, 1..nu, 11..11+ns-1
       int sn = blue_subnet_alloc(b, i), nu = s->n_users[sn], ns = s->n_servers[sn];
@@ -928,19 +929,25 @@ CC4_HD void reset_agents(Ctx x) {
     }
     s->blue[b].parent_host = (uint8_t)ph;
   }
-  {
+  {   // _generate_green_agents (ESG.py:700-749): one per user host, host order
     int g = 0;
     for (int sn = 0; sn < NSUB - 1; ++sn) for (int i = 0; i < s->n_users[sn]; ++i) s->green_host[g++] = (uint8_t)h_make(sn, 1 + i);
     s->n_green = (uint8_t)g;
   }
-  for (int r = 0; r < NRED; ++r) {
+  for (int r = 0; r < NRED; ++r) {   // _generate_red_agents (ESG.py:751-817)
     int sn = red_subnet_alloc(r, (int)rng_below(x.r, (uint32_t)red_nsub(r)));
-    int c = (int)rng_below(x.r, (uint32_t)(s->n_users[sn] + s->n_servers[sn]));
+    int c = (int)rng_below(x.r, (uint32_t)(s->n_users[sn] + s->n_servers[sn]));   // choice(non-router hosts): users then servers
     s->red[r].h.start_host = (uint8_t)(c < s->n_users[sn] ? h_make(sn, 1 + c) : h_make(sn, 11 + (c - s->n_users[sn])));
     s->red[r].h.new_sess_host = 0xFF;
   }
 }
-// phase 5, per host: starting sessions (State.__init__, State.py:103-136) from the host's stream, then the backup image
+// host.create_backup() (State.py:137-138) of a generated host: the backup image is written, and what the generation parked in the row (the
+// address, the OS) leaves it
+CC4_HD void reset_seal_host(Ctx x, int h) {
+  host_backup(x, h, x.hd[h].procs[PIN - 1].pid);
+  x.hd[h].procs[PIN - 1].pid = 0; x.hd[h].gtmp = 0;
+}
+// phase 5, counter mode, per host: starting sessions (State.__init__, State.py:103-136) from the host's stream, then the backup image
 CC4_HD void reset_host_sessions(Ctx x, int h) {
   EnvState* s = x.s;
   if (!bit_get(s->exists, h)) return;
@@ -948,10 +955,39 @@ CC4_HD void reset_host_sessions(Ctx x, int h) {
   if (blue_of_subnet(h_subnet(h)) >= 0) (void)start_session_proc(x, h, K_SESS_BLUE);
   if (h != H_INTERNET && h_is_user(h)) (void)start_session_proc(x, h, K_SESS_GREEN);
   if (h == s->red[0].h.start_host) (void)start_session_proc(x, h, K_SESS_RED);
-  host_backup(x, h, x.hd[h].procs[PIN - 1].pid);
-  x.hd[h].procs[PIN - 1].pid = 0; x.hd[h].gtmp = 0;
+  reset_seal_host(x, h);
 }
-// phase 6, one thread: red_agent_0's session, initial observations, counters
+// phase 5, numpy stream: the same starting sessions in the reference's order (State.py:103-136: agent by agent, a blue agent's parent host
+// first); the backup images follow in reset_seal_all_hosts
+CC4_HD void reset_sessions_agent_order(Ctx x) {
+  EnvState* s = x.s;
+  for (int b = 0; b < NBLUE; ++b) {
+    int ph = s->blue[b].parent_host;
+    (void)start_session_proc(x, ph, K_SESS_BLUE);
+    for (int i = 0; i < blue_nsub(b); ++i) {
+      int sn = blue_subnet_alloc(b, i);
+      for (int sl = 0; sl < SLOTS; ++sl) {
+        int h = h_make(sn, sl);
+        if (!bit_get(s->exists, h) || h == ph) continue;
+        (void)start_session_proc(x, h, K_SESS_BLUE);
+      }
+    }
+  }
+  for (int g = 0; g < s->n_green; ++g) (void)start_session_proc(x, s->green_host[g], K_SESS_GREEN);
+  (void)start_session_proc(x, s->red[0].h.start_host, K_SESS_RED);
+}
+// numpy stream, behind the sessions: the backup image of every host, serially (counter mode seals a host on its own thread, in reset_host_sessions)
+CC4_HD void reset_seal_all_hosts(Ctx x) {
+  EnvState* s = x.s;
+  for (int h = 0; h < MAXH; ++h) {
+    if (bit_get(s->exists, h)) reset_seal_host(x, h);
+    eph_clear(x, h);
+  }
+  s->npend = 0;
+}
+// phase 6, one thread: red_agent_0's session (it starts active with session 0, ESG.py:791-801), initial observations (AgentInterface.set_init_obs,
+// Shared/AgentInterface.py:110-117, with the OSINT observation of the start host; SimulationController.reset_observation, SC:767-773: the first FSM
+// call sees it keyed by hostname), counters.  topo_seed: 0 on the numpy stream.
 CC4_HD void reset_finish(Ctx x, ResetCarry k, int steps, uint32_t topo_seed, bool rng_is_copy) {
   EnvState* s = x.s;
   {
@@ -982,11 +1018,11 @@ CC4_HD void reset_finish(Ctx x, ResetCarry k, int steps, uint32_t topo_seed, boo
 CC4_HD void env_reset_counter_mode(Ctx x, uint64_t seed, int steps, bool continue_stream, int policy, uint32_t topo_seed, uint32_t* ws,
                                    bool rng_is_copy) {
   reset_zero(x.s, x.hd, x.c, 0, 1);
-  ResetCarry k = reset_topology(x, seed, steps, continue_stream, policy, topo_seed, ws, rng_is_copy);
+  ResetCarry k = reset_topology<1>(x, seed, steps, continue_stream, policy, topo_seed, ws, rng_is_copy, ResetHostLater{});
   {
     Rng t; rng_fork(&t, x.r, ST_GEN_HOST);
     Ctx xh = x; xh.r = &t;
-    for (int h = 0; h < MAXH; ++h) reset_gen_host(xh, h);
+    for (int h = 0; h < MAXH; ++h) reset_gen_host<1>(xh, h);
   }
   reset_pid_serial(x, reset_used_set(x.s));
   reset_used_clear(x.s, 0, 1);
@@ -998,171 +1034,27 @@ CC4_HD void env_reset_counter_mode(Ctx x, uint64_t seed, int steps, bool continu
   }
   reset_finish(x, k, steps, topo_seed, rng_is_copy);
 }
+// the phases in the numpy stream's draw order: every host right behind its address, every pid against the running set (lent from the idle
+// session pool like counter mode's), the starting sessions in agent order.  No topology seed on this stream: the reference randomises per reset.
+CC4_HD void env_reset_numpy_stream(Ctx x, uint64_t seed, int steps, bool continue_stream, int policy, bool rng_is_copy) {
+  reset_zero(x.s, x.hd, x.c, 0, 1);
+  ResetCarry k = reset_topology<0>(x, seed, steps, continue_stream, policy, 0, nullptr, rng_is_copy, ResetHostNow{});
+  reset_used_clear(x.s, 0, 1);
+  reset_agents(x);
+  reset_sessions_agent_order(x);
+  reset_seal_all_hosts(x);
+  reset_finish(x, k, steps, 0, rng_is_copy);
+}
 
 // continue_stream = true restates CybORG.reset(seed=None) (env.py:218-243): the same Generator keeps going.
 // topo_seed != 0 (counter-based RNG mode only): every episode draws its scenario from the reset stream of the key
 // `topo_seed` instead of its own key, i.e. all episodes of a batch share topology, services and pids and differ only in
 // their dynamics (SURVEY 8(d)-5 "uniform topology" contrast; the reference always randomises per reset).
-// pid_ws: counter mode: RESET_WS_WORDS words of work area; numpy-stream mode: optional 288-word area for the used-pid bitmap
-// of the generation (default: lent from the idle session pool of the row).
+// ws: counter mode: RESET_WS_WORDS words of work area; numpy stream: unused.
 CC4_HD void env_reset(Ctx x, uint64_t seed, int rng_mode, int steps, bool continue_stream, int policy = 0, uint32_t topo_seed = 0,
-                      uint32_t* pid_ws = nullptr, bool rng_is_copy = false) {
-  EnvState* s = x.s;
-  if (rng_mode == 1) {   // counter-based mode: generation in per-host phases; pid_ws must then hold RESET_WS_WORDS words
-    env_reset_counter_mode(x, seed, steps, continue_stream, policy, topo_seed, pid_ws, rng_is_copy);
-    return;
-  }
-  Rng keep = s->rng;
-  {  // zero everything (POD)
-    uint32_t* w = (uint32_t*)s;
-    for (size_t i = 0; i < offsetof(EnvState, hd) / 4; ++i) w[i] = 0;
-    uint32_t* hw = (uint32_t*)x.hd;
-    for (size_t i = 0; i < sizeof(HostDyn) * MAXH / 4; ++i) hw[i] = 0;
-  }
-  if (continue_stream) s->rng = keep; else rng_seed(&s->rng, seed, (uint32_t)rng_mode);  // NOTE: a fresh seed needs x.r == &s->rng;
-                                                                                          // a continued stream may be walked on a copy of it
-  s->rng_mode = (uint8_t)rng_mode;
-  s->policy = (uint8_t)policy;
-  rng_begin_episode(x.r);  // philox: the reset stream uses its own (step, episode) counter words
-  const uint64_t env_key = x.r->s_lo;
-  if (topo_seed && rng_mode == 1) x.r->s_lo = (uint64_t)topo_seed;
-  s->steps = steps;
-  {  // _generate_mission_phases (ESG.py:854-860)
-    int q = steps / 3, rem = steps % 3;
-    s->phase_len[0] = q + (rem >= 1 ? 1 : 0); s->phase_len[1] = q + (rem == 2 ? 1 : 0); s->phase_len[2] = q;
-  }
-  {  // backup images of the previous episode
-    uint32_t* w = (uint32_t*)x.c->hs;
-    for (size_t i = 0; i < sizeof(x.c->hs) / 4; ++i) w[i] = 0;
-  }
-  // bitmap of used_pids over 1000..9999: by default lent from the session pool, which stays empty until red_agent_0's
-  // session is added at the very end (records 8 .. 151; zeroed again below)
-  static_assert(8 + 288 * 4 / sizeof(RSess) <= RS_POOL, "the used-pid bitmap fits the idle session pool");
-  uint32_t* used = pid_ws ? pid_ws : reinterpret_cast<uint32_t*>(&s->spool[8]);
-  for (int i = 0; i < 288; ++i) used[i] = 0;
-
-  // _generate_subnets (ESG.py:171-266): choice(len(remaining /24 blocks)) per subnet, pop.  The remaining list stays
-  // ascending, so "pop(c)" is the c-th set bit of a 256-bit availability map
-  {
-    uint32_t* avail = x.w->scratch;  // 8 words
-    for (int i = 0; i < 8; ++i) avail[i] = 0xFFFFFFFFu;
-    int n = 256;
-    for (int sn = 0; sn < NSUB; ++sn) {
-      int c = (int)rng_below(x.r, (uint32_t)n);
-      int v = nth_set(avail, 8, c);
-      s->cidr_octet[sn] = (uint8_t)v;
-      bit_clr(avail, v);
-      n--;
-    }
-  }
-  // _generate_hosts (ESG.py:312-371): ip_addresses = hosts .1 .. .254 of the /24, ascending
-  for (int sn = 0; sn < NSUB; ++sn) {
-    uint32_t* ips = x.w->scratch;  // bit v set <=> 10.0.X.v still unassigned
-    for (int i = 0; i < 8; ++i) ips[i] = 0xFFFFFFFFu;
-    ips[0] &= ~1u; ips[7] &= 0x7FFFFFFFu;  // .0 and .255 are not host addresses
-    int n = 254;
-    auto pop_at = [&](int c) { int v = nth_set(ips, 8, c); bit_clr(ips, v); n--; return (uint8_t)v; };
-    if (sn == S_INT) {
-      int c = (int)rng_below(x.r, (uint32_t)n);
-      uint8_t ip = pop_at(c);
-      gen_host(x, H_INTERNET, used);
-      x.hd[H_INTERNET].procs[PIN - 1].pid = ip;   // parked in the last inline process slot until the backup image is written
-      continue;
-    }
-    int hr = h_make(sn, 0);
-    { int c = (int)rng_below(x.r, (uint32_t)n); uint8_t ip = pop_at(c); gen_host(x, hr, used); x.hd[hr].procs[PIN - 1].pid = ip; }
-    int nu = 3 + (int)rng_below(x.r, 8);  // integers(3, 10, endpoint=True)
-    for (int i = 0; i < nu; ++i) {
-      int h = h_make(sn, 1 + i);
-      int c = (int)rng_below(x.r, (uint32_t)n); uint8_t ip = pop_at(c);
-      gen_host(x, h, used); x.hd[h].procs[PIN - 1].pid = ip;
-    }
-    int ns = 1 + (int)rng_below(x.r, 6);  // integers(1, 6, endpoint=True)
-    for (int i = 0; i < ns; ++i) {
-      int h = h_make(sn, 11 + i);
-      int v = last_set(ips, 8); bit_clr(ips, v); n--;  // ip_addresses.pop()
-      gen_host(x, h, used); x.hd[h].procs[PIN - 1].pid = (uint16_t)v;
-    }
-    s->n_users[sn] = (uint8_t)nu; s->n_servers[sn] = (uint8_t)ns;
-  }
-  // _generate_blue_agents (ESG.py:631-698)
-  for (int b = 0; b < NBLUE; ++b) {
-    int nsub = blue_nsub(b);
-    (void)rng_below(x.r, (uint32_t)nsub);  // starting_subnet = choice(allowed_subnets): unused
-    int cnt = 0;
-    for (int i = 0; i < nsub; ++i) { int sn = blue_subnet_alloc(b, i); cnt += 1 + s->n_users[sn] + s->n_servers[sn]; }
-    int c = (int)rng_below(x.r, (uint32_t)cnt);  // parent_host = choice(allowed_hosts)
-    int k = 0, ph = -1;
-    for (int i = 0; i < nsub && ph < 0; ++i) {
-      int sn = blue_subnet_alloc(b, i);
-      for (int sl = 0; sl < SLOTS; ++sl) { int h = h_make(sn, sl); if (bit_get(s->exists, h)) { if (k == c) { ph = h; break; } k++; } }
-    }
-    s->blue[b].parent_host = (uint8_t)ph;
-  }
-  // _generate_green_agents (ESG.py:700-749): one per user host, host order
-  {
-    int g = 0;
-    for (int h = 0; h < MAXH; ++h) if (bit_get(s->exists, h) && h_is_user(h)) s->green_host[g++] = (uint8_t)h;
-    s->n_green = (uint8_t)g;
-  }
-  // _generate_red_agents (ESG.py:751-817)
-  for (int r = 0; r < NRED; ++r) {
-    int nsub = red_nsub(r);
-    int sn = red_subnet_alloc(r, (int)rng_below(x.r, (uint32_t)nsub));
-    int cnt = s->n_users[sn] + s->n_servers[sn];
-    int c = (int)rng_below(x.r, (uint32_t)cnt);  // choice(non-router hosts): users then servers
-    int h = c < s->n_users[sn] ? h_make(sn, 1 + c) : h_make(sn, 11 + (c - s->n_users[sn]));
-    s->red[r].h.start_host = (uint8_t)h;
-    s->red[r].h.new_sess_host = 0xFF;
-    s->red[r].h.queue.busy = 0;
-  }
-  // State.__init__ (State.py:103-136): starting sessions in agent order; parent-less first
-  for (int b = 0; b < NBLUE; ++b) {
-    int ph = s->blue[b].parent_host;
-    (void)start_session_proc(x, ph, K_SESS_BLUE);
-    for (int i = 0; i < blue_nsub(b); ++i) {
-      int sn = blue_subnet_alloc(b, i);
-      for (int sl = 0; sl < SLOTS; ++sl) {
-        int h = h_make(sn, sl);
-        if (!bit_get(s->exists, h) || h == ph) continue;
-        (void)start_session_proc(x, h, K_SESS_BLUE);
-      }
-    }
-  }
-  for (int g = 0; g < s->n_green; ++g) (void)start_session_proc(x, s->green_host[g], K_SESS_GREEN);
-  int red0_pid = start_session_proc(x, s->red[0].h.start_host, K_SESS_RED);
-  // host.create_backup() for every host (State.py:137-138) -> dynamic state := static
-  for (int h = 0; h < MAXH; ++h) {
-    if (bit_get(s->exists, h)) { host_backup(x, h, x.hd[h].procs[PIN - 1].pid); x.hd[h].procs[PIN - 1].pid = 0; x.hd[h].gtmp = 0; }
-    eph_clear(x, h);
-  }
-  s->npend = 0;
-  if (!pid_ws) for (int i = 0; i < 288; ++i) used[i] = 0;
-  // red_agent_0 starts active with session 0 (ESG.py:791-801)
-  {
-    int idx = rs_add(x, 0, s->red[0].h.start_host, red0_pid, RS_ABSTRACT | RS_ORIG);
-    (void)idx;
-    s->red[0].h.active = 1;
-  }
-  // AgentInterface.set_init_obs (Shared/AgentInterface.py:110-117) with the OSINT observation of the start host
-  for (int r = 0; r < NRED; ++r) {
-    RedAgent& a = s->red[r];
-    int h = a.h.start_host;
-    bit_set(a.as_ip, h); bit_set(a.as_hn, h); a.h.as_subnet |= (uint16_t)(1u << h_subnet(h));
-    a.h.nobs = 0; a.h.obs_success = 0;
-    if (r == 0) {
-      as_know_sid(x, 0, 0);
-      // SimulationController.reset_observation (SC:767-773): first FSM call sees hostname-keyed OSINT obs
-      obs_put(x, 0, false, h, OE_SESS | OE_IFACE | OE_SYSHN, true);
-      obs_first(x, 0, T_UNKNOWN, RA_NONE, 0, 0);
-    }
-    a.h.exec_type = RA_SLEEP;
-  }
-  s->step_count = 0; s->phase = 0; s->done = (uint8_t)(0 >= steps - 1); s->reward = 0.f;
-  s->n_actions = NBLUE + s->n_green + NRED;
-  if (topo_seed && rng_mode == 1) x.r->s_lo = env_key;
-  if (rng_is_copy) s->rng = *x.r;      // the generator was walked on a caller-side (register) copy
-  rng_park(&s->rng);
+                      uint32_t* ws = nullptr, bool rng_is_copy = false) {
+  if (rng_mode == 1) env_reset_counter_mode(x, seed, steps, continue_stream, policy, topo_seed, ws, rng_is_copy);
+  else env_reset_numpy_stream(x, seed, steps, continue_stream, policy, rng_is_copy);
 }
 
 // ------------------------------------------------------------------ blue actions
@@ -2689,7 +2581,6 @@ CC4_HD uint32_t red_foreign_agents(const EnvState* s) {   // bit r: agent r hold
   }
   return foreign;
 }
-CC4_HD bool red_any_foreign_session(const EnvState* s) { return red_foreign_agents(s) != 0; }
 // The same question asked by the whole wave: the 30 zone words as a table built at compile time, entry 8 * w + r = the hosts of word w
 // OUTSIDE agent r's zone (the other entries are zero), so that lane 8 * w + r tests one word and a ballot holds the answers
 struct RedZoneTable { uint32_t out[40]; };
@@ -2992,120 +2883,103 @@ inline int state_edit(Ctx x, int op, int a0, int a1, int a2) {
 }
 
 // ------------------------------------------------------------------ BlueFlatWrapper.observation_change (BlueFlatWrapper.py:172-256)
-// out: OBS_TOTAL values, agents 0..3 (92 each) then agent 4 (210).  The vector splits into 12 independent parts:
-// parts 0..6 = the seven 59-value subnet blocks (agents 0..3 own one, agent 4 owns three), parts 7..11 = agent b's
-// phase word + 32 message bits.  The device encodes the parts on separate lanes; the host loops over them.
-enum : int { OBS_PARTS = 12 };
+// OBS_TOTAL values, agents 0..3 (92 each) then agent 4 (210).  An agent's segment: its phase word, one 59-value block per subnet it owns
+// (agents 0..3 own one, agent 4 owns three: seven blocks sb = 0..6 in all), the 32 message bits of the four other agents.  A block: subnet
+// one-hot, blocked bits, comms policy (9 values each, subnets in sorted order), then process and connection events of the zone's 16 host
+// slots (servers first).  The layout is stated once, in the helpers below; the four enumerations of the vector are written with them.
+enum : int { OBS_BLOCKS = 7, OBS_BLOCK_LEN = 59, OBS_MSG_BITS = (NBLUE - 1) * MSG_LEN,
+             OBS_K_ONEHOT = 0, OBS_K_BLOCKED = 9, OBS_K_COMMS = 18, OBS_K_PROC = 27, OBS_K_CONN = 43,      // offsets inside a block
+             OBS_EV_PROC = EV_CUR_PROC | EV_OLD_PROC, OBS_EV_CONN = EV_CUR_CONN | EV_OLD_CONN };           // the event masks of the two host values
+static_assert(OBS_SHORT == 1 + OBS_BLOCK_LEN + OBS_MSG_BITS && OBS_LONG == 1 + 3 * OBS_BLOCK_LEN + OBS_MSG_BITS && OBS_K_CONN + ZONE_HOSTS == OBS_BLOCK_LEN, "segment and block lengths");
+CC4_HD constexpr int obs_agent_base(int b) { return b < 4 ? b * OBS_SHORT : 4 * OBS_SHORT; }
+CC4_HD constexpr int obs_agent_len(int b) { return b < 4 ? OBS_SHORT : OBS_LONG; }
+CC4_HD constexpr int obs_block_agent(int sb) { return sb < 4 ? sb : 4; }
+CC4_HD constexpr int obs_block_subnet(int sb) { return blue_subnet_sorted(obs_block_agent(sb), sb < 4 ? 0 : sb - 4); }
+CC4_HD constexpr int obs_block_pos(int sb, int k) { return obs_agent_base(obs_block_agent(sb)) + 1 + OBS_BLOCK_LEN * (sb < 4 ? 0 : sb - 4) + k; }   // value k of block sb
+CC4_HD constexpr int obs_zone_host(int sn, int hs) { return hs < MAX_SERVERS ? h_make(sn, 11 + hs) : h_make(sn, 1 + (hs - MAX_SERVERS)); }      // zone slot hs of subnet sn
+// message bit m (0..31) of reader b: its position, and the byte of EnvState.msg it shows (the senders are the other agents in agent order)
+CC4_HD constexpr int obs_msg_pos(int b, int m) { return obs_agent_base(b) + obs_agent_len(b) - OBS_MSG_BITS + m; }
+CC4_HD constexpr int obs_msg_src(int b, int m) { return MSG_LEN * (m / MSG_LEN < b ? m / MSG_LEN : m / MSG_LEN + 1) + m % MSG_LEN; }   // msg[j][i] as j * MSG_LEN + i
+CC4_HD int obs_msg_value(const EnvState* s, int b, int m) { return (&s->msg[0][0])[obs_msg_src(b, m)]; }
+// value k of a block of subnet sn.  Event bytes of hosts that do not exist stay zero (reset_zero), so no existence test is needed.
+CC4_HD int obs_block_value(const EnvState* s, int sn, int k) {
+  if (k < OBS_K_BLOCKED) return sorted_subnet(k) == sn;
+  if (k < OBS_K_COMMS) return (s->blocks[sn] >> sorted_subnet(k - OBS_K_BLOCKED)) & 1u;
+  if (k < OBS_K_PROC) return !((comms_adjacent(s->phase, sn) >> sorted_subnet(k - OBS_K_COMMS)) & 1u);
+  const int ev = s->hev[obs_zone_host(sn, k < OBS_K_CONN ? k - OBS_K_PROC : k - OBS_K_CONN)];
+  return (ev & (k < OBS_K_CONN ? OBS_EV_PROC : OBS_EV_CONN)) != 0;
+}
+// (1) part by part, what the oracle and k_reset encode with.  The vector splits into 12 independent parts: parts 0..6 = the seven subnet
+// blocks, parts 7..11 = agent b's phase word + message bits.
+enum : int { OBS_PARTS = OBS_BLOCKS + NBLUE };
 template <typename T>
 CC4_HD void env_flat_obs_part(const EnvState* s, T* out, int part) {
-  if (part < 7) {
-    int b = part < 4 ? part : 4, i = part < 4 ? 0 : part - 4;
-    int o = (b < 4 ? b * OBS_SHORT : 4 * OBS_SHORT) + 1 + 59 * i;
-    int sn = blue_subnet_sorted(b, i);
+  if (part < OBS_BLOCKS) {
+    const int sn = obs_block_subnet(part), o = obs_block_pos(part, 0);
     uint32_t blk = s->blocks[sn];
     uint32_t adj = comms_adjacent(s->phase, sn);
     for (int k = 0; k < NSUB; ++k) {
       int ss = sorted_subnet(k);
-      out[o + k] = (T)(ss == sn);
-      out[o + 9 + k] = (T)((blk >> ss) & 1u);
-      out[o + 18 + k] = (T)(!((adj >> ss) & 1u));
+      out[o + OBS_K_ONEHOT + k] = (T)(ss == sn);
+      out[o + OBS_K_BLOCKED + k] = (T)((blk >> ss) & 1u);
+      out[o + OBS_K_COMMS + k] = (T)(!((adj >> ss) & 1u));
     }
     for (int hs = 0; hs < ZONE_HOSTS; ++hs) {
-      int h = hs < MAX_SERVERS ? h_make(sn, 11 + hs) : h_make(sn, 1 + (hs - MAX_SERVERS));
+      int h = obs_zone_host(sn, hs);
       int ev = bit_get(s->exists, h) ? s->hev[h] : 0;
-      out[o + 27 + hs] = (T)((ev & (EV_CUR_PROC | EV_OLD_PROC)) != 0);
-      out[o + 43 + hs] = (T)((ev & (EV_CUR_CONN | EV_OLD_CONN)) != 0);
+      out[o + OBS_K_PROC + hs] = (T)((ev & OBS_EV_PROC) != 0);
+      out[o + OBS_K_CONN + hs] = (T)((ev & OBS_EV_CONN) != 0);
     }
   } else {
-    int b = part - 7;
-    int base = b < 4 ? b * OBS_SHORT : 4 * OBS_SHORT;
-    int len = b < 4 ? OBS_SHORT : OBS_LONG;
-    out[base] = (T)s->phase;
-    int o = base + len - 32;
-    for (int j = 0; j < NBLUE; ++j) { if (j == b) continue; for (int i = 0; i < MSG_LEN; ++i) out[o++] = (T)s->msg[j][i]; }
+    const int b = part - OBS_BLOCKS;
+    out[obs_agent_base(b)] = (T)s->phase;
+    for (int m = 0; m < OBS_MSG_BITS; ++m) out[obs_msg_pos(b, m)] = (T)obs_msg_value(s, b, m);
   }
 }
-// the same vector, one value at a time (value `idx` of the 578): what the device encodes with one value per thread
+template <typename T>
+CC4_HD void env_flat_obs(const EnvState* s, T* out) {
+  for (int p = 0; p < OBS_PARTS; ++p) env_flat_obs_part<T>(s, out, p);
+}
+// (2) the same vector by position (value `idx` of the 578): the oracle's cross-check of the other enumerations
 CC4_HD int env_flat_obs_at(const EnvState* s, int idx) {
   const int b = idx < 4 * OBS_SHORT ? idx / OBS_SHORT : 4;
-  const int j = idx - (b < 4 ? b * OBS_SHORT : 4 * OBS_SHORT);
-  const int len = b < 4 ? OBS_SHORT : OBS_LONG;
+  const int j = idx - obs_agent_base(b), m0 = obs_agent_len(b) - OBS_MSG_BITS;
   if (j == 0) return s->phase;
-  if (j >= len - 32) {
-    const int m = j - (len - 32), jj = m / MSG_LEN;
-    return s->msg[jj < b ? jj : jj + 1][m % MSG_LEN];
-  }
-  const int q = j - 1, i = q / 59, k = q % 59;
-  const int sn = blue_subnet_sorted(b, i);
-  if (k < 9) return sorted_subnet(k) == sn;
-  if (k < 18) return (s->blocks[sn] >> sorted_subnet(k - 9)) & 1u;
-  if (k < 27) return !((comms_adjacent(s->phase, sn) >> sorted_subnet(k - 18)) & 1u);
-  const int hs = k < 43 ? k - 27 : k - 43;
-  const int h = hs < MAX_SERVERS ? h_make(sn, 11 + hs) : h_make(sn, 1 + (hs - MAX_SERVERS));
-  const int ev = s->hev[h];   // bytes of hosts that do not exist stay zero (env_reset), so no existence test is needed
-  return k < 43 ? ((ev & (EV_CUR_PROC | EV_OLD_PROC)) != 0) : ((ev & (EV_CUR_CONN | EV_OLD_CONN)) != 0);
+  if (j >= m0) return obs_msg_value(s, b, j - m0);
+  return obs_block_value(s, blue_subnet_sorted(b, (j - 1) / OBS_BLOCK_LEN), (j - 1) % OBS_BLOCK_LEN);
 }
-// The same 578 values enumerated kind by kind (v = 0..577), so that the lanes of a wave take the same branch, the values that
-// can change every step first:
-//   [0,224) host events (7 subnet blocks x {16 process, 16 connection}), [224,384) message bits (5 agents x 32)  -- OBS_FAST --
-//   [384,447) blocked bits, [447,510) comms policy, [510,573) subnet one-hot, [573,578) the 5 phase words (EnvState.obs_dirty).
-// *idx = position in the vector.
+// (3) The values that can change every step (OBS_FAST of them, v = 0..383: [0,224) host events, 7 subnet blocks x {16 process, 16 connection};
+// [224,384) message bits, 5 agents x 32) as a table -- the device kernels read it instead of redoing the index arithmetic for every value of
+// every step: entry v = position in the vector | source byte << 10 | bit mask << 18; the value is (byte & mask) != 0.  Source byte 0..136: the
+// event bits of host h (EnvState.hev); 137 + 8 j + i: message bit i of blue agent j (EnvState.msg[j][i]).
 enum : int { OBS_FAST = 384 };
-CC4_HD int env_flat_obs_sorted(const EnvState* s, int v, int* idx) {
-  if (v >= 224 && v < OBS_FAST) {
-    const int w = v - 224, b = w >> 5, m = w & 31, jj = m / MSG_LEN;
-    *idx = (b < 4 ? b * OBS_SHORT + OBS_SHORT : 4 * OBS_SHORT + OBS_LONG) - 32 + m;
-    return s->msg[jj < b ? jj : jj + 1][m % MSG_LEN];
-  }
-  if (v < 573) {
-    int sb, k;       // subnet block 0..6 (agents 0..3 own one, agent 4 owns three), offset inside the 59-value block
-    if (v < 224) { sb = v >> 5; const int r = v & 31; k = 27 + (r & 15) + ((r >> 4) ? 16 : 0); }
-    else { const int w = v - OBS_FAST, kind = w / 63, q = w % 63; sb = q / 9; k = 9 * (kind == 0 ? 1 : (kind == 1 ? 2 : 0)) + q % 9; }
-    const int b = sb < 4 ? sb : 4, i = sb < 4 ? 0 : sb - 4;
-    *idx = (b < 4 ? b * OBS_SHORT : 4 * OBS_SHORT) + 1 + 59 * i + k;
-    const int sn = blue_subnet_sorted(b, i);
-    if (k >= 27) {
-      const int hs = k < 43 ? k - 27 : k - 43;
-      const int h = hs < MAX_SERVERS ? h_make(sn, 11 + hs) : h_make(sn, 1 + (hs - MAX_SERVERS));
-      const int ev = s->hev[h];   // bytes of hosts that do not exist stay zero (env_reset)
-      return k < 43 ? ((ev & (EV_CUR_PROC | EV_OLD_PROC)) != 0) : ((ev & (EV_CUR_CONN | EV_OLD_CONN)) != 0);
-    }
-    if (k < 9) return sorted_subnet(k) == sn;
-    if (k < 18) return (s->blocks[sn] >> sorted_subnet(k - 9)) & 1u;
-    return !((comms_adjacent(s->phase, sn) >> sorted_subnet(k - 18)) & 1u);
-  }
-  const int b = v - 573;
-  *idx = b < 4 ? b * OBS_SHORT : 4 * OBS_SHORT;
-  return s->phase;
-}
-// The OBS_FAST values as a table (the device kernels read it instead of redoing the index arithmetic for every value of every
-// step): entry v = position in the vector | source byte << 10 | bit mask << 18; the value is (byte & mask) != 0.  Source byte
-// 0..136: the event bits of host h (EnvState.hev); 137 + 8 j + i: message bit i of blue agent j (EnvState.msg[j][i]).  Same enumeration as
-// env_flat_obs_sorted (tests/test_host_logic.py checks the two against each other).
 CC4_HD constexpr uint32_t obs_fast_entry(int v) {
   if (v >= 224) {
-    const int w = v - 224, b = w >> 5, m = w & 31, jj = m / MSG_LEN;
-    const int idx = (b < 4 ? b * OBS_SHORT + OBS_SHORT : 4 * OBS_SHORT + OBS_LONG) - 32 + m;
-    const int src = MAXH + MSG_LEN * (jj < b ? jj : jj + 1) + m % MSG_LEN;
-    return (uint32_t)idx | ((uint32_t)src << 10) | (1u << 18);
+    const int w = v - 224, b = w >> 5, m = w & 31;
+    return (uint32_t)obs_msg_pos(b, m) | ((uint32_t)(MAXH + obs_msg_src(b, m)) << 10) | (1u << 18);
   }
-  const int sb = v >> 5, r = v & 31, k = 27 + (r & 15) + ((r >> 4) ? 16 : 0);
-  const int b = sb < 4 ? sb : 4, i = sb < 4 ? 0 : sb - 4;
-  const int idx = (b < 4 ? b * OBS_SHORT : 4 * OBS_SHORT) + 1 + 59 * i + k;
-  const int sn = blue_subnet_sorted(b, i);
-  const int hs = k < 43 ? k - 27 : k - 43;
-  const int h = hs < MAX_SERVERS ? h_make(sn, 11 + hs) : h_make(sn, 1 + (hs - MAX_SERVERS));
-  const uint32_t mask = k < 43 ? (uint32_t)(EV_CUR_PROC | EV_OLD_PROC) : (uint32_t)(EV_CUR_CONN | EV_OLD_CONN);
-  return (uint32_t)idx | ((uint32_t)h << 10) | (mask << 18);
+  const int sb = v >> 5, r = v & 31;   // r: zone slot, + 16 for the connection value
+  const uint32_t mask = r < ZONE_HOSTS ? (uint32_t)OBS_EV_PROC : (uint32_t)OBS_EV_CONN;
+  return (uint32_t)obs_block_pos(sb, OBS_K_PROC + r) | ((uint32_t)obs_zone_host(obs_block_subnet(sb), r & 15) << 10) | (mask << 18);
 }
 CC4_HD int obs_fast_value(uint32_t entry, const EnvState* s) {
   const int src = (int)((entry >> 10) & 0xFF);
   const uint32_t byte = src < MAXH ? s->hev[src] : (&s->msg[0][0])[src - MAXH];
   return (byte & (entry >> 18)) != 0 ? 1 : 0;
 }
-template <typename T>
-CC4_HD void env_flat_obs(const EnvState* s, T* out) {
-  for (int p = 0; p < OBS_PARTS; ++p) env_flat_obs_part<T>(s, out, p);
+// (4) All 578 values enumerated kind by kind (v = 0..577), so that the lanes of a wave take the same branch, the values that can change
+// every step first: [0,384) the OBS_FAST values as above, [384,447) blocked bits, [447,510) comms policy, [510,573) subnet one-hot (7 blocks x
+// 9 each), [573,578) the 5 phase words (EnvState.obs_dirty).  *idx = position in the vector.
+CC4_HD int env_flat_obs_sorted(const EnvState* s, int v, int* idx) {
+  if (v < OBS_FAST) { const uint32_t e = obs_fast_entry(v); *idx = (int)(e & 0x3FFu); return obs_fast_value(e, s); }
+  if (v < 573) {
+    const int w = v - OBS_FAST, kind = w / 63, q = w % 63, sb = q / 9;
+    const int k = (kind == 0 ? OBS_K_BLOCKED : (kind == 1 ? OBS_K_COMMS : OBS_K_ONEHOT)) + q % 9;
+    *idx = obs_block_pos(sb, k);
+    return obs_block_value(s, obs_block_subnet(sb), k);
+  }
+  *idx = obs_agent_base(v - 573);
+  return s->phase;
 }
 
 }  // namespace cc4

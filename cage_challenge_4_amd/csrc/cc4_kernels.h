@@ -235,12 +235,12 @@ __device__ __forceinline__ void reset_counter_mode_block(EnvState* s, HostDyn* c
   Ctx xm{s, cold_e, RNG_COPY ? &rr : &s->rng, hd, work};
   if (t == 0) {
     if (RNG_COPY) { rr = s->rng; rr.mode = 1; }
-    carry = reset_topology(xm, seed, steps, continue_stream, policy, topo, ws, RNG_COPY);
+    carry = reset_topology<1>(xm, seed, steps, continue_stream, policy, topo, ws, RNG_COPY, ResetHostLater{});
   }
   __syncthreads();
   Rng rh; rng_fork(&rh, &s->rng, ST_GEN_HOST); rh.mode = 1;
   Ctx xh{s, cold_e, &rh, hd, work};
-  if constexpr (NT >= MAXH) { if (t < MAXH) reset_gen_host(xh, t); } else { for (int h = t; h < MAXH; h += NT) reset_gen_host(xh, h); }
+  if constexpr (NT >= MAXH) { if (t < MAXH) reset_gen_host<1>(xh, t); } else { for (int h = t; h < MAXH; h += NT) reset_gen_host<1>(xh, h); }
   __syncthreads();
   if (t == 0) { reset_pid_serial(xm, reset_used_set(s)); reset_agents(xm); }
   __syncthreads();
