@@ -19,6 +19,7 @@ NUM_BLUE = 5
 MSG_LEN = 8
 TOPOLOGY_BYTES = 27 + 2 * 137
 FEAT_HOSTS, FEAT_PER_HOST, FEAT_GLOBAL = 137, 16, 32     # CC4_FEAT_*: the state-feature tensors (state_features.py)
+POLICY_KEEP, POLICY_DEFAULT = -1, -2                     # CC4_POLICY_*: per-episode opponent classes (cc4_set_policies)
 OBS_LEN = (92, 92, 92, 92, 210)
 ACT_LEN = (82, 82, 82, 82, 242)
 OBS_OFF = (0, 92, 184, 276, 368)
@@ -84,6 +85,13 @@ SIGNATURES = {
     'cc4_clone_episodes': (ctypes.c_int, [_P, ctypes.c_int32, _P, _P, _P]),
     'cc4_state_features_device': (ctypes.c_int, [_P, _P, ctypes.c_int32, _P, ctypes.c_int32, _P, _P]),
     'cc4_state_features_from_row': (ctypes.c_int, [_P, _P, _P]),
+    'cc4_set_policies_device': (ctypes.c_int, [_P, _P, _P, _P]),
+    'cc4_set_policies': (ctypes.c_int, [_P, _P, _P, _P]),
+    'cc4_policies_device': (ctypes.c_int, [_P, _P, _P]),
+    'cc4_get_policies': (ctypes.c_int, [_P, _P, _P]),
+    'cc4_row_set_policies': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    'cc4_row_get_policies': (ctypes.c_int, [_P, _P, _P]),
+    'cc4_reset_device': (ctypes.c_int, [_P, _P, _P]),
     'cc4_rollout_begin': (ctypes.c_int, [_P, ctypes.c_int32]),
     'cc4_rollout_groups': (ctypes.c_int, [_P, _P, _P]),
     'cc4_rollout_policy_stream': (ctypes.c_int, [_P, _P]),

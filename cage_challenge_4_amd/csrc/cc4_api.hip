@@ -410,7 +410,7 @@ void cc4_destroy(cc4_handle* h) {
   if (h->rev) (void)hipEventDestroy(h->rev);
   for (void* p : {(void*)h->d_ract, (void*)h->d_rready, (void*)h->d_rcnt, (void*)h->d_rfail}) if (p) (void)hipFree(p);
   void* ptrs[] = {h->d_state, h->d_cold, h->small_io ? nullptr : (void*)h->d_actions, h->d_seeds, h->d_envmask, h->small_io ? nullptr : (void*)h->d_obs,
-                  h->d_mask, h->d_rng, h->d_reset_ws, h->d_ext, h->d_run, h->d_slot_part, h->d_pool, h->d_claim, h->d_mask_stale, h->d_copy_idx, h->d_copy_seeds};     // (d_msgs, d_reward, d_err, d_done live inside d_actions / d_obs; small handles: pinned host memory, freed below)
+                  h->d_mask, h->d_rng, h->d_reset_ws, h->d_ext, h->d_run, h->d_slot_part, h->d_pool, h->d_claim, h->d_mask_stale, h->d_copy_idx, h->d_copy_seeds, h->d_pol};     // (d_msgs, d_reward, d_err, d_done live inside d_actions / d_obs; small handles: pinned host memory, freed below)
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (h->shadow) { cc4_destroy(h->shadow); h->shadow = nullptr; (void)hipSetDevice(h->cfg.device_id); }
   for (void* p : {(void*)h->d_prev_state, (void*)h->d_prev_cold, (void*)h->d_prev_out}) if (p) (void)hipFree(p);
@@ -434,13 +434,10 @@ void cc4_destroy(cc4_handle* h) {
   delete h;
 }
 
-int cc4_reset(cc4_handle* h, const uint64_t* seeds, const uint8_t* env_mask) {
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  if (join_groups(h)) return -1;
-  size_t n = (size_t)h->cfg.num_envs;
-  if (seeds) HIPCHK(h, hipMemcpyAsync(h->d_seeds, seeds, n * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
-  if (env_mask) HIPCHK(h, hipMemcpyAsync(h->d_envmask, env_mask, n, hipMemcpyHostToDevice, h->stream));
-  ResetArgs a{h->d_state, h->d_cold, seeds ? h->d_seeds : nullptr, env_mask ? h->d_envmask : nullptr, h->d_obs, h->d_reward,
+// the launch of a reset on the main stream (joined by the caller), from seeds and a mask on the device (either may be null), and its bookkeeping: what
+// cc4_reset does behind its uploads and cc4_reset_device on the caller's own pointers
+static int reset_launch(cc4_handle* h, const uint64_t* d_seeds, const uint8_t* d_env_mask) {
+  ResetArgs a{h->d_state, h->d_cold, d_seeds, d_env_mask, h->d_obs, h->d_reward,
               h->d_done, h->d_err, h->d_mask, h->cfg.num_envs, h->cfg.steps, h->cfg.rng_mode,
               policy_bits(h->cfg), (uint32_t)h->cfg.topology_seed,
               h->comm ? h->d_obs8[h->obs_buf] : nullptr};
@@ -449,14 +446,107 @@ int cc4_reset(cc4_handle* h, const uint64_t* seeds, const uint8_t* env_mask) {
   if (h->comm && h->gathers_issued > h->gathers_waited) { HIPCHK(h, hipStreamSynchronize(h->comm_stream)); h->gathers_waited = h->gathers_issued; }
   if (h->comm && h->obs8_from_slab >= 0) {      // the reset writes the current ring buffer's packed rows itself -- all of them, unless it is masked
     const size_t row = (size_t)h->cfg.num_envs * OBS_PACKED;
-    if (env_mask) HIPCHK(h, hipMemcpyAsync(h->d_obs8[h->obs_buf], h->d_xslab + (size_t)h->obs8_from_slab * row, row, hipMemcpyDeviceToDevice, h->stream));
+    if (d_env_mask) HIPCHK(h, hipMemcpyAsync(h->d_obs8[h->obs_buf], h->d_xslab + (size_t)h->obs8_from_slab * row, row, hipMemcpyDeviceToDevice, h->stream));
     h->obs8_from_slab = -1;
   }
   hipLaunchKernelGGL(k_reset, dim3(h->cfg.num_envs), dim3(WAVE), 0, h->stream, a);
   HIPCHK(h, hipGetLastError());
   h->prev_valid = false;            // (cc4_replay_logged: no step to repeat)
   h->step_event_attached = false;   // the buffer's event must be recorded again before the next all-gather
+  return 0;
+}
+int cc4_reset(cc4_handle* h, const uint64_t* seeds, const uint8_t* env_mask) {
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  if (join_groups(h)) return -1;
+  size_t n = (size_t)h->cfg.num_envs;
+  if (seeds) HIPCHK(h, hipMemcpyAsync(h->d_seeds, seeds, n * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
+  if (env_mask) HIPCHK(h, hipMemcpyAsync(h->d_envmask, env_mask, n, hipMemcpyHostToDevice, h->stream));
+  if (int rc = reset_launch(h, seeds ? h->d_seeds : nullptr, env_mask ? h->d_envmask : nullptr)) return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));
+  return 0;
+}
+// cc4_reset on seeds and a mask that are on the device already (a criterion a kernel of the caller's evaluated: env_mask = done): no upload, no host wait
+int cc4_reset_device(cc4_handle* h, const uint64_t* d_seeds, const uint8_t* d_env_mask) {
+  if (h->rollout_k > 0) { h->err = "cc4_reset_device: a rollout is in flight on this handle: cc4_rollout_end first"; return -2; }
+  if (h->comm) { h->err = "cc4_reset_device: not on a handle with a communicator (cc4_reset orders the exchange's buffers through the host)"; return -2; }
+  if (reinterpret_cast<uintptr_t>(d_seeds) % 8) { h->err = "cc4_reset_device: the seeds must be 8-byte aligned"; return -2; }
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  if (join_groups(h)) return -1;
+  return reset_launch(h, d_seeds, d_env_mask);
+}
+
+// ---- per-episode opponent classes (include/cc4.h "Mixed opponents in one batch"; the rule: row_assign / row_policies, cc4_state.h).  An assignment
+// is a byte of the hot row that only the regenerations read: no step launch needs ordering behind these beyond the main stream's own.
+static int policy_call_refused(cc4_handle* h, const char* who) {
+  if (h->rollout_k > 0) { h->err = std::string(who) + ": a rollout is in flight on this handle: cc4_rollout_end first"; return -2; }
+  return 0;
+}
+int cc4_set_policies_device(cc4_handle* h, const int8_t* d_red, const int8_t* d_green, const int8_t* d_blue) {
+  if (int rc = policy_call_refused(h, "cc4_set_policies_device")) return rc;
+  if (!d_red && !d_green && !d_blue) return 0;
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  if (join_groups(h)) return -1;
+  const int n = h->cfg.num_envs;
+  hipLaunchKernelGGL(k_set_policies, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->d_state, d_red, d_green, d_blue, n, h->d_copy_fault);
+  HIPCHK(h, hipGetLastError());
+  h->prev_valid = false;        // (cc4_replay_logged would repeat a step from rows that have moved on)
+  return 0;
+}
+int cc4_set_policies(cc4_handle* h, const int8_t* red, const int8_t* green, const int8_t* blue) {
+  if (int rc = policy_call_refused(h, "cc4_set_policies")) return rc;
+  if (!red && !green && !blue) return 0;
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  if (join_groups(h)) return -1;
+  const size_t n = (size_t)h->cfg.num_envs;
+  if (!h->d_pol) HIPCHK(h, hipMalloc(&h->d_pol, 6 * n));
+  const int8_t* src[3] = {red, green, blue};
+  const int8_t* dev[3] = {nullptr, nullptr, nullptr};
+  for (int c = 0; c < 3; ++c) if (src[c]) { HIPCHK(h, hipMemcpyAsync(h->d_pol + c * n, src[c], n, hipMemcpyHostToDevice, h->stream)); dev[c] = h->d_pol + c * n; }
+  if (int rc = cc4_set_policies_device(h, dev[0], dev[1], dev[2])) return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));     // (the host arrays may go away once the call returns)
+  return 0;
+}
+int cc4_policies_device(cc4_handle* h, int8_t* d_live, int8_t* d_assigned) {
+  if (int rc = policy_call_refused(h, "cc4_policies_device")) return rc;
+  if (!d_live && !d_assigned) return 0;
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  if (join_groups(h)) return -1;
+  const int n = h->cfg.num_envs;
+  hipLaunchKernelGGL(k_get_policies, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->d_state, d_live, d_assigned, n);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+int cc4_get_policies(cc4_handle* h, int8_t* live, int8_t* assigned) {
+  if (int rc = policy_call_refused(h, "cc4_get_policies")) return rc;
+  if (!live && !assigned) return 0;
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  if (join_groups(h)) return -1;
+  const size_t n = (size_t)h->cfg.num_envs;
+  if (!h->d_pol) HIPCHK(h, hipMalloc(&h->d_pol, 6 * n));
+  if (int rc = cc4_policies_device(h, live ? h->d_pol : nullptr, assigned ? h->d_pol + 3 * n : nullptr)) return rc;
+  if (live) HIPCHK(h, hipMemcpyAsync(live, h->d_pol, 3 * n, hipMemcpyDeviceToHost, h->stream));
+  if (assigned) HIPCHK(h, hipMemcpyAsync(assigned, h->d_pol + 3 * n, 3 * n, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return 0;
+}
+// The same definition on one hot row (cc4_get_state, a checkpoint): no device, no handle.
+int cc4_row_set_policies(void* hot_row, int red, int green, int blue) {
+  if (!hot_row) return -2;
+  EnvState* s = static_cast<EnvState*>(aligned_alloc(alignof(EnvState), sizeof(EnvState)));   // (the caller's bytes may sit at any address)
+  if (!s) return -1;
+  memcpy(s, hot_row, offsetof(EnvState, hd));
+  const bool ok = row_assign(s, red, green, blue);
+  if (ok) static_cast<uint8_t*>(hot_row)[offsetof(EnvState, assign)] = s->assign;
+  free(s);
+  return ok ? 0 : -2;
+}
+int cc4_row_get_policies(const void* hot_row, int8_t live[3], int8_t assigned[3]) {
+  if (!hot_row) return -2;
+  EnvState* s = static_cast<EnvState*>(aligned_alloc(alignof(EnvState), sizeof(EnvState)));
+  if (!s) return -1;
+  memcpy(s, hot_row, offsetof(EnvState, hd));
+  row_policies(s, live, assigned);
+  free(s);
   return 0;
 }
 

@@ -756,11 +756,11 @@ CC4_HD void host_restore(Ctx x, int h) {  // Host.restore (Host.py:373-429)
 struct ResetCarry { uint64_t env_key; };
 enum : int { RESET_WS_SEEN = 0, RESET_WS_DUP = 288, RESET_WS_HOSTS = 576, RESET_WS_WORDS = 584 };   // work area (LDS on the device)
 
-// phase 0, all threads: clear the row (except the generator) and the backup images
+// phase 0, all threads: clear the row (except the generator and the assignment of opponent classes) and the backup images
 CC4_HD void reset_zero(EnvState* s, HostDyn* hd, EnvCold* c, int t, int nt) {
   static_assert(offsetof(EnvState, rng) == 0, "the generator leads the row");
   uint32_t* w = (uint32_t*)s;
-  for (size_t i = sizeof(Rng) / 4 + (size_t)t; i < offsetof(EnvState, hd) / 4; i += (size_t)nt) w[i] = 0;
+  for (size_t i = sizeof(Rng) / 4 + (size_t)t; i < offsetof(EnvState, hd) / 4; i += (size_t)nt) w[i] = i == PA_WORD ? w[i] & PA_WORD_MASK : 0;   // (the episode's assignment outlives it)
   uint32_t* hw = (uint32_t*)hd;
   for (size_t i = (size_t)t; i < sizeof(HostDyn) * MAXH / 4; i += (size_t)nt) hw[i] = 0;
   uint32_t* b = (uint32_t*)c->hs;
@@ -825,7 +825,7 @@ CC4_HD ResetCarry reset_topology(Ctx x, uint64_t seed, int steps, bool continue_
   EnvState* s = x.s;
   if (!continue_stream) rng_seed(&s->rng, seed, (uint32_t)RNG_MODE);   // a fresh seed needs x.r == &s->rng; a continued stream may be walked on a copy of it
   s->rng_mode = (uint8_t)RNG_MODE;
-  s->policy = (uint8_t)policy;
+  s->policy = (uint8_t)policy_at_reset(s, policy);   // the episode's assignment (EnvState.assign), else the caller's classes: the handle's configuration
   rng_begin_episode(x.r);   // counter mode: the reset stream uses its own (step, episode) counter words
   ResetCarry k; k.env_key = x.r->s_lo;
   if (RNG_MODE == 1 && topo_seed) x.r->s_lo = (uint64_t)topo_seed;

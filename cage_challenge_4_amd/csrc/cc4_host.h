@@ -170,6 +170,7 @@ struct cc4_handle {
   // k_policy_outputs honours; the host-array surface (cc4_clone_episodes) stages its indices and seeds in d_copy_idx
   uint32_t* d_claim = nullptr; uint32_t* d_copy_fault = nullptr; uint8_t* d_mask_stale = nullptr;
   int32_t* d_copy_idx = nullptr; uint64_t* d_copy_seeds = nullptr;
+  int8_t* d_pol = nullptr;       // [6 n] staging of the host-array surface of the per-episode classes (cc4_set_policies: three [n] inputs; cc4_get_policies: two [n][3] outputs)
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   std::vector<hipEvent_t> evs;                   // timing events of cc4_run_random_steps: [group][2 * timed group of launches + {start, stop}]
   std::string err;

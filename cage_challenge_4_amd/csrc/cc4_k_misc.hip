@@ -166,6 +166,20 @@ __global__ __launch_bounds__(256) void k_policy_outputs(const EnvState* __restri
   }
 }
 
+// cc4_set_policies_device: one lane per episode, the rule of row_assign (cc4_state.h).  A refused value leaves the episode as it is and raises CF_RANGE.
+__global__ __launch_bounds__(256) void k_set_policies(EnvState* st, const int8_t* __restrict__ red, const int8_t* __restrict__ green, const int8_t* __restrict__ blue,
+                                                      int n, uint32_t* fault) {
+  const int e = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (e >= n) return;
+  if (!row_assign(st + e, red ? red[e] : PA_KEEP, green ? green[e] : PA_KEEP, blue ? blue[e] : PA_KEEP)) atomicOr(fault, (uint32_t)CF_RANGE);
+}
+// cc4_policies_device: live classes and assignment of every episode as [n][3] (row_policies); either output may be null
+__global__ __launch_bounds__(256) void k_get_policies(const EnvState* __restrict__ st, int8_t* __restrict__ live, int8_t* __restrict__ assigned, int n) {
+  const int e = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (e >= n) return;
+  row_policies(st + e, live ? live + 3 * (size_t)e : nullptr, assigned ? assigned + 3 * (size_t)e : nullptr);
+}
+
 // CybORG.set_seed (env.py:316-325) on every episode (episode_set_seed)
 __global__ void k_set_seed(EnvState* st, EnvCold* cold, size_t cold_row, const uint64_t* seeds, int n, int rng_mode) {
   int e = blockIdx.x * blockDim.x + threadIdx.x;

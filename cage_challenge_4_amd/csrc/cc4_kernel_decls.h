@@ -51,6 +51,9 @@ __global__ void k_copy_claim(CopyArgs a);
 __global__ void k_copy_episodes(CopyArgs a);
 // state features (cc4_k_feat.hip): one wavefront per requested episode or bank slot
 __global__ void k_state_features(FeatArgs a);
+// per-episode opponent classes (cc4_k_misc.hip): one lane per episode
+__global__ void k_set_policies(EnvState* st, const int8_t* __restrict__ red, const int8_t* __restrict__ green, const int8_t* __restrict__ blue, int n, uint32_t* fault);
+__global__ void k_get_policies(const EnvState* __restrict__ st, int8_t* __restrict__ live, int8_t* __restrict__ assigned, int n);
 __global__ void k_set_seed(EnvState* st, EnvCold* cold, size_t cold_row, const uint64_t* seeds, int n, int rng_mode);
 __global__ void k_set_rng_state(EnvState* st, const uint64_t* w, int n);
 __global__ void k_rng_state(const EnvState* st, uint64_t* out, int n);

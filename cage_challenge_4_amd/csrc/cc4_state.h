@@ -207,7 +207,9 @@ struct alignas(64) EnvState {
   uint8_t rng_split;                 // 1 after CybORG.set_seed: the agents' policies keep drawing from rng2 (see there)
   uint8_t obs_dirty;                 // this step changed a slowly varying part of the flat observation (OD_BLOCKS: a pair of the block matrix, OD_PHASE:
                                      // the mission phase): the lane-parallel kernels rewrite those values only then (the output buffer persists)
-  uint8_t pad0[2];
+  uint8_t assign;                    // the classes this episode regenerates into: 0 = the handle's configuration, else PA_SET | policy bits (below).  Read by
+                                     // reset_topology, kept by reset_zero, written only by row_assign: it takes effect at the next regeneration, never mid-episode
+  uint8_t pad0;
   uint16_t blocks[NSUB];             // blocks[to] bit from
   uint8_t cidr_octet[NSUB];
   uint8_t n_users[NSUB];
@@ -241,6 +243,41 @@ struct alignas(64) EnvState {
   alignas(64) HostDyn hd[MAXH];      // last member: the numpy-stream kernel stages only the part in front of it
 };
 static_assert(offsetof(EnvState, hd) % 64 == 0 && sizeof(EnvState) % 64 == 0 && sizeof(EnvState) == offsetof(EnvState, hd) + sizeof(HostDyn) * MAXH, "the host table closes the row; row and table are whole cache lines");
+
+// ---- the per-episode assignment of opponent classes (EnvState.assign; cc4_set_policies, cc4_row_set_policies).  An assignment is all three
+// classes or none: PA_SET | red class | GP_SLEEP_BIT | BP_RANDOM_BIT, the encoding of EnvState.policy (GP_OPEN_BIT belongs with cc4_step_ex and is
+// not assignable).  One definition for the device kernels, the host calls on a single row and the oracle.
+enum : int { PA_SET = 0x80, PA_BITS = 3 | GP_SLEEP_BIT | BP_RANDOM_BIT, PA_KEEP = -1 /* CC4_POLICY_KEEP */, PA_DEFAULT = -2 /* CC4_POLICY_DEFAULT */ };
+// the word of the row that holds `assign` and the byte's place in it: what reset_zero leaves standing
+static_assert(offsetof(EnvState, assign) % 4 == 2, "EnvState.assign is byte 2 of its word");
+enum : uint32_t { PA_WORD = (uint32_t)(offsetof(EnvState, assign) / 4), PA_WORD_MASK = 0x00FF0000u };
+// the classes a regeneration gives the episode: its assignment, else the caller's (the handle's configuration)
+CC4_HD int policy_at_reset(const EnvState* s, int handle_policy) { return (s->assign & PA_SET) ? (s->assign & PA_BITS) : handle_policy; }
+// One episode's assignment from (red, green, blue): a class, PA_KEEP or PA_DEFAULT each.  All PA_KEEP: nothing.  PA_DEFAULT (the others PA_DEFAULT or
+// PA_KEEP): no assignment.  Otherwise the classes given replace those of the assignment the episode has -- of its live classes if it has none.  False
+// and the row untouched: a value out of range (red 0..3, green and blue 0..1), or PA_DEFAULT beside a class.
+CC4_HD bool row_assign(EnvState* s, int red, int green, int blue) {
+  if (red < PA_DEFAULT || red > 3 || green < PA_DEFAULT || green > 1 || blue < PA_DEFAULT || blue > 1) return false;
+  const bool any_default = red == PA_DEFAULT || green == PA_DEFAULT || blue == PA_DEFAULT, any_class = red >= 0 || green >= 0 || blue >= 0;
+  if (any_default && any_class) return false;
+  if (any_default) { s->assign = 0; return true; }
+  if (!any_class) return true;
+  int b = ((s->assign & PA_SET) ? s->assign : s->policy) & PA_BITS;
+  if (red >= 0) b = (b & ~3) | red;
+  if (green >= 0) b = (b & ~GP_SLEEP_BIT) | (green ? GP_SLEEP_BIT : 0);
+  if (blue >= 0) b = (b & ~BP_RANDOM_BIT) | (blue ? BP_RANDOM_BIT : 0);
+  s->assign = (uint8_t)(PA_SET | b);
+  return true;
+}
+// the live classes and the assignment (PA_DEFAULT where none) of one episode as (red, green, blue); either pointer may be null
+CC4_HD void row_policies(const EnvState* s, int8_t* live, int8_t* assigned) {
+  if (live) { live[0] = (int8_t)(s->policy & 3); live[1] = (int8_t)((s->policy & GP_SLEEP_BIT) ? ((s->policy & GP_OPEN_BIT) ? 2 : 1) : 0); live[2] = (int8_t)((s->policy & BP_RANDOM_BIT) ? 1 : 0); }
+  if (assigned) {
+    const int a = s->assign;
+    const bool set = (a & PA_SET) != 0;
+    assigned[0] = (int8_t)(set ? (a & 3) : PA_DEFAULT); assigned[1] = (int8_t)(set ? ((a & GP_SLEEP_BIT) ? 1 : 0) : PA_DEFAULT); assigned[2] = (int8_t)(set ? ((a & BP_RANDOM_BIT) ? 1 : 0) : PA_DEFAULT);
+  }
+}
 
 // Work area of one step / one reset: temporaries the phases hand to each other.  Not part of the episode's state (LDS on the
 // device, the caller's stack on the host); everything in it is dead between steps.

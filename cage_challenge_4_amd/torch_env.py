@@ -49,6 +49,12 @@ class CC4TorchVecEnv:
     The privileged global state for a centralised critic (include/cc4.h cc4_state_features_device; cage_challenge_4_amd.state_features):
     state_features(ids=None, bank=None, out=None) -> (hosts [n, 137, 16] uint8, glob [n, 32] int32)   of the env's episodes, or of the slots of a bank
 
+    Mixed opponents in one batch (include/cc4.h cc4_set_policies_device, cc4_reset_device):
+    set_opponents(red=None, green=None, blue=None)   integer tensors [N] on the device: the classes each episode regenerates into from its next
+                                                     regeneration on (never mid-episode); None keeps
+    opponents()                                      -> (live, assigned) two [N, 3] int8 tensors (red, green, blue)
+    reset(seeds=tensor, env_mask=tensor)             seeds any integer dtype, env_mask bool or uint8 (env.reset(env_mask=env.done)): no host wait
+
     No call synchronises except check_errors(), which reads the error flags and raises what CC4VecEnv raises (ValueError for a step past
     the episode's end -- the reference's own error -- and CC4EngineError for any other flag; strict=False: the ValueError only), and raises
     CC4EngineError for the faults of the copies and state_features calls since the last call."""
@@ -88,7 +94,39 @@ class CC4TorchVecEnv:
             self.venv._chk(rc, 'cc4_policy_outputs')
         self.venv._chk(lib.cc4_stream_signal(h, s), 'cc4_stream_signal')
 
+    def _reset_device(self, seeds, env_mask):
+        """reset() from device tensors (cc4_reset_device): no upload, no host wait.  A NumPy array or scalar beside a tensor is moved to the device."""
+        n = self.num_envs
+        with torch.cuda.device(self.device):
+            s = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            sp = mp = None
+            if seeds is not None:           # (casts and uploads on s; the allocator keeps the temporaries on s, which cc4_stream_signal orders behind their reader)
+                if not torch.is_tensor(seeds):
+                    seeds = np.uint64(seeds) + np.arange(n, dtype=np.uint64) if np.isscalar(seeds) else np.ascontiguousarray(seeds, dtype=np.uint64)
+                    seeds = torch.from_numpy(seeds.view(np.int64)).to(self.device)
+                if tuple(seeds.shape) != (n,) or seeds.dtype.is_floating_point or seeds.dtype == torch.bool or seeds.device != self.device:
+                    raise ValueError(f'seeds must be an integer tensor [{n}] on {self.device}')
+                seeds = (seeds.view(torch.int64) if seeds.dtype == torch.uint64 else seeds.to(torch.int64)).contiguous()
+                sp = ctypes.c_void_p(seeds.data_ptr())
+            if env_mask is not None:
+                if not torch.is_tensor(env_mask):
+                    env_mask = torch.from_numpy(np.ascontiguousarray(env_mask, dtype=np.uint8)).to(self.device)
+                if tuple(env_mask.shape) != (n,) or env_mask.dtype not in (torch.bool, torch.uint8) or env_mask.device != self.device:
+                    raise ValueError(f'env_mask must be a bool or uint8 tensor [{n}] on {self.device}')
+                env_mask = env_mask.to(torch.uint8).contiguous()        # (a bool tensor -- this object's own `done`, which the reset's outputs rewrite -- is copied)
+                mp = ctypes.c_void_p(env_mask.data_ptr())
+            rc = self.lib.cc4_stream_wait(self._h, s) or self.lib.cc4_reset_device(self._h, sp, mp)
+            if rc:
+                self.venv._chk(rc, 'cc4_reset_device')
+            self._outputs(s)
+        return self.obs, self._info()
+
     def reset(self, seeds=None, env_mask=None):
+        """seeds / env_mask as CC4VecEnv.reset (NumPy arrays, a scalar, None: cc4_reset, which waits for the device) -- or tensors on the env's
+        device (seeds any integer dtype, env_mask bool or uint8, e.g. env.reset(env_mask=env.done)): cc4_reset_device on the current stream, no
+        host wait."""
+        if torch.is_tensor(seeds) or torch.is_tensor(env_mask):
+            return self._reset_device(seeds, env_mask)
         with torch.cuda.device(self.device):
             s = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
             # the reset rewrites rows the last step's kernels may still read, and the outputs go into tensors the caller's stream may
@@ -248,6 +286,42 @@ class CC4TorchVecEnv:
                 self.venv._chk(rc, 'cc4_state_features_device')
             self.venv._chk(lib.cc4_stream_signal(h, sp), 'cc4_stream_signal')
         return hosts, glob
+
+    def set_opponents(self, red=None, green=None, blue=None):
+        """Assign opponent classes per episode from the device (cc4_set_policies_device, include/cc4.h): red (0..3), green (0..1), blue (0..1) each
+        an integer tensor [N] on the env's device or None (keep); an entry may be L.POLICY_KEEP or L.POLICY_DEFAULT.  Takes effect at each
+        episode's next regeneration (reset, autoreset), never mid-episode.  On the current stream, no host wait; a refused entry (a class out of
+        range) leaves its episode as it was, and check_errors() raises CC4EngineError for it."""
+        n = self.num_envs
+        with torch.cuda.device(self.device):
+            s = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            ptrs, keep = [], []
+            for x, what in ((red, 'red'), (green, 'green'), (blue, 'blue')):
+                if x is None:
+                    ptrs.append(None)
+                    continue
+                if not torch.is_tensor(x) or tuple(x.shape) != (n,) or x.dtype.is_floating_point or x.dtype == torch.bool or x.device != self.device:
+                    raise ValueError(f'{what} must be an integer tensor [{n}] on {self.device}')
+                x = x.clamp(-128, 127).to(torch.int8).contiguous()      # (a value beyond int8 stays out of range instead of wrapping into it)
+                keep.append(x)
+                ptrs.append(ctypes.c_void_p(x.data_ptr()))
+            rc = self.lib.cc4_stream_wait(self._h, s) or self.lib.cc4_set_policies_device(self._h, *ptrs)
+            if rc:
+                self.venv._chk(rc, 'cc4_set_policies_device')
+            self.venv._chk(self.lib.cc4_stream_signal(self._h, s), 'cc4_stream_signal')
+
+    def opponents(self):
+        """(live, assigned): two fresh [N, 3] int8 tensors of (red, green, blue) classes -- what every episode runs now, and what it regenerates
+        into (L.POLICY_DEFAULT where it carries no assignment).  On the current stream, no host wait."""
+        with torch.cuda.device(self.device):
+            s = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            live = torch.empty((self.num_envs, 3), dtype=torch.int8, device=self.device)
+            assigned = torch.empty((self.num_envs, 3), dtype=torch.int8, device=self.device)
+            rc = self.lib.cc4_stream_wait(self._h, s) or self.lib.cc4_policies_device(self._h, ctypes.c_void_p(live.data_ptr()), ctypes.c_void_p(assigned.data_ptr()))
+            if rc:
+                self.venv._chk(rc, 'cc4_policies_device')
+            self.venv._chk(self.lib.cc4_stream_signal(self._h, s), 'cc4_stream_signal')
+        return live, assigned
 
     def check_errors(self):
         """The one synchronising call: reads the error flags of the last step / reset and raises what CC4VecEnv.step would have raised

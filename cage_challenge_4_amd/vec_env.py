@@ -67,6 +67,7 @@ class CC4VecEnv:
                  topology_seed=0, strict=True, blue_policy=0):
         """topology_seed != 0 (RNG_PHILOX only): all episodes share the scenario drawn from that key (uniform topology).
         blue_policy 1: cc4BlueRandomAgent acts for every blue agent whose action index is negative (0: such an agent sleeps).
+        red_policy / green_policy / blue_policy may be [N] arrays: a class per episode (set_policies), in place from the first reset on.
         strict: raise (ValueError for a step past the episode's end, as the reference does; CC4EngineError otherwise) as soon as
         any episode carries an error flag.  strict=False leaves the flags to the caller (`err`, `info['err']`)."""
         self.strict = bool(strict)
@@ -74,6 +75,14 @@ class CC4VecEnv:
         self.num_envs = int(num_envs)
         self.steps = int(steps)
         self._dev = int(device_id)
+        # per-episode classes ([N] arrays): the handle is created with class 0 for them, and they are assigned before the first reset
+        per_episode = {k: np.asarray(v) for k, v in (('red', red_policy), ('green', green_policy), ('blue', blue_policy)) if np.ndim(v) > 0}
+        if per_episode:
+            red_policy, green_policy, blue_policy = (0 if np.ndim(v) > 0 else v for v in (red_policy, green_policy, blue_policy))
+            if int(green_policy) == 2:
+                raise ValueError('green_policy 2 (the caller submits the green actions) cannot be combined with per-episode classes')
+            # (an assignment is all three classes: the scalar ones are assigned to every episode beside the arrays)
+            per_episode = {k: per_episode.get(k, v) for k, v in (('red', red_policy), ('green', green_policy), ('blue', blue_policy))}
         cfg = L.CC4Config(self.num_envs, self.steps, int(device_id), int(rng_mode), int(bool(autoreset)),
                           int(red_policy), int(green_policy), int(topology_seed), int(blue_policy))
         h = ctypes.c_void_p()
@@ -94,6 +103,12 @@ class CC4VecEnv:
         self._any_seen = False
         vp = ctypes.c_void_p
         self._p_out = (self._obs.ctypes.data_as(vp), self._rew.ctypes.data_as(vp), self._done.ctypes.data_as(vp), self._err.ctypes.data_as(vp))
+        if per_episode:
+            try:
+                self.set_policies(**per_episode)
+            except Exception:
+                self.close()
+                raise
 
     # -- lifecycle
     def close(self):
@@ -126,6 +141,38 @@ class CC4VecEnv:
             mp = env_mask.ctypes.data_as(ctypes.c_void_p)
         self._chk(self.lib.cc4_reset(self._h, sp, mp), 'cc4_reset')
         return self._fetch(mask=True)[0]
+
+    def _policy_array(self, v, name):
+        if v is None:
+            return None
+        a = np.asarray(v)
+        if a.ndim == 0:
+            a = np.full(self.num_envs, a)
+        if a.shape != (self.num_envs,):
+            raise ValueError(f'{name} must be a scalar or an array of {self.num_envs} classes')
+        if ((a < -128) | (a > 127)).any():
+            raise ValueError(f'{name}: class out of range')
+        return np.ascontiguousarray(a, dtype=np.int8)
+
+    def set_policies(self, red=None, green=None, blue=None):
+        """Assign opponent classes per episode (cc4_set_policies, include/cc4.h): each of red (0..3), green (0..1), blue (0..1) a scalar or an [N]
+        array, None = keep; an entry may be L.POLICY_KEEP or L.POLICY_DEFAULT (back to the handle's configuration).  An assignment takes effect
+        at the episode's next regeneration (reset, autoreset), never mid-episode.  Refused entries (a class out of range) leave their
+        episodes as they were and raise CC4EngineError after the others applied."""
+        arrs = [self._policy_array(v, k) for k, v in (('red', red), ('green', green), ('blue', blue))]
+        ptrs = [None if a is None else a.ctypes.data_as(ctypes.c_void_p) for a in arrs]
+        self._chk(self.lib.cc4_set_policies(self._h, *ptrs), 'cc4_set_policies')
+        faults = ctypes.c_uint32(0)
+        self._chk(self.lib.cc4_copy_faults(self._h, ctypes.byref(faults)), 'cc4_copy_faults')
+        raise_on_copy_faults(faults.value)
+
+    def policies(self):
+        """(live, assigned): two [N, 3] int8 arrays of (red, green, blue) classes -- what every episode runs now, and what it regenerates
+        into (L.POLICY_DEFAULT where it carries no assignment: the handle's configuration)."""
+        live = np.zeros((self.num_envs, 3), np.int8)
+        assigned = np.zeros((self.num_envs, 3), np.int8)
+        self._chk(self.lib.cc4_get_policies(self._h, live.ctypes.data_as(ctypes.c_void_p), assigned.ctypes.data_as(ctypes.c_void_p)), 'cc4_get_policies')
+        return live, assigned
 
     def step(self, actions=None, messages=None):
         """actions: int array [N,5] of wrapper indices (None / negative = no action -> Sleep)."""
