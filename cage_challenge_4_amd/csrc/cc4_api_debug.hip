@@ -104,6 +104,12 @@ int cc4_debug_copy_from_device(cc4_handle* h, void* host_dst, const void* device
   HIPCHK(h, hipMemcpy(host_dst, device_src, bytes, hipMemcpyDeviceToHost));
   return 0;
 }
+// test hook: the self-check's shadow handle, NULL where the handle has none (tests/handover_util.py reads the shadow's side of a checked call through it)
+int cc4_debug_shadow_handle(cc4_handle* h, cc4_handle** out) {
+  if (!h || !out) return -2;
+  *out = h->shadow;
+  return 0;
+}
 // debug / test hook: every all-gather is preceded by a kernel that keeps the communication stream busy for about `us`
 // microseconds -- an exchange slower than the step, which is what makes the observation ring's reuse guard work for its living
 int cc4_debug_comm_delay_us(cc4_handle* h, int us) {

@@ -33,6 +33,10 @@ int cc4_debug_persist_base(cc4_handle* h, uint32_t base);
 /* test hook: `bytes` bytes of device memory of this handle's device -- e.g. an action slot of a rollout (cc4_rollout_actions), packed observation rows
  * (cc4_rollout_obs_packed) -- copied to the host, behind everything enqueued on the handle's streams. */
 int cc4_debug_copy_from_device(cc4_handle* h, void* host_dst, const void* device_src, size_t bytes);
+/* test hook: the self-check's shadow handle (CC4_PERSIST_VERIFY / CC4_PERSIST_VERIFY_EVERY: created with the handle's first persistent call), NULL where
+ * there is none.  It stays the handle's own: the read-only getters (cc4_get_states, cc4_get_rng_state, cc4_get_err, cc4_fetch, cc4_get_cold) give the
+ * shadow's side of the last checked call; it is never stepped, reset or destroyed through this pointer. */
+int cc4_debug_shadow_handle(cc4_handle* h, cc4_handle** out);
 
 #ifdef __cplusplus
 }
