@@ -670,8 +670,10 @@ int cc4_edit_state(cc4_handle* h, int32_t env, int32_t op, int32_t a0, int32_t a
     StepWork w; memset(&w, 0, sizeof(w));
     Ctx x{st, cold, &st->rng, st->hd, &w};
     rc = state_edit(x, op, a0, a1, a2);
-    if (rc < 0) { h->err = "cc4_edit_state: unknown op or bad argument"; rc = -2; }
-    else { int r2 = cc4_set_state(h, env, st); if (r2 == 0) r2 = cc4_set_cold(h, env, cold); if (r2) rc = r2; }
+    // -1: an unknown op or a bad argument (the row is as it was), or an op a full container refused -- that one has raised its flag in
+    // EnvState.err and may have left a process and a pid draw behind, so the row goes back in either case
+    if (rc < 0) h->err = "cc4_edit_state: unknown op, bad argument, or refused by a full container (see the episode's error flags)";
+    int r2 = cc4_set_state(h, env, st); if (r2 == 0) r2 = cc4_set_cold(h, env, cold); if (r2) rc = r2;
   }
   free(st); free(cold);
   return rc;

@@ -1813,9 +1813,12 @@ CC4_HD void red_session_check(Ctx x, int r) {
     }
     A.h.as_subnet |= (uint16_t)sub;
   }
-  // session ids new to the ActionSpace, in session order: eight records and their eight known-id words per round, so the
-  // common case (everything known) costs two LDS round trips per eight sessions
+  // session ids new to the ActionSpace: eight records and their eight known-id words per round, so the common case (everything
+  // known) costs two LDS round trips per eight sessions.  One new id (nearly always) is appended as it is found.  Several: the
+  // observation is keyed by hostname, so ActionSpace.update meets the sessions host by host -- hosts in the order of their first
+  // entry in the agent's list, a host's sessions in list order (RedSessionCheck.py:58-65, Observation.add_session_info).
   const int n = A.h.nsess;
+  int fresh = 0, fresh_id = 0;
   for (int i0 = 0; i0 < n; i0 += 8) {
     const S8 q = rs_load8(s, A, i0);
     uint32_t kw[8];
@@ -1824,9 +1827,21 @@ CC4_HD void red_session_check(Ctx x, int r) {
       if (i0 + k >= n || !(rsw_flags(q.v[k]) & RS_ABSTRACT)) continue;
       const int id = rsw_id(q.v[k]);
       if (id < 256 && ((kw[k] >> (id & 31)) & 1u)) continue;
-      as_know_sid(x, r, id);   // rare; two new records of one round never share an id, so the words read above stay valid
+      fresh++; fresh_id = id;   // (an id >= 256 counts whether known or not: as_know_sid sorts that out)
     }
   }
+  if (fresh == 1) as_know_sid(x, r, fresh_id);
+  else if (fresh > 1)
+    for (int i = 0; i < n; ++i) {
+      const int h = rsw_host(rs_at(s, A, i));
+      bool first = true;
+      for (int j = 0; j < i && first; ++j) first = rsw_host(rs_at(s, A, j)) != h;
+      if (!first) continue;
+      for (int j = i; j < n; ++j) {
+        const uint64_t w = rs_at(s, A, j);
+        if (rsw_host(w) == h && (rsw_flags(w) & RS_ABSTRACT)) as_know_sid(x, r, rsw_id(w));   // a known id: nothing
+      }
+    }
   A.h.rsc_dirty = 0;
 }
 // Withdraw.execute (ConcreteActions/Withdraw.py:38-91) + StopProcess(stop_all=True).  a.host = ip_address (unused beyond the
@@ -2814,12 +2829,14 @@ inline int state_edit(Ctx x, int op, int a0, int a1, int a2) {
       HostDyn& d = x.hd[a0];
       const int nsv = hd_nsvc(d);
       int si = -1;
-      for (int i = nsv - 1; i >= 0; --i) if (d.svcs[i].kind == a1) si = i;   // add_service on an existing name replaces the entry
+      for (int i = nsv - 1; i >= 0; --i) if (d.svcs[i].kind == a1) si = i;   // add_service keeps the entry of an existing name (Host.py:302-308)
       if (si < 0 && nsv >= MAXSV) return -1;
       const int pid = create_pid(x, a0);
       if (!add_proc(x, a0, pid, K_PLAIN, a2 ? PF_ROOT : 0)) return -1;   // Process(pid=pid, process_name=...): no open_ports
-      if (si < 0) { si = nsv; hd_set_nsvc(d, nsv + 1); }
-      d.svcs[si].kind = (uint8_t)a1; d.svcs[si].pid = (uint16_t)pid; d.svcs[si].st = (uint8_t)(SV_ACTIVE | 5);
+      if (si < 0) {
+        si = nsv; hd_set_nsvc(d, nsv + 1);
+        d.svcs[si].kind = (uint8_t)a1; d.svcs[si].pid = (uint16_t)pid; d.svcs[si].st = (uint8_t)(SV_ACTIVE | 5);
+      }
       return pid;
     }
     case SE_SET_RELIABILITY: {

@@ -336,9 +336,34 @@ int cc4o_layout(char* buf, int cap) {
 #define G(m) n += snprintf(buf + n, cap - n, "red." #m " %zu\n", offsetof(RedAgent, h) + offsetof(RedHdr, m))
   G(queue); G(as_subnet); G(fsm_step); G(nsess); G(nknown); G(fsm_n); G(nobs); G(active); G(obs_success); G(exec_type); G(new_sess_host); G(new_sess_id); G(start_host);
 #undef G
-  n += snprintf(buf + n, cap - n, "sizeof.RedAgent %zu\nsizeof.BlueAgent %zu\nsizeof.HostDyn %zu\nsizeof.HostStatic %zu\nsizeof.EnvState %zu\n",
-                sizeof(RedAgent), sizeof(BlueAgent), sizeof(HostDyn), sizeof(HostStatic), sizeof(EnvState));
+#define G(m) n += snprintf(buf + n, cap - n, "blue." #m " %zu\n", offsetof(BlueAgent, m))
+  G(sus_hosts); G(queue); G(nsus); G(parent_host);
+#undef G
+#define G(m) n += snprintf(buf + n, cap - n, "hd." #m " %zu\n", offsetof(HostDyn, m))
+  G(procs); G(svcs); G(nproc); G(nsf);
+#undef G
+#define G(m) n += snprintf(buf + n, cap - n, "rsess." #m " %zu\n", offsetof(RSess, m))
+  G(id); G(pid); G(host); G(flags);
+#undef G
+  // the cold row: the fixed part's members, then where the two steps-sized containers begin (sus[b] and povf[h] are
+  // cold_sus_cap(steps) / cold_povf_cap(steps) words apart: cc4o_caps)
+#define G(m) n += snprintf(buf + n, cap - n, "cold." #m " %zu\n", offsetof(EnvCold, m))
+  G(hs); G(eph); G(evlog); G(kports); G(xrate); G(gfail); G(known_sid); G(rng2);
+#undef G
+  n += snprintf(buf + n, cap - n, "cold.sus %zu\n", sizeof(EnvCold));
+  n += snprintf(buf + n, cap - n, "sizeof.RedAgent %zu\nsizeof.BlueAgent %zu\nsizeof.HostDyn %zu\nsizeof.HostStatic %zu\nsizeof.EnvState %zu\nsizeof.RSess %zu\nsizeof.EnvCold %zu\n",
+                sizeof(RedAgent), sizeof(BlueAgent), sizeof(HostDyn), sizeof(HostStatic), sizeof(EnvState), sizeof(RSess), sizeof(EnvCold));
   return n;
+}
+// the capacities of the bounded containers (csrc/cc4_state.h) for episodes of `steps` steps, and the flags their overflows raise:
+// out[0..8] = PIN, cold_povf_cap, cold_sus_cap, MAX_RS, RS_POOL, MAX_KS, MAX_OBS, MAX_PEND, byte offset of povf[0] in the cold row;
+// out[9..14] = E_PROC_OVERFLOW, E_RSESS_OVERFLOW, E_KS_OVERFLOW, E_SUS_OVERFLOW, E_OBS_OVERFLOW, E_PEND_OVERFLOW; out[15] = the cold row's bytes
+void cc4o_caps(int steps, uint32_t* out /* [16] */) {
+  out[0] = PIN; out[1] = (uint32_t)cold_povf_cap(steps); out[2] = (uint32_t)cold_sus_cap(steps); out[3] = MAX_RS; out[4] = RS_POOL;
+  out[5] = MAX_KS; out[6] = MAX_OBS; out[7] = MAX_PEND;
+  out[8] = (uint32_t)(sizeof(EnvCold) + 4u * (size_t)NBLUE * (size_t)cold_sus_cap(steps));
+  out[9] = E_PROC_OVERFLOW; out[10] = E_RSESS_OVERFLOW; out[11] = E_KS_OVERFLOW; out[12] = E_SUS_OVERFLOW; out[13] = E_OBS_OVERFLOW; out[14] = E_PEND_OVERFLOW;
+  out[15] = (uint32_t)cold_row_bytes(steps);
 }
 
 // canonical text dump of one episode's state (parity bisecting against oracle/refgen/ref_dump.py)

@@ -12,6 +12,9 @@ engine's terms (cc4_step_ex records, cc4_edit_state ops).  The oracle replays th
 fixture that the restatement cannot reproduce is reported here, not later.  tests/test_scripted.py replays the fixtures on the
 oracle (CPU) and on all three HIP step kernels (GPU).
 
+The "capacity" family at the end is no restatement of a test of the reference: its scripts leave a bounded container of the engine exactly
+full -- the reference's lists are unbounded, so it is a valid witness up to there and not beyond -- and fail here if the oracle raises a flag.
+
 Where a test pokes something the engine has no notion of (a Process named after the agent, a service keyed by a bare string) the
 re-expression uses the canonical object of the same meaning (ProcessName.OTSERVICE, as test_Impact.py:89-101 does); where a test
 calls action.execute(state) directly, the action goes through a step instead (SleepAgents everywhere: nothing else happens in it).
@@ -60,8 +63,9 @@ def sha(txt):
 
 class Case:
     """One environment: the reference and the oracle in lockstep; everything done to them is recorded."""
-    def __init__(self, seed, steps=100, red='sleep', green='sleep', resets=0, note='', slim=False):
+    def __init__(self, seed, steps=100, red='sleep', green='sleep', resets=0, note='', slim=False, no_err=False):
         self.slim = slim                       # long trajectories: a digest of the flat observation instead of its 578 digits
+        self.no_err = no_err                   # also after every edit: the oracle's err word is zero (the step asserts it anyway)
         sg = EnterpriseScenarioGenerator(blue_agent_class=SleepAgent, green_agent_class=GREEN[green][0], red_agent_class=RED[red][0], steps=steps)
         self.pol = RED[red][1] | (0x10 if GREEN[green][1] else 0)
         self.env = CybORG(sg, seed=seed)
@@ -120,6 +124,8 @@ class Case:
         ref_fn()
         rc = lib.cc4o_edit_state(self.H, 0, op, a0, a1, a2)
         assert rc >= 0, (op, a0, a1, a2)
+        if self.no_err:      # the capacity family: the reference has no caps, so a script that trips one of the engine's is not a fixture
+            assert lib.cc4o_err(self.H, 0) == 0, ('err', lib.cc4o_err(self.H, 0), op, a0, a1, a2)
         ref = self._check(f'edit {op}')
         self.rec['script'].append({'edit': [op, a0, a1, a2], 'rc': rc, 'dump': sha(ref), 'rng': self._rng()})
         return rc
@@ -173,6 +179,24 @@ class Case:
             out['ident'] = sess.ident
         rc = self.edit(5, int(agent[-1]), host_index(hostname), 1 | 4, fn)
         assert rc == out['ident'], (rc, out)
+        return rc
+
+    def add_session(self, agent, hostname, root=False, abstract=False, child=False):
+        """state.add_session of a plain shell Session or a RedAbstractSession with ident = None (State.add_session picks max + 1);
+        child: parent = the agent's session 0, where it has one.  Returns the ident."""
+        out = {}
+
+        def fn():
+            from CybORG.Shared.Session import RedAbstractSession
+            parent = 0 if (child and 0 in self.st.sessions[agent]) else None
+            out['child'] = parent is not None
+            kw = dict(hostname=hostname, username='root' if root else 'user', agent=agent, parent=parent, ident=None, pid=None)
+            sess = RedAbstractSession(session_type='RedAbstractSession', **kw) if abstract else Session(session_type='shell', **kw)
+            self.st.add_session(sess)
+            out['ident'] = sess.ident
+        child = bool(child and 0 in self.st.sessions[agent])
+        rc = self.edit(5, int(agent[-1]), host_index(hostname), (1 if root else 0) | (2 if child else 0) | (4 if abstract else 0), fn)
+        assert rc == out['ident'] and child == out['child'], (rc, out)
         return rc
 
     def block(self, to_subnet, from_subnet):
@@ -926,6 +950,232 @@ def _():
                 agent = f'blue_agent_{b}'
                 assert list(c.st.sessions[agent].keys()) == [k for k, v in c.ec.agent_interfaces[agent].action_space.client_session.items() if v]
         yield c
+
+
+# ------------------------------------------------------------------------------------------------ capacity: the engine's bounded containers exactly full
+# The reference's lists are unbounded, so it is a valid witness for any state that is exactly full and not beyond.  These scripts fill a container
+# of the engine to its capacity (cc4o_caps: no cap is a literal here) with the ops above and then run the operations that read and compact it; the
+# oracle's err word must stay zero at every entry (Case(no_err=True)).  SleepAgents everywhere: nothing else happens in a step.  RedSessionCheck is
+# not an action of the step's dict here -- the controller runs it for every active red agent at the end of every step.
+RZA, OZA, OFF = 'restricted_zone_a_subnet', 'operational_zone_a_subnet', 'office_network_subnet'
+RED_ZONES = [['contractor_network_subnet'], [RZA], [OZA], ['restricted_zone_b_subnet'], ['operational_zone_b_subnet'],
+             ['public_access_zone_subnet', 'admin_network_subnet', OFF]]
+
+
+def caps(steps):
+    out = (ctypes.c_uint32 * 16)()
+    lib.cc4o_caps(int(steps), out)
+    return dict(zip(('PIN', 'povf', 'sus', 'MAX_RS', 'RS_POOL', 'MAX_KS', 'MAX_OBS', 'MAX_PEND'), [int(v) for v in out[:8]]))
+
+
+def plain_hosts(c, subnet):
+    return sorted((h for h in c.st.hosts if h.startswith(subnet + '_') and 'router' not in h), key=host_index)
+
+
+def red(r):
+    return f'red_agent_{r}'
+
+
+def nsess(c, agent):
+    return len(c.st.sessions[agent])
+
+
+def fill_sessions(c, agent, hosts, total, crowded=(), per_crowded=0):
+    """Hand-made sessions until the agent holds `total`: abstract and shell, root and user, with and without a parent, round-robin over `hosts`;
+    every fifth one goes to a crowded host until each of those holds per_crowded."""
+    on = {h: 0 for h in crowded}
+    j = 0
+    while nsess(c, agent) < total:
+        left = total - nsess(c, agent)
+        need = [h for h in crowded if on[h] < per_crowded]
+        if need and (j % 5 == 0 or left <= sum(per_crowded - on[h] for h in need)):
+            hn = need[0]
+            on[hn] += 1
+        else:
+            hn = hosts[j % len(hosts)]
+        c.add_session(agent, hn, root=(j % 4 == 1), abstract=(j % 3 != 0), child=(j % 5 == 2))
+        j += 1
+    c.set_red_active(agent, True)
+    assert nsess(c, agent) == total and all(v == per_crowded for v in on.values()), (agent, nsess(c, agent), on)
+
+
+def exploit_from_cns0(c, hostname, tries=6):
+    """red_agent_0 (root shell on CNS0) exploits `hostname` until a session comes of it (the controller hands it to the zone's agent at the end of
+    the step).  Returns the number of sessions red agents hold on the host afterwards."""
+    tip = c.ip(hostname)
+    o = c.step({RED0: AggressiveServiceDiscovery(session=0, agent=RED0, ip_address=tip)})
+    assert o[RED0]['success'] == True             # noqa: E712
+    for _ in range(tries):
+        o = c.step({RED0: one(ExploitRemoteService(ip_address=tip, session=0, agent=RED0), 1)})
+        if o[RED0]['success'] == True:            # noqa: E712
+            return
+    raise SystemExit(f'no exploit of {hostname} succeeded')
+
+
+def list_entry(c, agent, idx):
+    ident = list(c.st.sessions[agent].keys())[idx]
+    return ident, c.st.sessions[agent][ident]
+
+
+@fixture('capacity_session_list', 'capacity family (no test of the reference: its lists are unbounded): red_agent_1 holds exactly MAX_RS sessions, 62 made by hand (state.add_session as '
+         'test_Red/test_Withdraw.py:10-17 and test_Acceptance/test_priority.py:172-176 do) and two from red_agent_0\'s exploits handed over at the end of the step; then PrivilegeEscalate / '
+         'Impact naming the last list entry, Remove and Restore on a host with 11 of them, Withdraw from a host with 9')
+def _():
+    cp = caps(100)
+    c = Case(301, steps=100, slim=True, no_err=True, note=f'MAX_RS {cp["MAX_RS"]}')
+    hosts = plain_hosts(c, RZA)
+    th, h2 = TH, [h for h in hosts if h != TH][-1]
+    others = [h for h in hosts if h not in (th, h2)]
+    c.add_ot_service(th, root=True)
+    root_shell_on_cns0(c)
+    fill_sessions(c, RED1, others, cp['MAX_RS'] - 2, crowded=(th, h2), per_crowded=9)
+    c.step({})                                                    # RedSessionCheck of a 62-entry list
+    for k in (2, 1):                                              # entries 62 and 63: exploits of red_agent_0, reassigned into the nearly full agent
+        exploit_from_cns0(c, th)
+        assert nsess(c, RED1) == cp['MAX_RS'] - k + 1, nsess(c, RED1)
+    assert nsess(c, RED1) == cp['MAX_RS'], [nsess(c, red(r)) for r in range(6)]
+    c.step({})                                                    # RedSessionCheck of the full list
+    ident, last = list_entry(c, RED1, cp['MAX_RS'] - 1)
+    assert last.hostname == th and last.username == 'user'
+    c.step({RED1: one(PrivilegeEscalate(hostname=th, session=ident, agent=RED1), 1)}, skip_valid=True)
+    ident, last = list_entry(c, RED1, nsess(c, RED1) - 1)
+    c.step({RED1: one(Impact(hostname=th, session=ident, agent=RED1), 1)}, skip_valid=True)
+    n0 = nsess(c, RED1)
+    c.step({BLUE0: one(Remove(session=0, agent=BLUE0, hostname=th), 1)})        # the suspicious pids: the exploits' shells at the list's end
+    assert nsess(c, RED1) < n0, (n0, nsess(c, RED1))
+    fill_sessions(c, RED1, others, cp['MAX_RS'])                  # back to full
+    c.step({RED1: Withdraw(session=list_entry(c, RED1, 0)[0], agent=RED1, ip_address=c.ip(others[0]), hostname=h2)}, skip_valid=True)
+    assert nsess(c, RED1) == cp['MAX_RS'] - 9, nsess(c, RED1)
+    fill_sessions(c, RED1, others, cp['MAX_RS'])
+    n0 = nsess(c, RED1)
+    c.step({BLUE0: one(Restore(session=0, agent=BLUE0, hostname=th), 1)})       # every session on the host goes: entries of several rounds
+    assert nsess(c, RED1) <= n0 - 9, (n0, nsess(c, RED1))
+    fill_sessions(c, RED1, others, cp['MAX_RS'])
+    for _ in range(3):
+        c.step({})
+    yield c
+
+
+@fixture('capacity_session_pool', 'capacity family: all RS_POOL session records live, 32 per red agent in its own zone; Withdraw and Restore free records, hand-made sessions and an '
+         'exploit take them again (the engine hands out the lowest free record; the reference has no pool: what is pinned is that nothing else changes)')
+def _():
+    cp = caps(100)
+    c = Case(302, steps=100, slim=True, no_err=True, note=f'RS_POOL {cp["RS_POOL"]}')
+    per = cp['RS_POOL'] // 6
+    assert per * 6 == cp['RS_POOL'] and per <= cp['MAX_RS']
+    root_shell_on_cns0(c)
+    zone_hosts = [[h for sn in z for h in plain_hosts(c, sn)] for z in RED_ZONES]
+    for r in range(6):
+        crowd = (zone_hosts[r][-1],) if r else ()
+        fill_sessions(c, red(r), [h for h in zone_hosts[r] if h not in crowd], per, crowded=crowd, per_crowded=9)
+    total = lambda: sum(nsess(c, red(r)) for r in range(6))                       # noqa: E731
+    assert total() == cp['RS_POOL']
+    c.step({})
+    c.step({})
+    # red_agent_2 leaves its crowded host (9 records free), red_agent_4's crowded host is restored (9 more)
+    c.step({red(2): Withdraw(session=list_entry(c, red(2), 0)[0], agent=red(2), ip_address=c.ip(zone_hosts[2][0]), hostname=zone_hosts[2][-1])}, skip_valid=True)
+    c.step({'blue_agent_3': one(Restore(session=0, agent='blue_agent_3', hostname=zone_hosts[4][-1]), 1)})
+    assert total() == cp['RS_POOL'] - 18, total()
+    fill_sessions(c, red(5), zone_hosts[5][:-1], per + 10)                        # ten of the freed records, lowest first
+    fill_sessions(c, red(1), zone_hosts[1][:-1], per + 7)
+    exploit_from_cns0(c, TH)                                                      # the last free record: the exploit's session, handed to red_agent_1
+    assert total() == cp['RS_POOL'], total()
+    c.step({BLUE0: one(Remove(session=0, agent=BLUE0, hostname=TH), 1)})
+    assert total() == cp['RS_POOL'] - 1, total()
+    fill_sessions(c, red(3), zone_hosts[3][:-1], per + 1)
+    for _ in range(3):
+        c.step({})
+    assert total() == cp['RS_POOL']
+    yield c
+
+
+@fixture('capacity_foreign_sessions', 'capacity family: sessions of red_agent_0 on hosts outside its allowed subnet (state.add_session by hand), so that '
+         'different_subnet_agent_reassignment (SimulationController.py:820-903) moves 40 of them in one step into two agents, one of which ends at exactly MAX_RS')
+def _():
+    cp = caps(100)
+    c = Case(303, steps=100, slim=True, no_err=True, note=f'MAX_RS {cp["MAX_RS"]}')
+    rza, oza, con = plain_hosts(c, RZA), plain_hosts(c, OZA), plain_hosts(c, 'contractor_network_subnet')
+    fill_sessions(c, RED1, rza, cp['MAX_RS'] - 25, crowded=(rza[0],), per_crowded=9)
+    fill_sessions(c, red(2), oza, 11)
+    c.step({})
+    j = 0
+    for hn, k in ((rza, 25), (oza, 15), (con, 8)):                                 # interleaved with sessions that stay
+        for i in range(k):
+            c.add_session(RED0, hn[(i + j) % len(hn)], root=(i % 3 == 0), abstract=(i % 2 == 0), child=(i % 4 == 3))
+        j += 1
+    assert nsess(c, RED0) == 49
+    c.step({})
+    assert (nsess(c, RED0), nsess(c, RED1), nsess(c, red(2))) == (9, cp['MAX_RS'], 26), [nsess(c, red(r)) for r in range(3)]
+    c.step({})
+    ident, last = list_entry(c, RED1, cp['MAX_RS'] - 1)
+    c.step({RED1: one(PrivilegeEscalate(hostname=last.hostname, session=ident, agent=RED1), 1)}, skip_valid=True)
+    c.step({BLUE0: one(Restore(session=0, agent=BLUE0, hostname=rza[0]), 1)})
+    for _ in range(2):
+        c.step({})
+    yield c
+
+
+def vsftpd_decoy(c, hostname, agent):
+    assert c.deploy_decoy(hostname, DecoyVsftpd, 8, agent)       # its port check never refuses (DecoyVsftpd.py:17-20): one more process per call
+
+
+@fixture('capacity_process_lists', 'capacity family: process lists at the boundary between the inline and the overflow part (7, 8, 9 processes) and exactly full for the shortest '
+         'episodes the fixtures use (30 steps): the highest-numbered host of a defended zone filled by decoy factories (test_Red/test_DiscoverDeception.py:43) to one below, DeployDecoy '
+         'fills it, Remove stops the shell of an earlier exploit near the list\'s head, Restore, a new exploit with PrivilegeEscalate; root_internet_host_0 -- the last row -- filled by hand')
+def _():
+    steps = 30
+    cp = caps(steps)
+    full = cp['PIN'] + cp['povf']
+    c = Case(304, steps=steps, slim=True, no_err=True, note=f'PIN {cp["PIN"]} + cold_povf_cap({steps}) {cp["povf"]}')
+    b4 = 'blue_agent_4'
+    a_host = plain_hosts(c, RZA)[0]
+    b_host = plain_hosts(c, OFF)[-1]                              # the highest-numbered host a blue agent defends
+    inet = 'root_internet_host_0'                                 # the highest-numbered host: its overflow row closes the cold row
+    nproc = lambda hn: len(c.st.hosts[hn].processes)              # noqa: E731
+    src = plain_hosts(c, OFF)[0]
+    c.add_session(red(5), src, root=True, abstract=True)
+    c.set_red_active(red(5), True)
+    tip = c.ip(b_host)
+
+    def exploit_b():
+        o = c.step({red(5): one(AggressiveServiceDiscovery(session=0, agent=red(5), ip_address=tip), 1)}, skip_valid=True)
+        assert o[red(5)]['success'] == True       # noqa: E712
+        for _ in range(4):
+            n0 = nsess(c, red(5))
+            c.step({red(5): one(ExploitRemoteService(ip_address=tip, session=0, agent=red(5)), 1)}, skip_valid=True)
+            if nsess(c, red(5)) > n0:
+                return
+        raise SystemExit('no exploit succeeded')
+    exploit_b()                                                   # its shell sits near the head of the list, its pid becomes suspicious
+    for want in (cp['PIN'] - 1, cp['PIN'], cp['PIN'] + 1):        # 7, 8, 9 processes on a host, a step on each
+        while nproc(a_host) < want:
+            vsftpd_decoy(c, a_host, BLUE0)
+        assert nproc(a_host) == want
+        c.step({BLUE0: one(Analyse(session=0, agent=BLUE0, hostname=a_host), 1)})
+    while nproc(inet) < full:
+        c.add_ot_service(inet, root=bool(nproc(inet) % 2))        # (no agent has a session there for a decoy factory to act through)
+    while nproc(b_host) < full - 1:
+        vsftpd_decoy(c, b_host, b4)
+    c.step({})                                                    # one below the cap
+    c.step({b4: one(DeployDecoy(session=0, agent=b4, hostname=b_host), 1)})
+    assert nproc(b_host) == full and nproc(inet) == full
+    c.step({})                                                    # exactly full
+    c.step({b4: one(Remove(session=0, agent=b4, hostname=b_host), 1)})          # the exploit's shell goes: every later record moves down one
+    assert nproc(b_host) == full - 1
+    vsftpd_decoy(c, b_host, b4)
+    c.step({b4: one(Restore(session=0, agent=b4, hostname=b_host), 1)})
+    assert nproc(b_host) < cp['PIN']
+    while nproc(b_host) < full - 1:
+        vsftpd_decoy(c, b_host, b4)
+    exploit_b()                                                   # the exploit's shell is the record that fills the list
+    assert nproc(b_host) == full
+    ident, last = list_entry(c, red(5), nsess(c, red(5)) - 1)
+    assert last.hostname == b_host
+    c.step({red(5): one(PrivilegeEscalate(hostname=b_host, session=ident, agent=red(5)), 1)}, skip_valid=True)
+    assert nproc(b_host) == full
+    c.step({BLUE0: one(Remove(session=0, agent=BLUE0, hostname=a_host), 1)})
+    c.step({})
+    yield c
 
 
 def main():
