@@ -298,6 +298,10 @@ int cc4_verify_stats(cc4_handle* h, int64_t* out /* [2] */) { out[0] = h->verify
 // One launch of the persistent kernel for k steps of the whole batch (cc4_run_random_steps form 3; cc4_rollout_begin with rollout = true: every step
 // an item of its own, the actions from the rollout's slots behind the caller's publishes).
 // pl: a plan call (cc4_run_plan_device) -- the plan builds k_run_philox1p / k_run_pcgp on the same schedule, tickets and progress words.
+// what k_run_philox1 is compiled for (philox1_body<.., HEAD>): a step that draws its blue actions itself and reads nothing else of a caller's
+static bool head_shape(const StepArgs& a, const XchgArgs& x) {
+  return a.rand_out && !a.actions && !a.msgs && !a.act_sys && !a.obs8 && !a.prof && !a.ext && !a.dbg_stop && !x.slab;
+}
 int persist_launch(cc4_handle* h, StepArgs a, int k, uint32_t t0, const XchgArgs& x, hipEvent_t e0, hipEvent_t e1, bool rollout, const PlanArgs* pl) {
   if (h->pool_base + (uint32_t)k > PROGRESS_CLEAR_AT) {      // (the progress words count steps since they were last cleared)
     HIPCHK(h, hipMemsetAsync(h->d_run, 0, h->run_words * sizeof(uint32_t), h->stream));
@@ -328,7 +332,10 @@ int persist_launch(cc4_handle* h, StepArgs a, int k, uint32_t t0, const XchgArgs
     // a rollout leaves `rollout_margin` waves per CU to the caller's policy kernels and the gates (CC4_ROLLOUT_MARGIN)
     const int grid = rollout ? h->run_grid - h->rollout_margin * h->cus : h->run_grid;
     if (rollout) hipExtLaunchKernelGGL(k_run_philox1r, dim3(grid > h->cus ? grid : h->cus), dim3(WAVE), offsetof(EnvState, hd), h->stream, e0, e1, 0, a, ra, x);
-    else hipExtLaunchKernelGGL(k_run_philox1, dim3(grid), dim3(WAVE), offsetof(EnvState, hd), h->stream, e0, e1, 0, a, ra, x);
+    // the headline build knows its call's shape at compile time -- actions drawn in the kernel, none given, no messages, nothing of the debug or
+    // exchange arguments: a call of any other shape takes the build that reads them at run time
+    else if (head_shape(a, x)) hipExtLaunchKernelGGL(k_run_philox1, dim3(grid), dim3(WAVE), offsetof(EnvState, hd), h->stream, e0, e1, 0, a, ra);
+    else hipExtLaunchKernelGGL(k_run_philox1g, dim3(grid), dim3(WAVE), offsetof(EnvState, hd), h->stream, e0, e1, 0, a, ra, x);
   }
   return 0;
 }

@@ -20,7 +20,8 @@ extern template __global__ void k_step_philox1<true>(StepArgs);
 __global__ void k_run_philox(StepArgs a, int K, uint32_t t0, XchgArgs x);
 __global__ void k_run_philox8(StepArgs a, int K, uint32_t t0, XchgArgs x);
 __global__ void k_run_philox1m(StepArgs a, int K, uint32_t t0, XchgArgs x);
-__global__ void k_run_philox1(StepArgs a, RunArgs ra, XchgArgs x);
+__global__ void k_run_philox1(StepArgs a, RunArgs ra);      // the headline build: in-kernel action draw only (persist_launch)
+__global__ void k_run_philox1g(StepArgs a, RunArgs ra, XchgArgs x);      // the same schedule with every run-time flag (cc4_k_run1g.hip)
 __global__ void k_run_philox1x(StepArgs a, RunArgs ra, XchgArgs x);
 __global__ void k_run_philox1r(StepArgs a, RunArgs ra, XchgArgs x);
 __global__ void k_run_pcg(StepArgs a, RunArgs ra, XchgArgs x);

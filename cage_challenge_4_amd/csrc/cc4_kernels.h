@@ -6,6 +6,8 @@
 //   cc4_k_philox1.hip  counter mode, one wavefront per episode: k_step_philox1<LOG>, k_run_philox1m (cc4_philox1_body.h: the step's body)
 //   cc4_k_run1.hip     the persistent kernel of large batches: k_run_philox1 (cc4_persist.h: its schedule, shared with k_run_pcg; cc4_sched.h: the index
 //                      arithmetic of that schedule, of the gates and of the host side -- partitions, tickets, runs, the progress word, the groups of 32)
+//                      -- the headline build: compiled for calls that draw their actions in the kernel and carry no actions or messages
+//   cc4_k_run1g.hip    the same schedule with every run-time flag, k_run_philox1g: what persist_launch sends a call of any other shape
 //   cc4_k_run1x.hip    its other builds: k_run_philox1x (beside RCCL), k_run_philox1r (rollouts with the policy in the loop)
 //   cc4_k_plan.hip     the plan build of the persistent kernel, k_run_philox1p (cc4_run_plan_device), and the plan call's helpers; the numpy-stream
 //                      plan build k_run_pcgp sits beside k_run_pcg (the numpy-stream step body and its jump table are private to cc4_k_pcg.hip)

@@ -6,7 +6,7 @@
 
 // the step bodies (defined in cc4_k_pcg.hip / cc4_philox1_body.h)
 template <bool LOG> __device__ __forceinline__ void pcg_body(StepArgs a, const int e, const int lane, const bool first = true, const bool last = true);
-template <bool LOG, bool PERSIST> __device__ __forceinline__ void philox1_body(StepArgs a, const int e, const uint32_t rand_t, const uint32_t item_k, const int lane,
+template <bool LOG, bool PERSIST, bool HEAD> __device__ __forceinline__ void philox1_body(StepArgs a, const int e, const uint32_t rand_t, const uint32_t item_k, const int lane,
                                                                 const bool first, const bool last);
 
 // the CU this wave runs on, as a slot id below CC4_SLOTS: (XCC id << 8) | HW_ID[15:8]
@@ -95,8 +95,11 @@ __device__ __forceinline__ void persist_step_out(const StepArgs& a, const RunArg
 // PLAN: the build serves cc4_run_plan_device (k_run_philox1p / k_run_pcgp; PlanArgs) -- step j of the call reads its blue actions and messages from row j
 // of the caller's plan and writes reward / done / packed observation row into row j of the caller's trajectory.  The plan was complete before the launch
 // and the trajectory is read behind its end: plain loads, no gate, no counter, no watchdog.  In every other build `pl` is dead and folds away.
-template <bool PCG, bool ROLLOUT = false, bool XCHG = true, bool PLAN = false>
+// HEAD: the build of the headline kernel k_run_philox1 (counter mode, no exchange, no rollout, no plan), launched only for calls whose blue actions are
+// drawn in the kernel and that carry no actions and no messages (persist_launch decides): the step body is compiled knowing that (philox1_body).
+template <bool PCG, bool ROLLOUT = false, bool XCHG = true, bool PLAN = false, bool HEAD = false>
 __device__ __forceinline__ void persist_loop(StepArgs a, RunArgs ra, const XchgArgs x, const PlanArgs pl = PlanArgs{}) {
+  static_assert(!HEAD || (!PCG && !ROLLOUT && !XCHG && !PLAN), "the headline build: counter mode, nothing but the steps");
   // (the item travels from lane 0 to the wave through v_readfirstlane, not through LDS)
   const int lane = threadIdx.x;
   const int my_slot = cu_slot();
@@ -248,7 +251,7 @@ __device__ __forceinline__ void persist_loop(StepArgs a, RunArgs ra, const XchgA
         if (XCHG && x.slab) b.obs8 = x.slab + (size_t)(item_k % (uint32_t)x.ring) * (size_t)a.n * OBS_PACKED;
         pcg_body<false>(b, e, lane_i, q == 0, q == run_len - 1);
       } else {
-        philox1_body<false, true>(a, e, ra.t0 + item_k, item_k, lane_i, q == 0, q == run_len - 1);      // (a.obs8 is null: the packed row is written by persist_step_out, behind the drain)
+        philox1_body<false, true, HEAD>(a, e, ra.t0 + item_k, item_k, lane_i, q == 0, q == run_len - 1);    // (a.obs8 is null: the packed row is written by persist_step_out, behind the drain)
       }
       if constexpr (PLAN) {          // (the agent part is still in LDS; the body's last barrier is behind the step's last set_err)
         extern __shared__ uint4 plan_lds[];

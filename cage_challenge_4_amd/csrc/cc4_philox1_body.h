@@ -35,9 +35,14 @@ __device__ __forceinline__ void philox1_autoreset(const StepArgs& a, const int e
 // LOG: the full build of a step kernel -- it records the HostEvents entries of the step (cc4_enable_event_log) and takes externally
 // submitted red / green actions (cc4_step_ex: StepArgs.ext).  A template parameter rather than a run-time flag: even a never-taken
 // logging branch at the eleven event sites costs the serial walk 10 %.
-template <bool LOG, bool PERSIST>
+// HEAD: the build of the headline kernel (k_run_philox1), which the host launches only for calls that draw the blue actions in the kernel and carry
+// neither actions nor messages (persist_launch checks it): rand_out is set, actions / msgs / act_sys / obs8 are not -- compile-time facts here, so the
+// step neither keeps those arguments nor tests them.
+template <bool LOG, bool PERSIST, bool HEAD = false>
 __device__ __forceinline__ void philox1_body(StepArgs a, const int e, const uint32_t rand_t, const uint32_t item_k, const int lane,
                                              const bool first = true, const bool last = true) {
+  static_assert(!HEAD || (PERSIST && !LOG), "the headline build is a fast persistent build");
+  if constexpr (HEAD) { a.actions = nullptr; a.msgs = nullptr; a.act_sys = 0; a.obs8 = nullptr; }
   extern __shared__ uint4 lds[];
   // Static LDS is kept under 512 bytes: agent part (7168 B) + statics then fit SIX 1280-byte LDS granules, 21 waves per CU by LDS and 20
   // by registers; a seventh granule would leave 18 (profiles/r05_lds_residency.txt: the occupancy query, which divides 160 KB by the
@@ -106,7 +111,7 @@ __device__ __forceinline__ void philox1_body(StepArgs a, const int e, const uint
         else if (lane < BK_BRAND) st = ST_BLUE_EXE + (uint32_t)(lane - BK_BEXE);
         bank[0] = 0u; bank[1] = st; bank[2] = (uint32_t)rl.inc_lo; bank[3] = (uint32_t)rl.inc_hi;      // rng_block(&rl, st, 0, .)
         uint32_t k0 = (uint32_t)rl.s_lo, k1 = (uint32_t)(rl.s_lo >> 32);
-        if (a.rand_out && lane >= BK_BRAND && lane < BK_END) {   // random_blue_action(seed0, t, e, b): another key and counter layout
+        if ((HEAD || a.rand_out) && lane >= BK_BRAND && lane < BK_END) {   // random_blue_action(seed0, t, e, b): another key and counter layout
           const uint64_t key = a.rand_seed0 + (uint64_t)e;
           bank[0] = rand_t; bank[1] = (uint32_t)(lane - BK_BRAND); bank[2] = 0xB10Eu; bank[3] = 0u; k0 = (uint32_t)key; k1 = (uint32_t)(key >> 32);
         }
@@ -136,7 +141,7 @@ __device__ __forceinline__ void philox1_body(StepArgs a, const int e, const uint
       } else if (lane >= 8 && lane < 8 + NBLUE && !(CC4_STOP_ON && a.dbg_stop == 3)) {
         const int b = lane - 8;
         int32_t act = !a.actions ? -1 : a.act_sys ? __hip_atomic_load(a.actions + e * NBLUE + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : a.actions[e * NBLUE + b];
-        if (a.rand_out) { act = (int32_t)(((uint64_t)brand * (uint32_t)(b == 4 ? ACT_LONG : ACT_SHORT)) >> 32); a.rand_out[e * NBLUE + b] = act; }   // == random_blue_action
+        if (HEAD || a.rand_out) { act = (int32_t)(((uint64_t)brand * (uint32_t)(b == 4 ? ACT_LONG : ACT_SHORT)) >> 32); a.rand_out[e * NBLUE + b] = act; }   // == random_blue_action
         step_blue_submit(xg, b, act);
         step_tick_blue(xg, b);
         if (!msgs_clean) step_messages(s, a.msgs ? a.msgs + e * NBLUE * MSG_LEN : nullptr, b);   // read back by this step's observation encode only
