@@ -661,7 +661,9 @@ CC4_HD void obs_put(Ctx x, int r, bool key_ip, int host, int flags, bool subnet_
 CC4_HD void obs_first(Ctx x, int r, int success, int atype, int ahost, int aarg) {
   RedAgent& a = x.s->red[r];
   if (a.h.obs_success != 0) return;
-  a.h.obs_success = (uint8_t)success; a.h.obs_act_type = (uint8_t)atype; a.h.obs_act_host = (uint8_t)ahost; a.h.obs_act_arg = (uint8_t)aarg;
+  // the four bytes are one aligned word of the header (hdr_obs_word): one store, whoever's lane this is
+  const uint32_t v = hdr_obs_word((uint32_t)success, (uint32_t)atype, (uint32_t)ahost, (uint32_t)aarg);
+  __builtin_memcpy(__builtin_assume_aligned(reinterpret_cast<char*>(&a.h) + offsetof(RedHdr, obs_success), 4), &v, 4);
 }
 
 // ------------------------------------------------------------------ routes (tree of routers)
@@ -1301,7 +1303,7 @@ CC4_HD void blue_decoy(Ctx x, int h) {
   }
   d.svcs[si].kind = (uint8_t)kind; d.svcs[si].pid = (uint16_t)pid; d.svcs[si].st = (uint8_t)(SV_ACTIVE | 5);
 }
-CC4_HD void blue_execute(Ctx x, int b, const Act& a) {
+CC4_HD void blue_execute(Ctx x, int b, const Act& a) {   // (the record's type, host and arg as bytes: read as one word the extracts cost more than the two reads they save)
   EnvState* s = x.s;
   switch (a.type) {
     case BA_MONITOR: blue_monitor(x, b); break;
@@ -1783,15 +1785,19 @@ CC4_HD void red_deception(Ctx x, int r, const Act& a, RedPre pre = RedPre()) {
   red_result(x, r, a, T_TRUE);
 }
 // RedSessionCheck.execute (ConcreteActions/RedSessionCheck.py:9-65)
-CC4_HD void red_session_check(Ctx x, int r) {
+// H: the header's second vector in registers (hdr_load(.., HDR_HI)); the caller stores it back.  The agent's lane owns its header in this phase (nobody
+// else writes a red header between the Monitor roll-over and the end of the step), so obs_first, rsc_listed and rsc_dirty are edits of H; what the
+// callees below write in the row is in the FIRST vector (nknown, as_subnet), which is not stored back, or mirrored in H (rs_move_to_end's rsc_dirty).
+CC4_HD void red_session_check(Ctx x, int r, RedHdrW& H) {
   EnvState* s = x.s;
   RedAgent& A = s->red[r];
-  obs_first(x, r, T_TRUE, RA_NONE, 0, 0);
+  if (hget<RH_OBS_SUCCESS>(H) == 0) H.w[hdr_field(RH_OBS_SUCCESS).word] = hdr_obs_word(T_TRUE, RA_NONE, 0, 0);   // obs_first(TRUE)
   if (A.h.nsess == 0) return;
   // the primary (id 0) sits first, or last after a promotion / restore re-insert: look there before scanning
   if (rsw_id(rs_at(s, A, 0)) != 0 && rsw_id(rs_at(s, A, A.h.nsess - 1)) != 0 && rs_find_id(s, A, 0) < 0) {
     int c = (int)rng_below(x.r, (uint32_t)A.h.nsess);
     rs_move_to_end(s, A, c, 0);   // active_sessions.pop(old_id); ident = 0; re-inserted last (RedSessionCheck.py:36-45)
+    hset<RH_RSC_DIRTY>(H, 1);     // (as rs_move_to_end set it in the row)
     // every other session's parent becomes new_primary.name, which is None unless the promoted session is the scenario's
     // own 'red_session_0' (never the case: that one holds id 0 from the start) (RedSessionCheck.py:52-55)
     for (int i = 0; i < A.h.nsess; ++i) s->spool[A.sord[i]].flags &= (uint8_t)~RS_CHILD;
@@ -1799,8 +1805,8 @@ CC4_HD void red_session_check(Ctx x, int r) {
   // The observation lists every session as a hostname-keyed entry with Sessions / Interface{ip, Subnet} / System info.
   // Instead of materialising one entry per session, its three effects are applied in bulk from RedAgent.live_hosts (the
   // exact set of hosts in the listing): ActionSpace knowledge here, FSM knowledge in fsm_observe (rsc_listed).
-  A.h.rsc_listed = 1;
-  if (!A.h.rsc_dirty) return;      // same session table as at the last listing: nothing new to learn
+  hset<RH_RSC_LISTED>(H, 1);
+  if (!hget<RH_RSC_DIRTY>(H)) return;      // same session table as at the last listing: nothing new to learn
   const B5 live = b5_load(A.live_hosts);
   { const B5 ip = b5_load(A.as_ip), hn = b5_load(A.as_hn); b5_store(A.as_ip, b5_or(ip, live)); b5_store(A.as_hn, b5_or(hn, live)); }
   {  // the subnets of the session hosts = the subnets with a live host (ids 17 sn .. 17 sn + 16)
@@ -1842,7 +1848,7 @@ CC4_HD void red_session_check(Ctx x, int r) {
         if (rsw_host(w) == h && (rsw_flags(w) & RS_ABSTRACT)) as_know_sid(x, r, rsw_id(w));   // a known id: nothing
       }
     }
-  A.h.rsc_dirty = 0;
+  hset<RH_RSC_DIRTY>(H, 0);
 }
 // Withdraw.execute (ConcreteActions/Withdraw.py:38-91) + StopProcess(stop_all=True).  a.host = ip_address (unused beyond the
 // route, which always exists), a.arg = hostname
@@ -1879,7 +1885,12 @@ CC4_HD void red_withdraw(Ctx x, int r, const Act& a, RedPre pre = RedPre()) {
   red_result(x, r, a, ok);
 }
 // pre: the agent's RedPre for this action when computed ahead (rs_wave_query; pre.ok)
-CC4_HD void red_execute(Ctx x, int r, const Act& a, RedPre pre = RedPre()) {
+// w: the agent's record (EnvState.rexec[r]) as the caller read it, one word: the action bodies take its fields from registers.
+// RELIED UPON: `a` below is a local struct whose address goes to force-inlined functions only, so the optimiser scalarises it (its six fields become
+// extracts of w; nothing is stored to scratch).  tools/hdr_traffic.py shows it: rexec is read at 4 sites of k_run_philox1, and the kernel's scratch size
+// in profiles/kernel_resources.txt has not moved.  An action body that is no longer inlined, or that takes &a.field, ends that.
+CC4_HD void red_execute(Ctx x, int r, ActW w, RedPre pre = RedPre()) {
+  const Act a = act_unpack(w);
   switch (a.type) {
     case RA_DRS: red_drs(x, r, a, pre); break;
     // detection_rate: the class's own, or the one the action object came with (ExtAct: the reference's tests set it to 0 and 1)
@@ -1937,7 +1948,7 @@ CC4_HD void fsm_set_state(RedAgent& A, int h, int st) {
   if ((st & 1) || st == FS_F) bit_set(A.fsm_nodrs, h); else bit_clr(A.fsm_nodrs, h);
   fsm_put(A, h, st);
 }
-CC4_HD void fsm_apply(Ctx x, int r, RedHdr& H, int h, int act, bool success) {  // _host_state_transition inner loop (:147-167)
+CC4_HD void fsm_apply(Ctx x, int r, RedHdrW& H, int h, int act, bool success) {  // _host_state_transition inner loop (:147-167)
   RedAgent& A = x.s->red[r];
   int cur = fsm_get(A, h);
   if (cur == FS_NONE) return;
@@ -1947,27 +1958,30 @@ CC4_HD void fsm_apply(Ctx x, int r, RedHdr& H, int h, int act, bool success) {  
   if (nx != cur) fsm_set_state(A, h, nx);
   if (nx == FS_F && cur != FS_F) {  // leaves known_hosts for good
     int n = 0;
-    for (int i = 0; i < H.fsm_n; ++i) if (A.fsm_order[i] != h) A.fsm_order[n++] = A.fsm_order[i];
-    H.fsm_n = (uint8_t)n;
+    const int fn = (int)hget<RH_FSM_N>(H);
+    for (int i = 0; i < fn; ++i) if (A.fsm_order[i] != h) A.fsm_order[n++] = A.fsm_order[i];
+    hset<RH_FSM_N>(H, (uint32_t)n);
   }
 }
-// H: the agent's scalar fields in registers (RedHdr); the caller loaded them and stores them back
-CC4_HD void fsm_observe(Ctx x, int r, RedHdr& H) {
+// H: the agent's scalar fields in registers (the word view of RedHdr); the caller loaded them and stores them back.  Writes fsm_n and fsm_dirty only:
+// the header's second vector
+CC4_HD void fsm_observe(Ctx x, int r, RedHdrW& H) {
   RedAgent& A = x.s->red[r];
   CC4_AT0(x);
   // Mid-action agent whose observation is just the RedSessionCheck listing of an unchanged session table: nothing below can
   // change anything.  No transition (success is IN_PROGRESS), no entry to process, the listing's hosts were merged when the
   // table last changed (live <= known, hostnames known), and the removal check found fsm_ur & ~live empty then -- neither
   // set has moved since (fsm_ur only moves in this function, live only with fsm_dirty).
-  if (H.obs_success == T_IN_PROGRESS && H.nobs == 0 && H.rsc_listed && !H.fsm_dirty) return;
+  const uint32_t obs_success = hget<RH_OBS_SUCCESS>(H), nobs = hget<RH_NOBS>(H);
+  if (obs_success == T_IN_PROGRESS && nobs == 0 && hget<RH_RSC_LISTED>(H) && !hget<RH_FSM_DIRTY>(H)) return;
   // 1. _host_state_transition (:124-167)
-  if (H.obs_act_type <= RA_WITHDRAW && H.obs_success != T_IN_PROGRESS && H.obs_success != 0) {
-    bool ok = H.obs_success == T_TRUE;
-    int t = H.obs_act_type;
+  if (hget<RH_OBS_ACT_TYPE>(H) <= RA_WITHDRAW && obs_success != T_IN_PROGRESS && obs_success != 0) {
+    bool ok = obs_success == T_TRUE;
+    int t = (int)hget<RH_OBS_ACT_TYPE>(H);
     if (t == RA_DRS) {
       // every known host of the pinged subnet (ids subnet*17 .. +16); the order of the per-host transitions is immaterial
       // on success only K, S, U, R move (to KD, SD, UD, RD): visit just those hosts
-      const int lo = H.obs_act_arg * SLOTS, hi = lo + SLOTS - 1;
+      const int lo = (int)hget<RH_OBS_ACT_ARG>(H) * SLOTS, hi = lo + SLOTS - 1;
       for (int w = lo >> 5; w <= (hi >> 5) && w < 5; ++w) {
         uint32_t m = A.fsm_known[w];
         if (ok) m &= ~A.fsm_nodrs[w];
@@ -1977,16 +1991,16 @@ CC4_HD void fsm_observe(Ctx x, int r, RedHdr& H) {
         while (m) { int b = ctz32(m); m &= m - 1; fsm_apply(x, r, H, w * 32 + b, t, ok); }
       }
     } else if (t == RA_PRIVESC || t == RA_IMPACT || t == RA_DEGRADE) {
-      int h = H.obs_act_host;  // matched through host_states[ip]['hostname']
+      int h = (int)hget<RH_OBS_ACT_HOST>(H);  // matched through host_states[ip]['hostname']
       if (bit_get(A.fsm_known, h) && bit_get(A.fsm_hn, h)) fsm_apply(x, r, H, h, t, ok);
     } else {
-      fsm_apply(x, r, H, H.obs_act_host, t, ok);
+      fsm_apply(x, r, H, (int)hget<RH_OBS_ACT_HOST>(H), t, ok);
     }
   }
   CC4_AT(x, 3);
   // 2. _process_new_observations (:190-250)
   B5 seen = b5_zero();   // hosts whose observation entry carries Sessions
-  for (int i = 0; i < H.nobs; ++i) {
+  for (int i = 0; i < (int)nobs; ++i) {
     int h = A.obs[i].host; int f = A.obs[i].flags;
     if (f & OE_SESS) b5_set(seen, h);
     bool hn = !(f & OE_KEY_IP) || (f & OE_SYSHN);
@@ -1997,8 +2011,8 @@ CC4_HD void fsm_observe(Ctx x, int r, RedHdr& H) {
       continue;
     }
     if (!bit_get(A.fsm_known, h)) {
-      fsm_set_state(A, h, H.fsm_step == 0 ? FS_U : FS_K);
-      A.fsm_order[H.fsm_n++] = (uint8_t)h;
+      fsm_set_state(A, h, hget<RH_FSM_STEP>(H) == 0 ? FS_U : FS_K);
+      A.fsm_order[hget<RH_FSM_N>(H)] = (uint8_t)h; hinc<RH_FSM_N>(H);
       bit_set(A.fsm_known, h);
     }
     if (hn) bit_set(A.fsm_hn, h);
@@ -2006,19 +2020,19 @@ CC4_HD void fsm_observe(Ctx x, int r, RedHdr& H) {
   CC4_AT(x, 4);
   // the RedSessionCheck listing (comes last in the observation's key order): every session host is hostname-known, carries
   // Sessions, and is new to host_states iff it is not in fsm_known -- added in session (dict) order
-  if (H.rsc_listed) {
+  if (hget<RH_RSC_LISTED>(H)) {
     const B5 live = b5_load(A.live_hosts), known = b5_load(A.fsm_known), hn = b5_load(A.fsm_hn);
     seen = b5_or(seen, live);
     if (b5_any(b5_andn(live, known)))
-      for (int i = 0; i < H.nsess; ++i) {
+      for (int i = 0, ns = (int)hget<RH_NSESS>(H); i < ns; ++i) {
         int h = rsw_host(rs_at(x.s, A, i));
         if (bit_get(A.fsm_known, h)) continue;
-        fsm_set_state(A, h, H.fsm_step == 0 ? FS_U : FS_K);
-        A.fsm_order[H.fsm_n++] = (uint8_t)h;
+        fsm_set_state(A, h, hget<RH_FSM_STEP>(H) == 0 ? FS_U : FS_K);
+        A.fsm_order[hget<RH_FSM_N>(H)] = (uint8_t)h; hinc<RH_FSM_N>(H);
         bit_set(A.fsm_known, h);
       }
     b5_store(A.fsm_hn, b5_or(hn, live));
-    H.fsm_dirty = 0;
+    hset<RH_FSM_DIRTY>(H, 0);
   }
   CC4_AT(x, 5);
   // 3. _session_removal_state_change (:169-188): hosts in U/UD/R/RD without a Sessions entry in the observation -> KD
@@ -2035,11 +2049,12 @@ CC4_HD void fsm_observe(Ctx x, int r, RedHdr& H) {
 // DiscoveryFSRed._choose_host (FiniteStateRedAgent.py:252-293 with FSMRedVariants.py:95-110): host-state priorities
 // {K,KD,S,SD: 20, U,UD: 10, R,RD: 0} and prioritise_servers.  The float arithmetic restates the Python expressions
 // operation by operation (probs = (p/100) * (1/(sum/100)); numpy choice(p) = cumsum, /= last, searchsorted right).
-CC4_HD int fsm_choose_host_discovery(Ctx x, int r, RedHdr& H) {
+CC4_HD int fsm_choose_host_discovery(Ctx x, int r, const RedHdrW& H) {
   RedAgent& A = x.s->red[r];
+  const int fsm_n = (int)hget<RH_FSM_N>(H);
   // available_states in order of first appearance among the known hosts, packed as nibbles
   uint32_t order = 0; int nst = 0; uint32_t seen = 0;
-  for (int i = 0; i < H.fsm_n && nst < 8; ++i) {
+  for (int i = 0; i < fsm_n && nst < 8; ++i) {
     int st = fsm_get(A, A.fsm_order[i]);
     if (!((seen >> st) & 1u)) { seen |= 1u << st; order |= (uint32_t)st << (4 * nst); nst++; }
   }
@@ -2063,7 +2078,7 @@ CC4_HD int fsm_choose_host_discovery(Ctx x, int r, RedHdr& H) {
     chosen_state = (order >> (4 * (int)rng_below(x.r, (uint32_t)nst))) & 0xF;
   }
   int n_all = 0, n_srv = 0;
-  for (int i = 0; i < H.fsm_n; ++i) {
+  for (int i = 0; i < fsm_n; ++i) {
     int h = A.fsm_order[i];
     if (fsm_get(A, h) != chosen_state) continue;
     n_all++;
@@ -2076,7 +2091,7 @@ CC4_HD int fsm_choose_host_discovery(Ctx x, int r, RedHdr& H) {
   }
   int cnt = want_srv < 0 ? n_all : (want_srv ? n_srv : n_all - n_srv);
   int c = (int)rng_below(x.r, (uint32_t)cnt);
-  for (int i = 0; i < H.fsm_n; ++i) {
+  for (int i = 0; i < fsm_n; ++i) {
     int h = A.fsm_order[i];
     if (fsm_get(A, h) != chosen_state) continue;
     bool srv = h_is_server(h) && bit_get(A.fsm_hn, h);
@@ -2135,16 +2150,16 @@ static constexpr FsmPkTab fsm_pk_tab = make_fsm_pk_tab();
 CC4_HD uint32_t fsm_pk(bool discovery, int host_state) { return fsm_pk_tab.v[fsm_pk_index(discovery, host_state)]; }
 // get_action (:58-122) incl. _choose_host (:252-293) and _choose_host_and_action (:296-336)
 // observed: fsm_observe (which draws nothing) has already run for this step (step_red_observe)
-CC4_HD Act fsm_get_action(Ctx x, int r, RedHdr& H, bool observed = false) {
+CC4_HD ActW fsm_get_action(Ctx x, int r, RedHdrW& H, bool observed = false) {
   EnvState* s = x.s;
   RedAgent& A = s->red[r];
-  Act out; out.type = RA_SLEEP; out.host = 0; out.arg = 0; out.ticks = 1; out.sid = 0; out.busy = 0;
+  constexpr ActW sleep = act_word(RA_SLEEP, 0, 0, 1, 0, 0);
   CC4_FT0(x, r);
   if (!observed) fsm_observe(x, r, H);
   CC4_FT(x, r, 5);
-  if (H.obs_success == T_IN_PROGRESS) { H.fsm_step++; return out; }
-  int n = H.fsm_n;  // fsm_order holds exactly the non-'F' hosts, in host_states insertion order
-  if (n == 0) { set_err(x, E_FSM_NO_HOST); H.fsm_step++; return out; }
+  if (hget<RH_OBS_SUCCESS>(H) == T_IN_PROGRESS) { hinc<RH_FSM_STEP>(H); return sleep; }
+  int n = (int)hget<RH_FSM_N>(H);  // fsm_order holds exactly the non-'F' hosts, in host_states insertion order
+  if (n == 0) { set_err(x, E_FSM_NO_HOST); hinc<RH_FSM_STEP>(H); return sleep; }
   const bool discovery = (s->policy & 3) == RP_DISCOVERY;
   int host;
   if (!discovery) host = A.fsm_order[rng_below(x.r, (uint32_t)n)];
@@ -2155,32 +2170,35 @@ CC4_HD Act fsm_get_action(Ctx x, int r, RedHdr& H, bool observed = false) {
   int k = 0;
   for (int i = 0; i < 4; ++i) if ((int)((pk >> (16 + 4 * i)) & 0xF) <= fl) k++;
   int t = (int)((pk >> (4 * k)) & 0xF);
-  out.type = (uint8_t)t; out.host = (uint8_t)host;
+  uint32_t arg = 0, sid = 0;
   // parameters in constructor-signature order; only `subnet` and `session` can draw
   bool bad = false;
   if (t == RA_DRS) {
-    uint32_t known = H.as_subnet;  // known subnets in dict (= SUBNET enum) order
-    if (known == 0) bad = true; else out.arg = (uint8_t)nth_bit(known, (int)rng_below(x.r, (uint32_t)popc32(known)));
+    uint32_t known = hget<RH_AS_SUBNET>(H);  // known subnets in dict (= SUBNET enum) order
+    if (known == 0) bad = true; else arg = (uint32_t)nth_bit(known, (int)rng_below(x.r, (uint32_t)popc32(known)));
   }
   if ((t == RA_PRIVESC || t == RA_IMPACT || t == RA_DEGRADE) && !bit_get(A.fsm_hn, host)) bad = true;
   if (!bad) {
-    if (H.nknown == 0) bad = true; else out.sid = x.c->known_sid[r][rng_below(x.r, (uint32_t)H.nknown)];
+    const uint32_t nknown = hget<RH_NKNOWN>(H);
+    if (nknown == 0) bad = true; else sid = x.c->known_sid[r][rng_below(x.r, nknown)];
   }
-  if (bad) { set_err(x, E_UNREACHABLE); out.type = RA_SLEEP; }  // reference would re-draw with p not summing to 1 and raise
-  out.ticks = (uint8_t)red_duration(out.type);
-  H.fsm_step++;
+  if (bad) { set_err(x, E_UNREACHABLE); t = RA_SLEEP; }  // reference would re-draw with p not summing to 1 and raise
+  hinc<RH_FSM_STEP>(H);
   CC4_FT(x, r, 7);
-  return out;
+  return act_word((uint32_t)t, (uint32_t)host, arg, (uint32_t)red_duration(t), sid, 0);
 }
 // RandomSelectRedAgent.get_action (Agents/SimpleAgents/RandomSelectRedAgent.py:33-103): uniform command, then uniform
 // parameters from the ActionSpace entries that are True.  Commands in red_actions order (ESG.py:764-768), parameters in
 // constructor order; a draw is made only when there is more than one option.
-CC4_HD Act random_red_get_action(Ctx x, int r, RedHdr& H) {
+// (The action is put together as a local Act and packed at the end -- a struct the optimiser scalarises, relied upon as in red_execute; this policy is
+// not the headline's.)
+CC4_HD ActW random_red_get_action(Ctx x, int r, RedHdrW& H) {
   RedAgent& A = x.s->red[r];
   Act out; out.type = RA_SLEEP; out.host = 0; out.arg = 0; out.ticks = 1; out.sid = 0; out.busy = 0;
   const int nip = popc32(A.as_ip[0]) + popc32(A.as_ip[1]) + popc32(A.as_ip[2]) + popc32(A.as_ip[3]) + popc32(A.as_ip[4]);
   const int nhn = popc32(A.as_hn[0]) + popc32(A.as_hn[1]) + popc32(A.as_hn[2]) + popc32(A.as_hn[3]) + popc32(A.as_hn[4]);
-  const int nsub = popc32(H.as_subnet), nsid = H.nknown;
+  const uint32_t as_subnet = hget<RH_AS_SUBNET>(H);
+  const int nsub = popc32(as_subnet), nsid = (int)hget<RH_NKNOWN>(H);
   // valid_commands: a command is listed only if each of its parameters has at least one True option
   // order: DRS, Aggressive, Stealth, Exploit, PrivEsc, Degrade, DiscoverDeception, Impact, Withdraw, Sleep
   const uint8_t types[10] = {RA_DRS, RA_AGGR, RA_STEALTH, RA_EXPLOIT, RA_PRIVESC, RA_DEGRADE, RA_DECEPTION, RA_IMPACT, RA_WITHDRAW, RA_SLEEP};
@@ -2200,7 +2218,7 @@ CC4_HD Act random_red_get_action(Ctx x, int r, RedHdr& H) {
   auto pick_hn = [&]() { return nth_set(A.as_hn, 5, (int)rng_below(x.r, (uint32_t)nhn)); };
   out.type = (uint8_t)t;
   switch (t) {
-    case RA_DRS: out.arg = (uint8_t)nth_bit(H.as_subnet, (int)rng_below(x.r, (uint32_t)nsub)); out.sid = (uint16_t)pick_sid(); break;
+    case RA_DRS: out.arg = (uint8_t)nth_bit(as_subnet, (int)rng_below(x.r, (uint32_t)nsub)); out.sid = (uint16_t)pick_sid(); break;
     case RA_AGGR: case RA_STEALTH: case RA_DECEPTION: out.sid = (uint16_t)pick_sid(); out.host = (uint8_t)pick_ip(); break;
     case RA_EXPLOIT: out.host = (uint8_t)pick_ip(); out.sid = (uint16_t)pick_sid(); break;
     case RA_PRIVESC: case RA_DEGRADE: case RA_IMPACT: out.host = (uint8_t)pick_hn(); out.sid = (uint16_t)pick_sid(); break;
@@ -2208,20 +2226,22 @@ CC4_HD Act random_red_get_action(Ctx x, int r, RedHdr& H) {
     default: break;
   }
   out.ticks = (uint8_t)red_duration(out.type);
-  H.fsm_step++;   // self.step
-  return out;
+  hinc<RH_FSM_STEP>(H);   // self.step
+  return act_pack(out);
 }
 // SimulationController.replace_action_if_invalid (SC:1068-1112) for a red action
-CC4_HD void red_validate(Ctx x, int r, const RedHdr& H, Act& a) {
+CC4_HD ActW red_validate(Ctx x, int r, const RedHdrW& H, ActW a) {
   RedAgent& A = x.s->red[r];
-  if (a.type >= RA_SLEEP) return;
+  const int type = (int)aget<AW_TYPE>(a), host = (int)aget<AW_HOST>(a), arg = (int)aget<AW_ARG>(a);
+  if (type >= RA_SLEEP) return a;
   bool ok = true;
-  if (!sid_known(A, x.c->known_sid[r], a.sid, H.nknown)) ok = false;
-  if (a.type == RA_DRS) { if (!((H.as_subnet >> a.arg) & 1u)) ok = false; }
-  else if (a.type == RA_PRIVESC || a.type == RA_IMPACT || a.type == RA_DEGRADE) { if (!bit_get(A.as_hn, a.host)) ok = false; }
-  else if (a.type == RA_WITHDRAW) { if (!bit_get(A.as_ip, a.host) || !bit_get(A.as_hn, a.arg)) ok = false; }
-  else { if (!bit_get(A.as_ip, a.host)) ok = false; }
-  if (!ok) { a.type = RA_INVALID; a.ticks = 1; }
+  if (!sid_known(A, x.c->known_sid[r], (int)aget<AW_SID>(a), (int)hget<RH_NKNOWN>(H))) ok = false;
+  if (type == RA_DRS) { if (!((hget<RH_AS_SUBNET>(H) >> arg) & 1u)) ok = false; }
+  else if (type == RA_PRIVESC || type == RA_IMPACT || type == RA_DEGRADE) { if (!bit_get(A.as_hn, host)) ok = false; }
+  else if (type == RA_WITHDRAW) { if (!bit_get(A.as_ip, host) || !bit_get(A.as_hn, arg)) ok = false; }
+  else { if (!bit_get(A.as_ip, host)) ok = false; }
+  if (!ok) a = aset<AW_TICKS>(aset<AW_TYPE>(a, RA_INVALID), 1);
+  return a;
 }
 
 // ------------------------------------------------------------------ different_subnet_agent_reassignment (SC:820-903)
@@ -2390,7 +2410,7 @@ CC4_HD void step_blue_submit(Ctx x, int b, int action_index) {
 #endif
   }
   a.ticks = (uint8_t)(dur ? dur : blue_duration(a.type));
-  if (!s->blue[b].queue.busy) { s->blue[b].queue = a; s->blue[b].queue.busy = 1; }
+  if (!aget<AW_BUSY>(act_load(&s->blue[b].queue))) act_store(&s->blue[b].queue, aset<AW_BUSY>(act_pack(a), 1));
 }
 // The policies' generator while a set_seed split is in force (EnvState.rng2; numpy-stream mode only -- in the counter mode
 // cc4_set_seed re-keys every stream): the walking generator and rng2 trade places around the policy loops.
@@ -2448,9 +2468,9 @@ CC4_HD void step_red_observe(Ctx x, int r) {
   const int pol = s->policy & 3;
   if (!A.h.active || pol == RP_RANDOM || pol == RP_SLEEP) return;
   if (x.ext && x.ext[r].type != XA_NONE) return;   // an action was submitted for this agent: get_action is not called, nothing is observed
-  RedHdr H = A.h;
+  RedHdrW H = hdr_load(&A.h);
   fsm_observe(x, r, H);
-  A.h = H;
+  hdr_store(&A.h, H, HDR_HI);   // fsm_n, fsm_dirty
 }
 // True if agent r's end-of-turn RedSessionCheck will draw (it promotes a session to primary: no session holds ident 0)
 CC4_HD bool rsc_draws(const EnvState* s, int r) {
@@ -2463,8 +2483,8 @@ CC4_HD int step_red_policy_tick(Ctx x, int r, bool observed = false, const uint3
   EnvState* s = x.s;
   RedAgent& A = s->red[r];
   CC4_FT0(x, r);
-  RedHdr H = A.h;
-  Act a; a.type = RA_SLEEP; a.host = 0; a.arg = 0; a.ticks = 1; a.sid = 0; a.busy = 0;
+  RedHdrW H = hdr_load(&A.h);
+  ActW a = act_word(RA_SLEEP, 0, 0, 1, 0, 0);
   rng_set_stream(x.r, ST_RED_POL + (uint32_t)r);
   if (pre) rng_preload(x.r, pre);
   CC4_FT(x, r, 0);
@@ -2472,36 +2492,35 @@ CC4_HD int step_red_policy_tick(Ctx x, int r, bool observed = false, const uint3
   if (ea) {
     // actions.get(agent_name) (SC:236-240): the submitted action is taken whether or not the agent is active, the agent object is
     // not asked -- no draw, no FSM observation, no step count -- and it goes through the same validity check (SC:241-242)
-    a.type = (uint8_t)ea->type; a.host = ea->host; a.arg = ea->arg; a.sid = ea->sid;
-    a.ticks = (uint8_t)(ea->ticks ? ea->ticks : red_duration(a.type));
-    if (!(ea->flags & XF_SKIP_VALID)) red_validate(x, r, H, a);
-    if (a.type < RA_SLEEP && (ea->flags & (XF_RATE0 | XF_RATE1))) a.busy = (uint16_t)((ea->flags & XF_RATE0 ? AQ_RATE0 : 0) | (ea->flags & XF_RATE1 ? AQ_RATE1 : 0));
+    const uint32_t type = (uint8_t)ea->type;
+    a = act_word(type, ea->host, ea->arg, (uint32_t)(ea->ticks ? ea->ticks : red_duration((int)type)), ea->sid, 0);
+    if (!(ea->flags & XF_SKIP_VALID)) a = red_validate(x, r, H, a);
+    if (aget<AW_TYPE>(a) < RA_SLEEP && (ea->flags & (XF_RATE0 | XF_RATE1))) a = aset<AW_BUSY>(a, (uint32_t)((ea->flags & XF_RATE0 ? AQ_RATE0 : 0) | (ea->flags & XF_RATE1 ? AQ_RATE1 : 0)));
   }
-  else if (H.active && (s->policy & 3) == RP_RANDOM) { a = random_red_get_action(x, r, H); red_validate(x, r, H, a); }
-  else if (H.active && (s->policy & 3) != RP_SLEEP) { a = fsm_get_action(x, r, H, observed); CC4_AT0(x); red_validate(x, r, H, a); CC4_AT(x, 7); }   // AgentInterface.get_action (:120-143); SleepAgent -> Sleep
+  else if (hget<RH_ACTIVE>(H) && (s->policy & 3) == RP_RANDOM) { a = random_red_get_action(x, r, H); a = red_validate(x, r, H, a); }
+  else if (hget<RH_ACTIVE>(H) && (s->policy & 3) != RP_SLEEP) { a = fsm_get_action(x, r, H, observed); CC4_AT0(x); a = red_validate(x, r, H, a); CC4_AT(x, 7); }   // AgentInterface.get_action (:120-143); SleepAgent -> Sleep
   CC4_FT(x, r, 1);
-  if (!H.queue.busy) {
-    H.queue = a; H.queue.busy = (uint16_t)(AQ_BUSY | a.busy);
-    if (x.ext && (a.busy & (AQ_RATE0 | AQ_RATE1))) { x.c->xrate[r][0] = ea->rate0; x.c->xrate[r][1] = ea->rate1; }
+  if (!hget<RH_Q_BUSY>(H)) {
+    hdr_set_queue(H, a | (ActW)AQ_BUSY << (32 + act_field(AW_BUSY).shift));
+    if (x.ext && (aget<AW_BUSY>(a) & (AQ_RATE0 | AQ_RATE1))) { x.c->xrate[r][0] = ea->rate0; x.c->xrate[r][1] = ea->rate1; }
   }
   // ---- tick: a new step's observation starts empty
-  H.nobs = 0; H.obs_success = 0; H.obs_act_type = RA_NONE; H.new_sess_host = 0xFF; H.rsc_listed = 0;
+  hdr_tick_reset(H);
   for (int w = 0; w < 5; ++w) { A.obs_has[0][w] = 0; A.obs_has[1][w] = 0; }
-  Act q = H.queue, ex;
-  q.ticks--;
-  if (q.ticks < 1) { ex = q; q.busy = 0; }
+  ActW q = act_tick(hdr_queue(H)), ex;
+  if (aget<AW_TICKS>(q) < 1) { ex = q; q = aset<AW_BUSY>(q, 0); }
   else {
-    ex.type = RA_SLEEP; ex.host = 0; ex.arg = 0; ex.ticks = 0; ex.sid = 0; ex.busy = 0;
-    H.obs_success = T_IN_PROGRESS; H.obs_act_type = RA_NONE; H.obs_act_host = 0; H.obs_act_arg = 0;   // obs_first(IN_PROGRESS)
+    ex = act_word(RA_SLEEP, 0, 0, 0, 0, 0);
+    H.w[hdr_field(RH_OBS_SUCCESS).word] = hdr_obs_word(T_IN_PROGRESS, RA_NONE, 0, 0);   // obs_first(IN_PROGRESS)
   }
-  H.queue = q;
-  H.exec_type = ex.type; H.exec_host = ex.host;
+  hdr_set_queue(H, q);
+  hset<RH_EXEC_TYPE>(H, aget<AW_TYPE>(ex)); hset<RH_EXEC_HOST>(H, aget<AW_HOST>(ex));
   int dropped = 0;
   CC4_FT(x, r, 2);
-  if (ex.type <= RA_WITHDRAW && rs_find_id(s, A, ex.sid, H.nsess) < 0) { ex.type = RA_NONE; dropped = 1; }
+  if (aget<AW_TYPE>(ex) <= RA_WITHDRAW && rs_find_id(s, A, (int)aget<AW_SID>(ex), (int)hget<RH_NSESS>(H)) < 0) { ex = aset<AW_TYPE>(ex, RA_NONE); dropped = 1; }
   CC4_FT(x, r, 3);
-  s->rexec[r] = ex;
-  A.h = H;
+  act_store(&s->rexec[r], ex);
+  hdr_store(&A.h, H);
   CC4_FT(x, r, 4);
   return dropped;
 }
@@ -2540,10 +2559,10 @@ CC4_HD bool blue_exec_independent(const EnvState* s) {
 // duration queue of one blue agent (SC:251-265)
 CC4_HD void step_tick_blue(Ctx x, int b) {
   EnvState* s = x.s;
-  Act& q = s->blue[b].queue;
-  q.ticks--;
-  if (q.ticks < 1) { s->bexec[b] = q; q.busy = 0; }
-  else { Act z; z.type = BA_SLEEP; z.host = 0; z.arg = 0; z.ticks = 0; z.sid = 0; z.busy = 0; s->bexec[b] = z; }
+  ActW q = act_tick(act_load(&s->blue[b].queue));
+  if (aget<AW_TICKS>(q) < 1) { act_store(&s->bexec[b], q); q = aset<AW_BUSY>(q, 0); }
+  else act_store(&s->bexec[b], act_word(BA_SLEEP, 0, 0, 0, 0, 0));
+  act_store(&s->blue[b].queue, q);
 }
 // returns the BlueRewardMachine penalty of this green agent's action (<= 0)
 // pre: block 0 of the agent's stream when the caller has it already (rng_preload), else null
@@ -2628,10 +2647,11 @@ __device__ __forceinline__ uint32_t red_foreign_wave(const EnvState* s, int lane
 // pre: block 0 of the agent's action stream when the caller has it already (rng_preload), else null
 CC4_HD void step_red_exec_agent(Ctx x, int r, const uint32_t* pre = nullptr) {
   EnvState* s = x.s;
-  if (s->rexec[r].type == RA_NONE) return;
+  const ActW w = act_load(&s->rexec[r]);
+  if (aget<AW_TYPE>(w) == RA_NONE) return;
   rng_set_stream(x.r, ST_RED_EXE + (uint32_t)r);
   if (pre) rng_preload(x.r, pre);
-  red_execute(x, r, s->rexec[r]);
+  red_execute(x, r, w);
 }
 // Red actions of different agents commute when they name different hosts (each action reads/writes its own agent's
 // tables, its target host and commutative event bits); DiscoverRemoteSystems only reads the topology.  Returns the set of
@@ -2723,9 +2743,12 @@ CC4_HD void step_monitor_pend(Ctx x) {  // session.add_sus_pids for the pid-carr
   s->npend = 0;
 }
 CC4_HD void step_rsc(Ctx x, int r) {
-  if (!x.s->red[r].h.active) return;
+  RedHdr* const h = &x.s->red[r].h;
+  RedHdrW H = hdr_load(h, HDR_HI);   // active, obs_success, rsc_listed, rsc_dirty: one 16-byte read, one 16-byte write
+  if (!hget<RH_ACTIVE>(H)) return;
   rng_set_stream(x.r, ST_RED_RSC + (uint32_t)r);
-  red_session_check(x, r);
+  red_session_check(x, r, H);
+  hdr_store(h, H, HDR_HI);
 }
 // the messages submitted with this step, agent b's row (read back by the observation encode of the same step only, so the
 // lane-parallel kernel stores them when the actions are submitted and step_end skips the copy)
@@ -2738,7 +2761,9 @@ CC4_HD void step_messages(EnvState* s, const uint8_t* messages, int b) {
 // step_end's Impact term of agent r alone (the one-wave kernel: agent r's lane adds it to EnvState.brm ahead of step_end, which then skips its loop)
 CC4_HD int step_impact_term(const EnvState* s, int r) {
   const RedHdr& h = s->red[r].h;
-  return (h.exec_type == RA_IMPACT && h.nsess > 0) ? reward_table(s->phase, h_subnet(h.exec_host), RW_RIA) : 0;
+  static_assert(hdr_field(RH_EXEC_TYPE).word == hdr_field(RH_EXEC_HOST).word, "exec_type and exec_host are one word");
+  const uint32_t w = hdr_word(&h, hdr_field(RH_EXEC_TYPE).word);
+  return (wget<RH_EXEC_TYPE>(w) == RA_IMPACT && h.nsess > 0) ? reward_table(s->phase, h_subnet((int)wget<RH_EXEC_HOST>(w)), RW_RIA) : 0;
 }
 // impact: add the six agents' Impact terms here (false: the caller has added them to brm already, step_impact_term)
 CC4_HD void step_end(Ctx x, const uint8_t* messages, bool copy_msgs = true, bool impact = true) {

@@ -241,16 +241,17 @@ __device__ __forceinline__ void philox1_body(StepArgs a, const int e, const uint
           // host): one pass of the wave for all six (rs_wave_query; `side` is uniform, every lane is here) instead of a list scan inside each
           // action body.  The serial rounds run after other agents' actions and look up for themselves (pe.ok = false).
           RedPre pe;
+          const ActW rex = go ? act_load(&s->rexec[r]) : act_word(RA_NONE, 0, 0, 0, 0, 0);   // the agent's record, read once as one word
           if (side) {
-            const bool look = go && s->rexec[lane].type < RA_SLEEP;              // (Sleep / InvalidAction / none look nothing up)
-            pe = rs_wave_query(s, lane, look ? (int)s->rexec[lane].sid : -1, look ? (int)s->rexec[lane].host : -1);
+            const bool look = aget<AW_TYPE>(rex) < RA_SLEEP;                        // (Sleep / InvalidAction / none look nothing up)
+            pe = rs_wave_query(s, lane, look ? (int)aget<AW_SID>(rex) : -1, look ? (int)aget<AW_HOST>(rex) : -1);
           }
           if (go) {
             unsigned long long t0 = xe.aprof ? clock64() : 0;
-            if (s->rexec[r].type != RA_NONE) {                                      // == step_red_exec_agent
+            if (aget<AW_TYPE>(rex) != RA_NONE) {                                    // == step_red_exec_agent
               rng_set_stream(&rl, ST_RED_EXE + (uint32_t)r);
               if (side) rng_preload(&rl, pre_re);
-              red_execute(xe, r, s->rexec[r], pe);
+              red_execute(xe, r, rex, pe);
             }
             if (xe.aprof) xe.aprof[1] += clock64() - t0;
           }

@@ -146,7 +146,7 @@ struct alignas(2) ObsEnt { uint8_t host; uint8_t flags; };
 
 // A red agent's scalar fields, 32 bytes = two 16-byte vectors: the policy / tick path of a step reads them as one batch into
 // registers, works there, and writes them back once (every field read separately is an LDS round trip on the agent's
-// dependency chain).
+// dependency chain) -- through the word view below (RedHdrW), not a copy of the struct.
 struct alignas(16) RedHdr {
   Act queue;                         // actions_in_progress[agent]
   uint16_t as_subnet;                // ActionSpace.subnet known bits
@@ -166,6 +166,158 @@ struct alignas(16) RedHdr {
   uint8_t pad[1];
 };
 static_assert(sizeof(RedHdr) == 32, "RedHdr is two 16-byte vectors");
+
+// ---- The header and the action records as words. The layout in memory is RedHdr / Act, bit for bit; this is how the policy / tick
+// path holds them: the header as eight 32-bit words, an Act as one 64-bit word, every field a (word, shift, width) taken from offsetof / sizeof of
+// the structs, so a get is one bit-field extract and a set one insert.  Left as a struct copy, the compiler gives every byte field a register of
+// its own, reads the 32 bytes with eight narrow LDS instructions and puts them together again in front of eight narrow writes.
+struct WField { int word, shift, width; };
+constexpr WField wfield_at(size_t off, size_t size) { return WField{(int)(off / 4), (int)(off % 4) * 8, (int)size * 8}; }
+constexpr uint32_t wfield_max(WField f) { return f.width >= 32 ? 0xFFFFFFFFu : ((1u << f.width) - 1u); }
+constexpr uint32_t wfield_mask(WField f) { return wfield_max(f) << f.shift; }
+enum : int {
+  RH_Q_TYPE, RH_Q_HOST, RH_Q_ARG, RH_Q_TICKS, RH_Q_SID, RH_Q_BUSY, RH_AS_SUBNET, RH_FSM_STEP, RH_NEW_SESS_ID, RH_NSESS, RH_NKNOWN, RH_FSM_N,
+  RH_NOBS, RH_NLIVE, RH_ACTIVE, RH_OBS_SUCCESS, RH_OBS_ACT_TYPE, RH_OBS_ACT_HOST, RH_OBS_ACT_ARG, RH_EXEC_TYPE, RH_EXEC_HOST, RH_NEW_SESS_HOST,
+  RH_START_HOST, RH_RSC_DIRTY, RH_RSC_LISTED, RH_FSM_DIRTY, RH_NFIELDS
+};
+enum : int { AW_TYPE, AW_HOST, AW_ARG, AW_TICKS, AW_SID, AW_BUSY, AW_NFIELDS };
+#define CC4_WF(T, m) wfield_at(offsetof(T, m), sizeof(T::m))
+#define CC4_WFQ(m) wfield_at(offsetof(RedHdr, queue) + offsetof(Act, m), sizeof(Act::m))
+constexpr WField act_field(int f) {    // in the record's two words
+  switch (f) {
+    case AW_TYPE: return CC4_WF(Act, type);   case AW_HOST: return CC4_WF(Act, host);   case AW_ARG: return CC4_WF(Act, arg);
+    case AW_TICKS: return CC4_WF(Act, ticks); case AW_SID: return CC4_WF(Act, sid);     default: return CC4_WF(Act, busy);
+  }
+}
+constexpr WField hdr_field(int f) {
+  switch (f) {
+    case RH_Q_TYPE: return CC4_WFQ(type);   case RH_Q_HOST: return CC4_WFQ(host);   case RH_Q_ARG: return CC4_WFQ(arg);
+    case RH_Q_TICKS: return CC4_WFQ(ticks); case RH_Q_SID: return CC4_WFQ(sid);     case RH_Q_BUSY: return CC4_WFQ(busy);
+    case RH_AS_SUBNET: return CC4_WF(RedHdr, as_subnet);         case RH_FSM_STEP: return CC4_WF(RedHdr, fsm_step);
+    case RH_NEW_SESS_ID: return CC4_WF(RedHdr, new_sess_id);     case RH_NSESS: return CC4_WF(RedHdr, nsess);
+    case RH_NKNOWN: return CC4_WF(RedHdr, nknown);               case RH_FSM_N: return CC4_WF(RedHdr, fsm_n);
+    case RH_NOBS: return CC4_WF(RedHdr, nobs);                   case RH_NLIVE: return CC4_WF(RedHdr, nlive);
+    case RH_ACTIVE: return CC4_WF(RedHdr, active);               case RH_OBS_SUCCESS: return CC4_WF(RedHdr, obs_success);
+    case RH_OBS_ACT_TYPE: return CC4_WF(RedHdr, obs_act_type);   case RH_OBS_ACT_HOST: return CC4_WF(RedHdr, obs_act_host);
+    case RH_OBS_ACT_ARG: return CC4_WF(RedHdr, obs_act_arg);     case RH_EXEC_TYPE: return CC4_WF(RedHdr, exec_type);
+    case RH_EXEC_HOST: return CC4_WF(RedHdr, exec_host);         case RH_NEW_SESS_HOST: return CC4_WF(RedHdr, new_sess_host);
+    case RH_START_HOST: return CC4_WF(RedHdr, start_host);       case RH_RSC_DIRTY: return CC4_WF(RedHdr, rsc_dirty);
+    case RH_RSC_LISTED: return CC4_WF(RedHdr, rsc_listed);       default: return CC4_WF(RedHdr, fsm_dirty);
+  }
+}
+#undef CC4_WF
+#undef CC4_WFQ
+// every field lies inside one word, no two share a bit, and together they are the struct less its padding
+constexpr bool wfields_tile(WField (*field)(int), int nfields, int nwords, int pad_bits) {
+  uint32_t used[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  int bits = 0;
+  for (int f = 0; f < nfields; ++f) {
+    const WField d = field(f);
+    if (d.word < 0 || d.word >= nwords || d.width < 8 || d.shift + d.width > 32 || (used[d.word] & wfield_mask(d))) return false;
+    used[d.word] |= wfield_mask(d); bits += d.width;
+  }
+  return bits + pad_bits == 32 * nwords;
+}
+static_assert(wfields_tile(hdr_field, RH_NFIELDS, 8, 8 * (int)sizeof(RedHdr::pad)), "the header's word fields are RedHdr's members");
+static_assert(wfields_tile(act_field, AW_NFIELDS, 2, 0) && sizeof(Act) == 8, "the action word's fields are Act's members");
+static_assert(hdr_field(RH_Q_TYPE).word == act_field(AW_TYPE).word && hdr_field(RH_Q_BUSY).word == act_field(AW_BUSY).word && offsetof(RedHdr, queue) == 0,
+              "RedHdr.queue is words 0 and 1 of the header: the header's queue as an action word is w[0] | w[1] << 32");
+static_assert(hdr_field(RH_OBS_SUCCESS).word == 5 && hdr_field(RH_OBS_SUCCESS).shift == 0 && hdr_field(RH_OBS_ACT_TYPE).word == 5 &&
+              hdr_field(RH_OBS_ACT_HOST).word == 5 && hdr_field(RH_OBS_ACT_ARG).word == 5, "obs_first's four bytes are word 5, obs_success lowest");
+static_assert(act_field(AW_TICKS).word == 0 && act_field(AW_TICKS).shift == 24 && hdr_field(RH_FSM_STEP).shift == 16 && hdr_field(RH_FSM_STEP).width == 16,
+              "ticks and fsm_step are the top fields of their words: a count on the word wraps as the member does");
+
+struct RedHdrW { uint32_t w[8]; };
+typedef uint64_t ActW;
+template <int F> CC4_HD uint32_t hget(const RedHdrW& H) { constexpr WField d = hdr_field(F); return (H.w[d.word] >> d.shift) & wfield_max(d); }
+template <int F> CC4_HD void hset(RedHdrW& H, uint32_t v) {
+  constexpr WField d = hdr_field(F);
+  H.w[d.word] = (H.w[d.word] & ~wfield_mask(d)) | ((v & wfield_max(d)) << d.shift);
+}
+// field += 1, wrapping at the member's width
+template <int F> CC4_HD void hinc(RedHdrW& H) {
+  constexpr WField d = hdr_field(F);
+  if (d.shift + d.width == 32) H.w[d.word] += 1u << d.shift; else hset<F>(H, hget<F>(H) + 1u);
+}
+template <int F> CC4_HD uint32_t aget(ActW a) { constexpr WField d = act_field(F); return ((uint32_t)(a >> (32 * d.word)) >> d.shift) & wfield_max(d); }
+template <int F> CC4_HD ActW aset(ActW a, uint32_t v) {
+  constexpr WField d = act_field(F);
+  return (a & ~((uint64_t)wfield_mask(d) << (32 * d.word))) | ((uint64_t)(v & wfield_max(d)) << (32 * d.word + d.shift));
+}
+CC4_HD constexpr ActW act_word(uint32_t type, uint32_t host, uint32_t arg, uint32_t ticks, uint32_t sid, uint32_t busy) {
+  return (uint64_t)((type & 0xFFu) << act_field(AW_TYPE).shift | (host & 0xFFu) << act_field(AW_HOST).shift | (arg & 0xFFu) << act_field(AW_ARG).shift |
+                    (ticks & 0xFFu) << act_field(AW_TICKS).shift) |
+         (uint64_t)((sid & 0xFFFFu) << act_field(AW_SID).shift | (busy & 0xFFFFu) << act_field(AW_BUSY).shift) << 32;
+}
+CC4_HD ActW act_tick(ActW a) { return (a & 0xFFFFFFFF00000000ull) | (uint32_t)((uint32_t)a - (1u << 24)); }   // ticks-- as the uint8_t member wraps
+CC4_HD ActW act_pack(const Act& a) { return act_word(a.type, a.host, a.arg, a.ticks, a.sid, a.busy); }
+CC4_HD Act act_unpack(ActW w) {
+  Act a; a.type = (uint8_t)aget<AW_TYPE>(w); a.host = (uint8_t)aget<AW_HOST>(w); a.arg = (uint8_t)aget<AW_ARG>(w); a.ticks = (uint8_t)aget<AW_TICKS>(w);
+  a.sid = (uint16_t)aget<AW_SID>(w); a.busy = (uint16_t)aget<AW_BUSY>(w);
+  return a;
+}
+CC4_HD ActW hdr_queue(const RedHdrW& H) { return (uint64_t)H.w[0] | (uint64_t)H.w[1] << 32; }
+CC4_HD void hdr_set_queue(RedHdrW& H, ActW q) { H.w[0] = (uint32_t)q; H.w[1] = (uint32_t)(q >> 32); }
+// The tick's resets as masks (a new step's observation starts empty): nobs = 0, obs_success = 0, obs_act_type = RA_NONE, new_sess_host = 0xFF, rsc_listed = 0
+CC4_HD void hdr_tick_reset(RedHdrW& H) {
+  H.w[hdr_field(RH_NOBS).word] &= ~wfield_mask(hdr_field(RH_NOBS));
+  uint32_t& ow = H.w[hdr_field(RH_OBS_SUCCESS).word];   // (obs_act_type shares it: static_assert above)
+  ow = (ow & ~(wfield_mask(hdr_field(RH_OBS_SUCCESS)) | wfield_mask(hdr_field(RH_OBS_ACT_TYPE)))) | (uint32_t)RA_NONE << hdr_field(RH_OBS_ACT_TYPE).shift;
+  H.w[hdr_field(RH_NEW_SESS_HOST).word] |= wfield_mask(hdr_field(RH_NEW_SESS_HOST));
+  H.w[hdr_field(RH_RSC_LISTED).word] &= ~wfield_mask(hdr_field(RH_RSC_LISTED));
+}
+// obs_first(success, type, host, arg) as one word: the first observation of a step sets all four, a later one nothing
+CC4_HD constexpr uint32_t hdr_obs_word(uint32_t success, uint32_t type, uint32_t host, uint32_t arg) {
+  return (success & 0xFFu) | (type & 0xFFu) << hdr_field(RH_OBS_ACT_TYPE).shift | (host & 0xFFu) << hdr_field(RH_OBS_ACT_HOST).shift | (arg & 0xFFu) << hdr_field(RH_OBS_ACT_ARG).shift;
+}
+// Load and store.  On the device two 16-byte reads and two 16-byte writes (of LDS, where the row is staged); the loaded words are pinned in vector
+// registers, or the optimiser narrows the reads back to the bytes each use wants.  On the host the same bytes through memcpy.
+#if defined(__HIP_DEVICE_COMPILE__)
+typedef uint32_t cc4_u32x4 __attribute__((ext_vector_type(4)));
+#endif
+enum : int { HDR_LO = 1, HDR_HI = 2, HDR_BOTH = 3 };   // which 16-byte vector(s) a load reads (the other's words are 0) or a store writes: a vector no path wrote may be skipped
+CC4_HD RedHdrW hdr_load(const RedHdr* h, int which = HDR_BOTH) {
+  RedHdrW H;
+#if defined(__HIP_DEVICE_COMPILE__)
+  cc4_u32x4 a = {0u, 0u, 0u, 0u}, b = {0u, 0u, 0u, 0u};
+  if (which & HDR_LO) { __builtin_memcpy(&a, h, 16); asm volatile("" : "+v"(a)); }
+  if (which & HDR_HI) { __builtin_memcpy(&b, reinterpret_cast<const char*>(h) + 16, 16); asm volatile("" : "+v"(b)); }
+  H.w[0] = a.x; H.w[1] = a.y; H.w[2] = a.z; H.w[3] = a.w; H.w[4] = b.x; H.w[5] = b.y; H.w[6] = b.z; H.w[7] = b.w;
+#else
+  for (int i = 0; i < 8; ++i) H.w[i] = 0;
+  if (which & HDR_LO) __builtin_memcpy(H.w, h, 16);
+  if (which & HDR_HI) __builtin_memcpy(H.w + 4, reinterpret_cast<const char*>(h) + 16, 16);
+#endif
+  return H;
+}
+// one word of the header, for a phase that reads two fields of it and owns nothing (a read needs no owner)
+CC4_HD uint32_t hdr_word(const RedHdr* h, int word) {
+  uint32_t w; __builtin_memcpy(&w, reinterpret_cast<const char*>(__builtin_assume_aligned(h, 16)) + 4 * word, 4);
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile("" : "+v"(w));
+#endif
+  return w;
+}
+template <int F> CC4_HD uint32_t wget(uint32_t w) { constexpr WField d = hdr_field(F); return (w >> d.shift) & wfield_max(d); }   // field F of its own word
+CC4_HD void hdr_store(RedHdr* h, const RedHdrW& H, int which = HDR_BOTH) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  if (which & HDR_LO) { cc4_u32x4 a = {H.w[0], H.w[1], H.w[2], H.w[3]}; asm volatile("" : "+v"(a)); __builtin_memcpy(h, &a, 16); }
+  if (which & HDR_HI) { cc4_u32x4 b = {H.w[4], H.w[5], H.w[6], H.w[7]}; asm volatile("" : "+v"(b)); __builtin_memcpy(reinterpret_cast<char*>(h) + 16, &b, 16); }
+#else
+  if (which & HDR_LO) __builtin_memcpy(h, H.w, 16);
+  if (which & HDR_HI) __builtin_memcpy(reinterpret_cast<char*>(h) + 16, H.w + 4, 16);
+#endif
+}
+// one 8-byte read / write per record (the word pinned like the header's: a load that two extracts share is otherwise split into their bytes)
+CC4_HD ActW act_load(const Act* a) {
+  ActW w; __builtin_memcpy(&w, a, 8);
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile("" : "+v"(w));
+#endif
+  return w;
+}
+CC4_HD void act_store(Act* a, ActW w) { __builtin_memcpy(a, &w, 8); }
+
 struct alignas(16) RedAgent {
   alignas(8) uint8_t sord[MAX_RS];   // state.sessions[agent] in dict order: pool slots (read eight at a time)
   uint32_t known_bm[8];              // ActionSpace.server_session keys with value True as a bitmap over ids 0..255.  The same set in
