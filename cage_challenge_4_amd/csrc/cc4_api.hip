@@ -4,6 +4,7 @@
 #include "cc4_host.h"
 #include "cc4_export.h"
 #include "cc4_features.h"
+#include "cc4_red_view.h"
 
 static thread_local std::string g_create_err;
 
@@ -176,7 +177,7 @@ int launch_step(cc4_handle* h, const int32_t* d_actions, const uint8_t* d_msgs, 
   if (h->ext_seen && h->ext_dirty && !ext_uploaded) {     // this step submits no red / green action: every record says so
     if (join_groups(h)) return -1;
     HIPCHK(h, hipMemsetAsync(h->d_ext, 0xFF, (size_t)h->cfg.num_envs * EXT_PER_ENV * sizeof(ExtAct), h->stream));
-    h->ext_dirty = false;
+    h->ext_dirty = false; h->ext_green_dirty = false;
   }
   const bool full = h->evlog_on || h->ext_seen;
   // the byte-observation buffer about to be overwritten may still be read by an overlapped all-gather
@@ -651,7 +652,7 @@ int cc4_step_ex(cc4_handle* h, const int32_t* actions, const uint8_t* messages, 
     }
   }
   HIPCHK(h, hipMemcpyAsync(h->d_ext, h->h_ext.data(), h->h_ext.size() * sizeof(ExtAct), hipMemcpyHostToDevice, h->stream));
-  h->ext_seen = true; h->ext_dirty = true;
+  h->ext_seen = true; h->ext_dirty = true; h->ext_green_dirty = green != nullptr;
   if (actions) HIPCHK(h, hipMemcpyAsync(h->d_actions, actions, n * NBLUE * sizeof(int32_t), hipMemcpyDefault, h->stream));
   if (messages) HIPCHK(h, hipMemcpyAsync(h->d_msgs, messages, n * NBLUE * MSG_LEN, hipMemcpyDefault, h->stream));
   if (launch_step(h, actions ? h->d_actions : nullptr, messages ? h->d_msgs : nullptr, false, 0, 0, true, true)) return -1;
@@ -682,6 +683,70 @@ int cc4_edit_state(cc4_handle* h, int32_t env, int32_t op, int32_t a0, int32_t a
 int cc4_step_device(cc4_handle* h, const int32_t* d_actions, const uint8_t* d_messages) {
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   return launch_step(h, d_actions, d_messages, false, 0, 0, false, true);
+}
+
+// ---- the red agents as learners (include/cc4.h; cc4_k_red.hip; the definition: cc4_red_view.h).
+// cc4_step_device with the red agents' actions from a device tensor: k_red_submit on the main stream, behind whatever the group streams still hold (it
+// reads the rows as they stand before the step and writes records the last step's kernels may still read), fills d_ext; the step's launches follow with
+// the records marked as uploaded.  No upload, no host copy, no host wait.
+int cc4_step_red_device(cc4_handle* h, const int32_t* d_actions, const uint8_t* d_messages, const int32_t* d_red) {
+  const char* who = "cc4_step_red_device";
+  if (!d_red) { h->err = std::string(who) + ": no red actions (cc4_step_device steps without them)"; return -2; }
+  if (h->rollout_k > 0) { h->err = std::string(who) + ": a rollout is in flight on this handle: cc4_rollout_end first"; return -2; }
+  if (h->comm) { h->err = std::string(who) + ": not on a handle with a communicator"; return -2; }
+  if (reinterpret_cast<uintptr_t>(d_red) % 16) { h->err = std::string(who) + ": the red actions must be 16-byte aligned"; return -2; }
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  if (join_groups(h)) return -1;
+  const int n = h->cfg.num_envs;
+  if (!h->d_ext) HIPCHK(h, hipMalloc(&h->d_ext, (size_t)n * EXT_PER_ENV * sizeof(ExtAct)));     // (ext_green_dirty is still true: the kernel writes every record)
+  RedSubmitArgs a{h->d_state, d_red, h->d_ext, n, h->ext_green_dirty ? 1 : 0, h->d_copy_fault};
+  hipLaunchKernelGGL(k_red_submit, dim3((n * NRED + 255) / 256), dim3(256), 0, h->stream, a);
+  HIPCHK(h, hipGetLastError());
+  h->ext_seen = true; h->ext_dirty = true; h->ext_green_dirty = false;
+  return launch_step(h, d_actions, d_messages, false, 0, 0, true, true);
+}
+// What each red agent knows as tensors: one launch on the main stream behind the group streams, no host synchronisation; it only reads rows.
+int cc4_red_view_device(cc4_handle* h, const void* d_bank, int32_t capacity, const int32_t* d_ids, int32_t n, uint8_t* d_hosts, int32_t* d_scalars) {
+  const char* who = "cc4_red_view_device";
+  if (h->rollout_k > 0) { h->err = std::string(who) + ": a rollout is in flight on this handle: cc4_rollout_end first"; return -2; }
+  if (n < 0) { h->err = std::string(who) + ": n < 0"; return -2; }
+  if (n == 0) return 0;
+  if (!d_hosts || reinterpret_cast<uintptr_t>(d_hosts) % 16 || reinterpret_cast<uintptr_t>(d_scalars) % 4) {
+    h->err = std::string(who) + ": the host-view buffer is required and must be 16-byte aligned (the agent words: 4-byte aligned or NULL)"; return -2;
+  }
+  if (d_bank && capacity < 1) { h->err = std::string(who) + ": a bank needs a capacity of at least one slot"; return -2; }
+  if (reinterpret_cast<uintptr_t>(d_bank) % 64) { h->err = std::string(who) + ": a bank must be 64-byte aligned"; return -2; }
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  if (join_groups(h)) return -1;
+  RedViewArgs a{h->d_state, static_cast<const uint8_t*>(d_bank), slot_bytes(h->cold_row), d_ids, n, d_bank ? capacity : h->cfg.num_envs,
+                h->cfg.steps, h->cfg.rng_mode, d_hosts, d_scalars, h->d_copy_fault};
+  hipLaunchKernelGGL(k_red_view, dim3(n), dim3(WAVE), 0, h->stream, a);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+// The same definitions on the host, from one hot row (cc4_get_state, a checkpoint): no device, no handle.
+static EnvState* row_copy(const void* hot_row) {
+  EnvState* s = static_cast<EnvState*>(aligned_alloc(alignof(EnvState), sizeof(EnvState)));   // (the caller's bytes may sit at any address)
+  if (s) memcpy(s, hot_row, sizeof(EnvState));
+  return s;
+}
+int cc4_red_view_from_row(const void* hot_row, uint8_t* hosts, int32_t* scalars) {
+  if (!hot_row || !hosts) return -2;
+  EnvState* s = row_copy(hot_row);
+  if (!s) return -1;
+  red_view_from_row(s, hosts, scalars);
+  free(s);
+  return 0;
+}
+int cc4_red_record_from_row(const void* hot_row, int32_t agent, const int32_t* words, cc4_agent_action* out) {
+  if (!hot_row || !words || !out || agent < 0 || agent >= NRED) return -2;
+  EnvState* s = row_copy(hot_row);
+  if (!s) return -1;
+  ExtActW rec;
+  const bool ok = red_record(s, agent, words[0], words[1], words[2], words[3], &rec);
+  memcpy(out, rec.w, sizeof(*out));
+  free(s);
+  return ok ? 0 : 1;
 }
 
 // ---- group-wise stepping for a policy that lives on the GPU.  A step of a large batch is one launch per episode group, each group on its

@@ -1,5 +1,5 @@
 // cc4_args.h -- what the host side and the kernels of libcc4.so share: the constants, the argument blocks of the kernels (StepArgs, XchgArgs, RunArgs,
-// PlanArgs, ResetArgs, CopyArgs, FeatArgs), the snapshot-slot layout, and the register budgets of the kernels.  No device helper (cc4_kernels.h) and nothing of
+// PlanArgs, ResetArgs, CopyArgs, FeatArgs, RedSubmitArgs, RedViewArgs), the snapshot-slot layout, and the register budgets of the kernels.  No device helper (cc4_kernels.h) and nothing of
 // the C++ host library (cc4_host.h).  The index arithmetic of the persistent schedule -- partitions, tickets, runs, the progress word -- is in cc4_sched.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -197,5 +197,25 @@ struct FeatArgs {
   int count, cap, steps, rng_mode;                       // cap: episodes of the handle / slots of the bank
   uint8_t* hosts;                                        // [count][137][16], 16-byte aligned
   int32_t* glob;                                         // [count][32] or null
+  uint32_t* fault;
+};
+
+// ---- the red agents as learners (cc4_k_red.hip; the definition: cc4_red_view.h).  cc4_step_red_device: red[e][r] = (type, host, arg, session) becomes
+// record r of ext[e]; clear_green: the green records of every episode are set to none as well.
+struct RedSubmitArgs {
+  const EnvState* st;                                    // the handle's hot rows as they stand before the step (CC4_RED_SID_AUTO)
+  const int32_t* red;                                    // [n][NRED][4], 16-byte aligned
+  ExtAct* ext;                                           // [n][EXT_PER_ENV]
+  int n, clear_green;
+  uint32_t* fault;
+};
+// cc4_red_view_device: entry i reads episode ids[i] (null: i) of the handle, or the hot row inside slot ids[i] of a snapshot bank, as FeatArgs does
+struct RedViewArgs {
+  const EnvState* st;
+  const uint8_t* bank; size_t slot;
+  const int32_t* ids;
+  int count, cap, steps, rng_mode;
+  uint8_t* hosts;                                        // [count][NRED][137][8], 16-byte aligned
+  int32_t* scal;                                         // [count][NRED][16] or null
   uint32_t* fault;
 };

@@ -160,6 +160,11 @@ struct cc4_handle {
   bool multistep = false;         // k_run_philox: cc4_run_random_steps as ONE launch, every block looping over the steps of its episode
   ExtAct* d_ext = nullptr;        // [num_envs][EXT_PER_ENV]
   bool ext_seen = false, ext_dirty = false;   // dirty: d_ext holds the records of an earlier step
+  // ext_green_dirty: false only while the GREEN records of d_ext are known to be all XA_NONE; cc4_step_red_device then writes its six red records per episode
+  // and nothing else, otherwise it sets the green records to none as well.  True from the start (d_ext not allocated, or allocated and never written: a
+  // cc4_step_ex that refused its records has allocated it already).  Cleared by: k_red_submit with clear_green (cc4_step_red_device), the upload of a
+  // cc4_step_ex without green actions, the memset of launch_step.  Set by: the upload of a cc4_step_ex with green actions.
+  bool ext_green_dirty = true;
   std::vector<ExtAct> h_ext;
   bool full_obs_next = true;      // the next step launch rewrites every observation value (fresh handle, restored state)
   uint32_t full_obs_gmask = 0;    // ... per group, for the group-wise launches of cc4_step_group_device

@@ -21,7 +21,7 @@ class CC4TorchVecEnv:
     autoreset, red_policy, green_policy, topology_seed, blue_policy, strict); the tensors live on cuda:<device_id>.
 
     reset(seeds=None, env_mask=None) -> (obs, info)             seeds / env_mask as CC4VecEnv.reset
-    step(actions, messages=None)     -> (obs, reward, done, info)
+    step(actions, messages=None, red_actions=None) -> (obs, reward, done, info)
         actions   integer tensor [N, 5] of wrapper action indices on the env's device (negative: no action), any integer dtype;
         messages  optional [N, 5, 8] tensor of 0 / 1 bytes;
         obs [N, 578] obs_dtype, reward [N] float32, done [N] bool, info {'action_mask': [N, 570] bool, 'err': [N] int32}.
@@ -48,6 +48,13 @@ class CC4TorchVecEnv:
 
     The privileged global state for a centralised critic (include/cc4.h cc4_state_features_device; cage_challenge_4_amd.state_features):
     state_features(ids=None, bank=None, out=None) -> (hosts [n, 137, 16] uint8, glob [n, 32] int32)   of the env's episodes, or of the slots of a bank
+
+    Red agents as learners (include/cc4.h cc4_step_red_device, cc4_red_view_device; cage_challenge_4_amd.red_view):
+    step(actions, messages=None, red_actions=t)   t integer tensor [N, 6, 4] on the device: (type, host, arg, session) per red agent; type -1: the
+                                                  agent's scripted policy acts; session -1: its first listed session.  A refused record (a type,
+                                                  host or subnet out of range) becomes "no action", and check_errors() raises CC4EngineError for it.
+                                                  Red's reward is -reward.  An env that has taken red actions runs the full builds of its step kernel.
+    red_view(ids=None, bank=None, out=None) -> (hosts [n, 6, 137, 8] uint8, scalars [n, 6, 16] int32)   what each red agent knows
 
     Mixed opponents in one batch (include/cc4.h cc4_set_policies_device, cc4_reset_device):
     set_opponents(red=None, green=None, blue=None)   integer tensors [N] on the device: the classes each episode regenerates into from its next
@@ -78,6 +85,7 @@ class CC4TorchVecEnv:
             self._actions = torch.zeros((n, L.NUM_BLUE), dtype=torch.int32, **z)
             self._fresh = torch.zeros(n, dtype=torch.uint8, **z)     # episodes a copy overwrote since the last check_errors (strict mode: new episodes)
             self._messages = torch.zeros((n, L.NUM_BLUE, L.MSG_LEN), dtype=torch.uint8, **z)
+            self._red = None         # [N, 6, 4] int32 staging of step(red_actions=...), allocated on first use
         vp = ctypes.c_void_p
         self._p_out = (vp(self.obs.data_ptr()), vp(self.action_mask.data_ptr()), vp(self.reward.data_ptr()), vp(self.done.data_ptr()),
                        vp(self.err.data_ptr()))
@@ -147,19 +155,33 @@ class CC4TorchVecEnv:
             self._outputs(s)
         return self.obs, self._info()
 
-    def step(self, actions, messages=None):
+    def step(self, actions, messages=None, red_actions=None):
         with torch.cuda.device(self.device):
             if tuple(actions.shape) != (self.num_envs, L.NUM_BLUE) or (messages is not None and tuple(messages.shape) != tuple(self._messages.shape)):
                 raise ValueError(f'actions must be [{self.num_envs}, {L.NUM_BLUE}] and messages [{self.num_envs}, {L.NUM_BLUE}, {L.MSG_LEN}]')
+            if red_actions is not None:
+                shape = (self.num_envs, L.NUM_RED, L.RED_ACT_WORDS)
+                if (not torch.is_tensor(red_actions) or tuple(red_actions.shape) != shape or red_actions.dtype.is_floating_point
+                        or red_actions.dtype == torch.bool or red_actions.device != self.device):
+                    raise ValueError(f'red_actions must be an integer tensor {list(shape)} (type, host, arg, session) on {self.device}')
+                if self._red is None:
+                    self._red = torch.zeros(shape, dtype=torch.int32, device=self.device)
             s = torch.cuda.current_stream(self.device)
             # staging copies on s: any integer dtype cast, and the env no longer depends on the lifetime of the caller's tensors
             self._actions.copy_(actions)
             if messages is not None:
                 self._messages.copy_(messages)
             lib, h, sp = self.lib, self._h, ctypes.c_void_p(s.cuda_stream)
-            rc = lib.cc4_stream_wait(h, sp) or lib.cc4_step_device(h, self._p_act, self._p_msg if messages is not None else None)
+            mp = self._p_msg if messages is not None else None
+            if red_actions is None:
+                rc = lib.cc4_stream_wait(h, sp) or lib.cc4_step_device(h, self._p_act, mp)
+            else:
+                if red_actions.dtype != torch.int32:     # (a value beyond int32 stays out of range instead of wrapping into it)
+                    red_actions = red_actions.clamp(-2 ** 31, 2 ** 31 - 1)
+                self._red.copy_(red_actions)
+                rc = lib.cc4_stream_wait(h, sp) or lib.cc4_step_red_device(h, self._p_act, mp, ctypes.c_void_p(self._red.data_ptr()))
             if rc:
-                self.venv._chk(rc, 'cc4_step_device')
+                self.venv._chk(rc, 'cc4_step_device' if red_actions is None else 'cc4_step_red_device')
             self._outputs(sp)
         return self.obs, self.reward, self.done, self._info()
 
@@ -286,6 +308,35 @@ class CC4TorchVecEnv:
                 self.venv._chk(rc, 'cc4_state_features_device')
             self.venv._chk(lib.cc4_stream_signal(h, sp), 'cc4_stream_signal')
         return hosts, glob
+
+    def red_view(self, ids=None, bank=None, out=None):
+        """What each red agent knows (cc4_red_view_device, include/cc4.h; columns and words: red_view.HOST_COLUMNS / SCALAR_WORDS) as tensors on
+        the env's device: (hosts [n, 6, 137, 8] uint8, scalars [n, 6, 16] int32).  ids, bank, out and the ordering on the current stream as
+        state_features(); no host copy, no host wait.  A faulty entry gives all-zero rows, and check_errors() raises CC4EngineError for it."""
+        with torch.cuda.device(self.device):
+            s = torch.cuda.current_stream(self.device)
+            vp = ctypes.c_void_p
+            bp, cap = self._bank(bank) if bank is not None else (None, 0)
+            if ids is not None:
+                ids = self._index(ids, 'ids')
+                n, ip = int(ids.numel()), vp(ids.data_ptr())
+            else:
+                n, ip = (cap if bank is not None else self.num_envs), None
+            shapes = ((n, L.NUM_RED, L.RED_VIEW_HOSTS, L.RED_VIEW_PER_HOST), (n, L.NUM_RED, L.RED_VIEW_SCALARS))
+            if out is None:
+                hosts = torch.empty(shapes[0], dtype=torch.uint8, device=self.device)
+                scal = torch.empty(shapes[1], dtype=torch.int32, device=self.device)
+            else:
+                hosts, scal = out
+                for x, shp, dt in ((hosts, shapes[0], torch.uint8), (scal, shapes[1], torch.int32)):
+                    if not torch.is_tensor(x) or tuple(x.shape) != shp or x.dtype != dt or x.device != self.device or not x.is_contiguous():
+                        raise ValueError(f'out must be contiguous tensors (uint8 {list(shapes[0])}, int32 {list(shapes[1])}) on {self.device}')
+            lib, h, sp = self.lib, self._h, vp(s.cuda_stream)
+            rc = lib.cc4_stream_wait(h, sp) or lib.cc4_red_view_device(h, bp, cap, ip, n, vp(hosts.data_ptr()), vp(scal.data_ptr()))
+            if rc:
+                self.venv._chk(rc, 'cc4_red_view_device')
+            self.venv._chk(lib.cc4_stream_signal(h, sp), 'cc4_stream_signal')
+        return hosts, scal
 
     def set_opponents(self, red=None, green=None, blue=None):
         """Assign opponent classes per episode from the device (cc4_set_policies_device, include/cc4.h): red (0..3), green (0..1), blue (0..1) each
