@@ -110,6 +110,13 @@ int cc4_debug_shadow_handle(cc4_handle* h, cc4_handle** out) {
   *out = h->shadow;
   return 0;
 }
+// test hook, read-only: the builds launch_range and run_one_launch pick on this handle (the one-wave step kernel or the four-wave one, the four-wave
+// kernel's register budget, the multi-step build) -- cc4_step_kernel has one name for k_step_philox<., 1 / 7 / 8>
+int cc4_debug_step_build(cc4_handle* h, int32_t out[3]) {
+  if (!h || !out) return -2;
+  out[0] = h->philox_lean ? 1 : 0; out[1] = h->philox_minw; out[2] = h->multistep_minb;
+  return 0;
+}
 // debug / test hook: every all-gather is preceded by a kernel that keeps the communication stream busy for about `us`
 // microseconds -- an exchange slower than the step, which is what makes the observation ring's reuse guard work for its living
 int cc4_debug_comm_delay_us(cc4_handle* h, int us) {

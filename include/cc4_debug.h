@@ -37,6 +37,10 @@ int cc4_debug_copy_from_device(cc4_handle* h, void* host_dst, const void* device
  * there is none.  It stays the handle's own: the read-only getters (cc4_get_states, cc4_get_rng_state, cc4_get_err, cc4_fetch, cc4_get_cold) give the
  * shadow's side of the last checked call; it is never stepped, reset or destroyed through this pointer. */
 int cc4_debug_shadow_handle(cc4_handle* h, cc4_handle** out);
+/* test hook, read-only: which builds this handle's counter-mode launches take -- out[0] 1 = the one-wave step kernel (k_step_philox1), 0 = the four-wave
+ * one; out[1] the four-wave step kernel's register budget (k_step_philox<., 1 / 7 / 8>: cc4_step_kernel names all three alike); out[2] the multi-step
+ * build (5: k_run_philox, 8: k_run_philox8; meaningful where cc4_run_kernel names one of them). */
+int cc4_debug_step_build(cc4_handle* h, int32_t out[3]);
 
 #ifdef __cplusplus
 }

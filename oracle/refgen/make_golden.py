@@ -8,10 +8,12 @@ its draw order.  numpy version is recorded (reference pins 1.26.4; this containe
 unchanged between them as far as the documented Generator API guarantees).
 
 usage: python make_golden.py            # writes tests/golden/traj_*.npz
+       python make_golden.py standin    # writes tests/golden/trajstand_*.npz: blue plays the stand-in policy's own draws (record(), akey)
 """
 import os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(__file__))
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', '..', 'tests'))
 import ref_shim  # noqa
 from CybORG import CybORG
 from CybORG.Simulator.Scenarios import EnterpriseScenarioGenerator
@@ -20,6 +22,8 @@ RED = {'fsm': (FiniteStateRedAgent, 0), 'sleep': (SleepAgent, 1), 'discovery': (
 GREEN = {'enterprise': (EnterpriseGreenAgent, 0), 'sleep': (SleepAgent, 1)}
 from CybORG.Agents.Wrappers import BlueFlatWrapper
 from blue_policies import BluePolicy, KINDS
+from golden_util import STANDIN_BASE                 # tests/golden_util.py: the action key of stand-in fixture d is STANDIN_BASE + d
+from oracle_binding import random_actions            # tests/oracle_binding.py: the host restatement of random_blue_action
 
 OUT = os.path.join(os.path.dirname(__file__), '..', '..', 'tests', 'golden')
 
@@ -34,7 +38,10 @@ def flat(obs):
     return np.concatenate([obs[f'blue_agent_{b}'] for b in range(5)]).astype(np.uint8)
 
 
-def record(seed, steps, blue, init, nsteps=None, msgs=False, red='fsm', green='enterprise'):
+def record(seed, steps, blue, init, nsteps=None, msgs=False, red='fsm', green='enterprise', akey=None):
+    # blue 'standin' (akey): the action of step t, agent b is random_blue_action(akey, t, 0, b) -- what cc4_run_random_steps(seed0, t0 = 0) draws in the kernel
+    # for the episode in slot akey - seed0 (Philox key seed0 + slot, counter (t, b, 0xB10E, 0)); written as trajstand_*.npz with akey stored
+    assert (blue == 'standin') == (akey is not None)
     # blue 'builtin': blue_agent_class=cc4BlueRandomAgent and no action submitted -- the scenario's own agent objects act
     sg = EnterpriseScenarioGenerator(blue_agent_class=cc4BlueRandomAgent if blue == 'builtin' else SleepAgent,
                                      green_agent_class=GREEN[green][0], red_agent_class=RED[red][0], steps=steps)
@@ -63,6 +70,9 @@ def record(seed, steps, blue, init, nsteps=None, msgs=False, red='fsm', green='e
         if blue == 'random':
             A[t] = [arng.integers(82), arng.integers(82), arng.integers(82), arng.integers(82), arng.integers(242)]
             acts = {f'blue_agent_{b}': int(A[t, b]) for b in range(5)}
+        elif blue == 'standin':
+            A[t] = random_actions(akey, t, 1)[0]
+            acts = {f'blue_agent_{b}': int(A[t, b]) for b in range(5)}
         elif bpol is not None:          # structured blue policy (blue_policies.py): one kind of action per agent
             A[t] = bpol.act(t)
             acts = {f'blue_agent_{b}': int(A[t, b]) for b in range(5)}
@@ -78,7 +88,11 @@ def record(seed, steps, blue, init, nsteps=None, msgs=False, red='fsm', green='e
         G[t + 1] = rng_words(env)
     pol = ('' if red == 'fsm' else f'_red{red}') + ('' if green == 'enterprise' else f'_green{green}')
     name = f"traj_seed{seed}_{blue}_{init}_{steps}{'_msg' if msgs else ''}{pol}.npz"
-    np.savez_compressed(os.path.join(OUT, name), seed=np.int64(seed), reset_seed=np.int64(reset_seed), steps=np.int32(steps),
+    extra = {}
+    if blue == 'standin':
+        name = f"trajstand_seed{seed}_d{akey - STANDIN_BASE}_{init}_{steps}{pol}.npz"
+        extra = {'akey': np.uint64(akey)}
+    np.savez_compressed(os.path.join(OUT, name), **extra, seed=np.int64(seed), reset_seed=np.int64(reset_seed), steps=np.int32(steps),
                         actions=A, obs_bits=np.packbits(O[:, 1:] if False else (O > 0).astype(np.uint8), axis=1), phase=O[:, 0].copy(),
                         phase_cols=np.array([0, 92, 184, 276, 368], np.int32), obs_phase_vals=O[:, [0, 92, 184, 276, 368]].copy(),
                         reward=R, done=D, rng=G, mask=mask, messages=M if msgs else np.zeros(0, np.uint8),
@@ -89,6 +103,11 @@ def record(seed, steps, blue, init, nsteps=None, msgs=False, red='fsm', green='e
 
 if __name__ == '__main__':
     os.makedirs(OUT, exist_ok=True)
+    if len(sys.argv) > 1 and sys.argv[1] == 'standin':    # 100-step episodes (mission phases 33 / 33 / 34), scenario seeds no other fixture uses
+        record(911, 100, 'standin', 'ctor', akey=STANDIN_BASE + 0)
+        record(912, 100, 'standin', 'ctor', red='discovery', akey=STANDIN_BASE + 64)
+        record(913, 100, 'standin', 'ctor', red='random', akey=STANDIN_BASE + 1023)
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == 'policies':   # built-in policy variants
         record(41, 500, 'random', 'ctor', red='discovery')
         record(42, 300, 'random', 'reset', red='sleep')

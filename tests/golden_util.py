@@ -51,6 +51,26 @@ def load_ctr(path):
             'red_policy': int(z['red_policy']), 'green_policy': int(z['green_policy']), 'blue_policy': int(z['blue_policy'])}
 
 
+# Stand-in fixtures (ctrstand_*.npz counter mode, trajstand_*.npz numpy stream; oracle/refgen/make_ctr_golden.py / make_golden.py `standin`): 100-step
+# reference episodes whose blue actions are the stand-in policy's own draws, random_blue_action(akey, t, 0, agent) -- what cc4_run_random_steps(seed0, t0 = 0)
+# draws in the kernel for the episode in slot akey - seed0.  The action key of fixture d is STANDIN_BASE + d (a key whose high word is not zero).
+STANDIN_BASE = (1 << 33) + 0x5EED
+STANDIN_OFFSETS = (0, 1, 31, 32, 63, 64, 255, 256, 1023)        # counter mode; the numpy stream has 0, 64 and 1023
+
+
+def list_standin_fixtures(mode):
+    """mode 1: ctrstand_*.npz, mode 0: trajstand_*.npz."""
+    return sorted(glob.glob(os.path.join(GOLDEN_DIR, 'ctrstand_*.npz' if mode else 'trajstand_*.npz')))
+
+
+def load_standin(path):
+    """load_ctr / load plus 'akey' and 'd' = akey - STANDIN_BASE."""
+    f = load_ctr(path) if os.path.basename(path).startswith('ctrstand_') else load(path)
+    f['akey'] = int(np.load(path)['akey'])
+    f['d'] = f['akey'] - STANDIN_BASE
+    return f
+
+
 def ctr_start(env_cls, fixes, **kw):
     """The episodes of counter-mode fixtures at step 0, on backend `env_cls` (CC4VecEnv or OracleVecEnv): the scenario comes from
     the numpy stream of the fixture's seed (reset(seed) then reset(None), as CybORG(seed) + wrapper.reset() do) on a numpy-stream

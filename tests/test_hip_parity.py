@@ -1,6 +1,8 @@
 """GPU: the HIP path (through the C ABI of libcc4.so) against (a) the golden trajectories recorded from the real
 reference, (b) the CPU oracle on seeded inputs incl. the full packed state, and (c) size-independent properties at
 BASELINE.json's full batch sizes.  Bit-exact everywhere: the path is integer / byte / index work."""
+import ctypes
+
 import numpy as np
 import pytest
 import golden_util as G
@@ -76,13 +78,21 @@ def test_hip_counter_mode_matches_reference_under_the_philox_proxy(philox_kernel
     scenario from the numpy stream (a numpy-stream handle generates it, its snapshot moves to a counter-mode handle through
     cc4_get/set_state + cc4_get/set_cold), the dynamics on the counter streams of the fixture's key (cc4_set_seed).  All
     episodes of one length in ONE batch; observations, reward, done of every step."""
+    _replay_ctr_fixtures(philox_kernel)
+
+
+def _replay_ctr_fixtures(kernel, build=None):
+    """build: what cc4_debug_step_build must say of every handle, {index: value} (include/cc4_debug.h)."""
     from cage_challenge_4_amd import CC4VecEnv
     allf = [G.load_ctr(p) for p in G.list_ctr_fixtures()]
     assert len(allf) >= 10
     for steps in sorted({f['steps'] for f in allf}):
         fixes = [f for f in allf if f['steps'] == steps]
         env, obs0, masks = G.ctr_start(CC4VecEnv, fixes)
-        assert env.step_kernel == philox_kernel
+        assert env.step_kernel == kernel
+        if build:
+            words = (ctypes.c_int32 * 3)()
+            assert env.lib.cc4_debug_step_build(env._h, words) == 0 and all(words[i] == v for i, v in build.items()), (tuple(words), build)
         for i, f in enumerate(fixes):
             assert np.array_equal(obs0[i], f['obs'][0]) and np.array_equal(masks[i], f['mask']), f['name']
         for t in range(steps):
@@ -94,6 +104,16 @@ def test_hip_counter_mode_matches_reference_under_the_philox_proxy(philox_kernel
                 assert rew[i] == f['reward'][t] and bool(done[i]) == bool(f['done'][t]), (f['name'], t)
             assert not info['err'].any()
         env.close()
+
+
+@pytest.mark.parametrize('minw', [7, 8])
+def test_hip_counter_mode_matches_reference_on_the_register_budget_builds(minw, monkeypatch):
+    """The same replay on k_step_philox<false, 7> and <false, 8>, the builds configure_groups picks for 1281 .. 2048 episodes (CC4_PHILOX_MINW puts the
+    small batch on them): the source of <false, 1>, other machine code -- tighter launch bounds, more spills.  cc4_step_kernel names the three alike;
+    cc4_debug_step_build tells which one the handle launches."""
+    monkeypatch.setenv('CC4_PHILOX_LEAN', '0')
+    monkeypatch.setenv('CC4_PHILOX_MINW', str(minw))
+    _replay_ctr_fixtures('k_step_philox', build={0: 0, 1: minw})
 
 
 @pytest.mark.parametrize('policies', [(0, 0), (2, 0), (1, 1), (3, 0)], ids=['fsm', 'discovery', 'sleep', 'randomselect'])

@@ -40,6 +40,61 @@ def test_oracle_matches_reference_trajectory(path, oracle_lib):
     env.close()
 
 
+# ---------------------------------------------------------------------------------------------------------------- the stand-in fixtures
+# ctrstand_*.npz / trajstand_*.npz: reference episodes whose blue actions are the draws cc4_run_random_steps makes in the kernel (golden_util.STANDIN_BASE)
+def test_standin_fixture_set():
+    """Nine counter-mode fixtures at the offsets the placement tests rely on, three numpy-stream ones; every red class, both green classes, a dynamics
+    key with a high word, action keys with a high word, scenario seeds no other fixture uses, 100-step episodes."""
+    import standin_util as S
+    ctr, pcg = S.fixtures(1), S.fixtures(0)
+    assert tuple(f['d'] for f in ctr) == G.STANDIN_OFFSETS and tuple(f['d'] for f in pcg) == (0, 64, 1023)
+    assert G.STANDIN_BASE >> 32 and all(f['akey'] >> 32 for f in ctr + pcg)
+    assert {f['red_policy'] for f in ctr} == {0, 1, 2, 3} and {f['green_policy'] for f in ctr} == {0, 1}
+    assert any(f['key'] >> 32 for f in ctr)
+    assert [f['red_policy'] for f in pcg] == [0, 2, 3]
+    others = {f['seed'] for f in map(G.load, G.list_fixtures())} | {f['seed'] for f in map(G.load_ctr, G.list_ctr_fixtures())}
+    seeds = [f['seed'] for f in ctr + pcg]
+    assert len(set(seeds)) == len(seeds) and not set(seeds) & others
+    assert all(f['steps'] == 100 and f['obs'].shape == (101, 578) for f in ctr + pcg)
+    for f in ctr + pcg:          # all three mission phases (33 / 33 / 34 steps), in order, and the episode ends with the last step
+        phase = f['obs'][:, 0]
+        assert set(phase.tolist()) == {0, 1, 2} and (np.diff(phase) >= 0).all() and (np.bincount(phase) >= 33).all(), f['name']
+        assert f['done'][-1] and not f['done'][:90].any(), f['name']
+
+
+@pytest.mark.parametrize('mode', [1, 0], ids=['counter', 'numpy-stream'])
+def test_standin_fixture_actions_are_the_stand_in_draws(mode):
+    """The stored actions are random_blue_action(akey, t, 0, agent), and the fixture with akey = STANDIN_BASE + d holds the draws of slot d of a batch stepped
+    with seed0 = STANDIN_BASE (the placement rule: slot e of a batch draws from key seed0 + e)."""
+    import standin_util as S
+    from oracle_binding import random_actions
+    fx = S.fixtures(mode)
+    deepest = max(f['d'] for f in fx)
+    for t in range(S.STEPS):
+        batch = random_actions(G.STANDIN_BASE, t, deepest + 1)
+        for f in fx:
+            assert np.array_equal(f['actions'][t], random_actions(f['akey'], t, 1)[0]), (f['name'], t)
+            assert np.array_equal(f['actions'][t], batch[f['d']]), (f['name'], t)
+    assert all((f['actions'] >= 0).all() and (f['actions'][:, :4] < 82).all() and (f['actions'][:, 4] < 242).all() for f in fx)
+
+
+@pytest.mark.parametrize('mode', [1, 0], ids=['counter', 'numpy-stream'])
+def test_oracle_matches_reference_on_the_standin_fixtures(mode, oracle_lib):
+    """Every stand-in fixture replays on the oracle at every step: observations, reward, done, no error flag, (first observations and masks:
+    standin_util._oracle_start) and the PCG64 stream position for the numpy-stream files."""
+    import standin_util as S
+    ora = S.oracle_replay(mode)
+    for f in S.fixtures(mode):
+        r = ora[f['name']]
+        for t in range(S.STEPS + 1):
+            assert np.array_equal(r['obs'][t], f['obs'][t]), (f['name'], 'observations after step', t - 1)
+            if mode == 0:
+                assert G.rng_words_match(f['rng'][t], r['rng'][t]), (f['name'], 'PCG64 stream position after step', t - 1)
+        assert np.array_equal(r['reward'], f['reward']), (f['name'], np.nonzero(r['reward'] != f['reward'])[0][:4])
+        assert np.array_equal(r['done'], f['done']) and not r['err'].any(), f['name']
+        assert sorted(r['hot']) == list(S.ENDS)
+
+
 def test_baseline_config1_episode_rewards(oracle_lib):
     # BASELINE.md section 2: seed 123 -> -5634, seed 7 -> -4154 (SleepAgent blue, 500 steps)
     want = {'traj_seed123_sleep_ctor_500.npz': -5634.0, 'traj_seed7_sleep_ctor_500.npz': -4154.0}
