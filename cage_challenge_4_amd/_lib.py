@@ -21,7 +21,8 @@ TOPOLOGY_BYTES = 27 + 2 * 137
 FEAT_HOSTS, FEAT_PER_HOST, FEAT_GLOBAL = 137, 16, 32     # CC4_FEAT_*: the state-feature tensors (state_features.py)
 RED_ACT_WORDS, RED_SID_AUTO = 4, -1                       # CC4_RED_*: red actions from the device (cc4_step_red_device) ...
 RED_VIEW_HOSTS, RED_VIEW_PER_HOST, RED_VIEW_SCALARS = 137, 8, 16     # ... and the red agents' view tensors (red_view.py)
-POLICY_KEEP, POLICY_DEFAULT = -1, -2                     # CC4_POLICY_*: per-episode opponent classes (cc4_set_policies)
+BLUE_VIEW_HOSTS, BLUE_VIEW_PER_HOST, BLUE_VIEW_SCALARS = 137, 8, 16  # CC4_BLUE_VIEW_*: blue's own knowledge as tensors (blue_view.py)
+POLICY_KEEP, POLICY_DEFAULT = -1, -2                    # CC4_POLICY_*: per-episode opponent classes (cc4_set_policies)
 OBS_LEN = (92, 92, 92, 92, 210)
 ACT_LEN = (82, 82, 82, 82, 242)
 OBS_OFF = (0, 92, 184, 276, 368)
@@ -91,6 +92,8 @@ SIGNATURES = {
     'cc4_red_view_device': (ctypes.c_int, [_P, _P, ctypes.c_int32, _P, ctypes.c_int32, _P, _P]),
     'cc4_red_view_from_row': (ctypes.c_int, [_P, _P, _P]),
     'cc4_red_record_from_row': (ctypes.c_int, [_P, ctypes.c_int32, _P, _P]),
+    'cc4_blue_view_device': (ctypes.c_int, [_P, _P, ctypes.c_int32, _P, ctypes.c_int32, _P, _P]),
+    'cc4_blue_view_from_row': (ctypes.c_int, [_P, _P, ctypes.c_int32, _P, _P]),
     'cc4_set_policies_device': (ctypes.c_int, [_P, _P, _P, _P]),
     'cc4_set_policies': (ctypes.c_int, [_P, _P, _P, _P]),
     'cc4_policies_device': (ctypes.c_int, [_P, _P, _P]),

@@ -5,6 +5,7 @@
 #include "cc4_export.h"
 #include "cc4_features.h"
 #include "cc4_red_view.h"
+#include "cc4_blue_view.h"
 
 static thread_local std::string g_create_err;
 
@@ -737,6 +738,51 @@ int cc4_red_view_from_row(const void* hot_row, uint8_t* hosts, int32_t* scalars)
   red_view_from_row(s, hosts, scalars);
   free(s);
   return 0;
+}
+// ---- blue's own knowledge (include/cc4.h; cc4_k_blue.hip; the definition: cc4_blue_view.h).  One launch on the main stream behind the group streams,
+// no host synchronisation; it only reads rows: the hot rows and, of the cold rows, the event log and the sus lists as the last step left them.
+int cc4_blue_view_device(cc4_handle* h, const void* d_bank, int32_t capacity, const int32_t* d_ids, int32_t n, uint8_t* d_hosts, int32_t* d_scalars) {
+  const char* who = "cc4_blue_view_device";
+  if (h->rollout_k > 0) { h->err = std::string(who) + ": a rollout is in flight on this handle: cc4_rollout_end first"; return -2; }
+  if (n < 0) { h->err = std::string(who) + ": n < 0"; return -2; }
+  if (n == 0) return 0;
+  if (!d_hosts || reinterpret_cast<uintptr_t>(d_hosts) % 8 || reinterpret_cast<uintptr_t>(d_scalars) % 4) {
+    h->err = std::string(who) + ": the host-view buffer is required and must be 8-byte aligned (the agent words: 4-byte aligned or NULL)"; return -2;
+  }
+  if (d_bank && capacity < 1) { h->err = std::string(who) + ": a bank needs a capacity of at least one slot"; return -2; }
+  if (reinterpret_cast<uintptr_t>(d_bank) % 64) { h->err = std::string(who) + ": a bank must be 64-byte aligned"; return -2; }
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  if (join_groups(h)) return -1;
+  BlueViewArgs a{h->d_state, h->d_cold, h->cold_row, static_cast<const uint8_t*>(d_bank), slot_bytes(h->cold_row), d_ids, n,
+                 d_bank ? capacity : h->cfg.num_envs, h->cfg.steps, h->cfg.rng_mode, d_hosts, d_scalars, h->d_copy_fault};
+  hipLaunchKernelGGL(k_blue_view, dim3(n), dim3(WAVE), 0, h->stream, a);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+// The same on the host, from one hot row and (optionally) its cold row: no device, no handle.  Only the event log and the sus lists of the cold row
+// are read; they are copied, like the hot row, because the caller's bytes may sit at any address.
+int cc4_blue_view_from_row(const void* hot_row, const void* cold_row, int32_t steps, uint8_t* hosts, int32_t* scalars) {
+  if (!hot_row || !hosts) return -2;
+  EnvState* s = row_copy(hot_row);
+  if (!s) return -1;
+  if (steps <= 0) steps = s->steps;                  // (the episode length the row itself was generated for)
+  if (steps <= 0 || steps > (1 << 20)) { free(s); return -2; }
+  int rc = 0;
+  if (!cold_row) blue_view_from_row(s, nullptr, nullptr, steps, hosts, scalars);
+  else {
+    const size_t b_sus = sizeof(uint32_t) * (size_t)NBLUE * (size_t)cold_sus_cap(steps);
+    EvLog* lg = static_cast<EvLog*>(aligned_alloc(alignof(EvLog), sizeof(EvLog)));
+    uint32_t* sus = static_cast<uint32_t*>(malloc(b_sus));
+    if (!lg || !sus) rc = -1;
+    else {
+      memcpy(lg, static_cast<const char*>(cold_row) + offsetof(EnvCold, evlog), sizeof(EvLog));
+      memcpy(sus, static_cast<const char*>(cold_row) + sizeof(EnvCold), b_sus);
+      blue_view_from_row(s, lg, sus, steps, hosts, scalars);
+    }
+    free(lg); free(sus);
+  }
+  free(s);
+  return rc;
 }
 int cc4_red_record_from_row(const void* hot_row, int32_t agent, const int32_t* words, cc4_agent_action* out) {
   if (!hot_row || !words || !out || agent < 0 || agent >= NRED) return -2;

@@ -56,6 +56,12 @@ class CC4TorchVecEnv:
                                                   Red's reward is -reward.  An env that has taken red actions runs the full builds of its step kernel.
     red_view(ids=None, bank=None, out=None) -> (hosts [n, 6, 137, 8] uint8, scalars [n, 6, 16] int32)   what each red agent knows
 
+    Blue's own knowledge (include/cc4.h cc4_blue_view_device; cage_challenge_4_amd.blue_view):
+    blue_view(ids=None, bank=None, out=None) -> (hosts [n, 5, 137, 8] uint8, scalars [n, 5, 16] int32)   busy, the outcome of the agent's own action,
+                                                  what Analyse found, the deployed decoy, suspicious pids; with enable_event_log() the Monitor's
+                                                  entries per host (counts, ports, remote hosts)
+    enable_event_log(on=True)                     the per-step event log (full builds of the step kernel, one launch per step)
+
     Mixed opponents in one batch (include/cc4.h cc4_set_policies_device, cc4_reset_device):
     set_opponents(red=None, green=None, blue=None)   integer tensors [N] on the device: the classes each episode regenerates into from its next
                                                      regeneration on (never mid-episode); None keeps
@@ -337,6 +343,47 @@ class CC4TorchVecEnv:
                 self.venv._chk(rc, 'cc4_red_view_device')
             self.venv._chk(lib.cc4_stream_signal(h, sp), 'cc4_stream_signal')
         return hosts, scal
+
+    def blue_view(self, ids=None, bank=None, out=None):
+        """Blue's own knowledge (cc4_blue_view_device, include/cc4.h; columns and words: blue_view.HOST_COLUMNS / SCALAR_WORDS) as tensors on the
+        env's device: (hosts [n, 5, 137, 8] uint8, scalars [n, 5, 16] int32) -- busy, the outcome of the agent's own action, what Analyse found,
+        the deployed decoy, suspicious pids, and with enable_event_log() the Monitor's entries per host (scalars[..., 10]: whether they are
+        filled).  ids, bank, out and the ordering on the current stream as state_features(); no host copy, no host wait.  A faulty entry gives
+        all-zero rows, and check_errors() raises CC4EngineError for it."""
+        with torch.cuda.device(self.device):
+            s = torch.cuda.current_stream(self.device)
+            vp = ctypes.c_void_p
+            bp, cap = self._bank(bank) if bank is not None else (None, 0)
+            if ids is not None:
+                ids = self._index(ids, 'ids')
+                n, ip = int(ids.numel()), vp(ids.data_ptr())
+            else:
+                n, ip = (cap if bank is not None else self.num_envs), None
+            shapes = ((n, L.NUM_BLUE, L.BLUE_VIEW_HOSTS, L.BLUE_VIEW_PER_HOST), (n, L.NUM_BLUE, L.BLUE_VIEW_SCALARS))
+            if out is None:
+                hosts = torch.empty(shapes[0], dtype=torch.uint8, device=self.device)
+                scal = torch.empty(shapes[1], dtype=torch.int32, device=self.device)
+            else:
+                hosts, scal = out
+                for x, shp, dt in ((hosts, shapes[0], torch.uint8), (scal, shapes[1], torch.int32)):
+                    if not torch.is_tensor(x) or tuple(x.shape) != shp or x.dtype != dt or x.device != self.device or not x.is_contiguous():
+                        raise ValueError(f'out must be contiguous tensors (uint8 {list(shapes[0])}, int32 {list(shapes[1])}) on {self.device}')
+            lib, h, sp = self.lib, self._h, vp(s.cuda_stream)
+            rc = lib.cc4_stream_wait(h, sp) or lib.cc4_blue_view_device(h, bp, cap, ip, n, vp(hosts.data_ptr()), vp(scal.data_ptr()))
+            if rc:
+                self.venv._chk(rc, 'cc4_blue_view_device')
+            self.venv._chk(lib.cc4_stream_signal(h, sp), 'cc4_stream_signal')
+        return hosts, scal
+
+    def enable_event_log(self, on=True):
+        """CC4VecEnv.enable_event_log (cc4_enable_event_log): record the HostEvents entries of every step, which fills the event columns of
+        blue_view() (entries per host, ports, remote hosts, the deployed decoy).  The log has a price: an env with the log on runs the full
+        builds of its step kernel, one launch per step, and leaves the one-launch forms of run / plan calls.  Without it blue_view() still
+        carries busy / success / what Analyse found / sus_pids."""
+        with torch.cuda.device(self.device):
+            s = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            self.venv._chk(self.lib.cc4_stream_wait(self._h, s), 'cc4_stream_wait')
+            self.venv.enable_event_log(on)
 
     def set_opponents(self, red=None, green=None, blue=None):
         """Assign opponent classes per episode from the device (cc4_set_policies_device, include/cc4.h): red (0..3), green (0..1), blue (0..1) each

@@ -517,6 +517,51 @@ class CC4VecEnv:
             raise_on_copy_faults(faults.value)
         return hosts, scal
 
+    def blue_view_device(self, d_hosts, d_scalars=None, n=None, d_ids=None, d_bank=None, capacity=0):
+        """cc4_blue_view_device into device memory of the caller's (device addresses): hosts [n, 5, 137, 8] uint8, 8-byte aligned, scalars
+        [n, 5, 16] int32 or None, of episodes d_ids (int32 [n] on the device; None: 0 .. n-1) of the env or of the slots of a snapshot bank.
+        Enqueued, no host wait."""
+        vp = ctypes.c_void_p
+        as_p = lambda x: x if x is None or isinstance(x, vp) else vp(int(x))      # noqa: E731
+        rc = self.lib.cc4_blue_view_device(self._h, as_p(d_bank), int(capacity), as_p(d_ids), self.num_envs if n is None else int(n),
+                                           as_p(d_hosts), as_p(d_scalars))
+        if rc:
+            self._chk(rc, 'cc4_blue_view_device')
+
+    def blue_view(self, env_ids=None):
+        """Blue's own knowledge (cc4_blue_view_device, include/cc4.h; columns and words: blue_view.HOST_COLUMNS / SCALAR_WORDS):
+        (hosts [n, 5, 137, 8] uint8, scalars [n, 5, 16] int32) of episodes env_ids (None: all), as NumPy arrays.  Synchronises, like the other
+        getters.  The event columns need enable_event_log(); scalars[..., 10] says whether they are filled.  An index out of range gives
+        all-zero rows and raises CC4EngineError after the call."""
+        ids = None if env_ids is None else np.ascontiguousarray(env_ids, dtype=np.int32).ravel()
+        n = self.num_envs if ids is None else int(ids.size)
+        hosts = np.zeros((n, L.NUM_BLUE, L.BLUE_VIEW_HOSTS, L.BLUE_VIEW_PER_HOST), np.uint8)
+        scal = np.zeros((n, L.NUM_BLUE, L.BLUE_VIEW_SCALARS), np.int32)
+        if n == 0:
+            return hosts, scal
+        hip, vp = _hip(), ctypes.c_void_p
+        b_ids = ((4 * n + 15) & ~15) if ids is not None else 0          # [ids | hosts | scalars]: every part 8-byte aligned
+        _hip_chk(hip.hipSetDevice(self._dev), 'hipSetDevice')
+        d = vp()
+        _hip_chk(hip.hipMalloc(ctypes.byref(d), b_ids + hosts.nbytes + scal.nbytes), 'hipMalloc')
+        try:
+            if ids is not None:
+                _hip_chk(hip.hipMemcpy(d, ids.ctypes.data_as(vp), ids.nbytes, 1), 'hipMemcpy')
+            d_hosts, d_scal = vp(d.value + b_ids), vp(d.value + b_ids + hosts.nbytes)
+            rc = self.lib.cc4_blue_view_device(self._h, None, 0, d if ids is not None else None, n, d_hosts, d_scal)
+            rc2 = self.lib.cc4_synchronize(self._h)
+            if rc or rc2:
+                self._chk(rc or rc2, 'cc4_blue_view_device')
+            _hip_chk(hip.hipMemcpy(hosts.ctypes.data_as(vp), d_hosts, hosts.nbytes, 2), 'hipMemcpy')
+            _hip_chk(hip.hipMemcpy(scal.ctypes.data_as(vp), d_scal, scal.nbytes, 2), 'hipMemcpy')
+        finally:
+            hip.hipFree(d)
+        if ids is not None and ((ids < 0) | (ids >= self.num_envs)).any():
+            faults = ctypes.c_uint32(0)
+            self._chk(self.lib.cc4_copy_faults(self._h, ctypes.byref(faults)), 'cc4_copy_faults')
+            raise_on_copy_faults(faults.value)
+        return hosts, scal
+
     def plan_kernel_for(self, k):
         """cc4_plan_kernel_for: the kernel a run_plan / step_plan call of k steps launches ('k_run_philox1p' / 'k_run_pcgp': one launch for the
         whole plan; else the step kernel, once per step)."""
