@@ -149,6 +149,7 @@ SIGNATURES = {
     'cc4_debug_persist_base': (ctypes.c_int, [_P, ctypes.c_uint32]),
     'cc4_debug_shadow_handle': (ctypes.c_int, [_P, ctypes.POINTER(_P)]),
     'cc4_debug_step_build': (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int32)]),
+    'cc4_debug_last_run_split': (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int32)]),
     'cc4_get_gather_log': (ctypes.c_int, [_P, _P, ctypes.c_int32, ctypes.c_int32]),
     'cc4_get_allgathered_obs': (ctypes.c_int, [_P, _P]),
     'cc4_unpack_obs_device': (ctypes.c_int, [_P, ctypes.POINTER(_P)]),

@@ -58,13 +58,16 @@ StepArgs step_args(const cc4_handle* h) {
 }
 // The same for the persistent kernels' RunArgs of a k-step call: the schedule's tables and the runs its k steps are cut into (run_split, cc4_sched.h).
 // persist_launch sets by name what is per call: the ticket counters' parity, base, the rollout's fields, the timeline.
-RunArgs run_args(const cc4_handle* h, int k, uint32_t t0) {
+// head: the call launches the headline kernel k_run_philox1 (persist_launch decides) -- only that one takes the long-call pattern of run_config_for_call:
+// the builds with the exchange hold a run against the ring of step slabs (run_config_for_call's comment), and the others keep the split they were measured with.
+RunArgs run_args(const cc4_handle* h, int k, uint32_t t0, bool head) {
   RunArgs ra{};
   ra.progress = h->d_run; ra.slot_part = h->d_slot_part;
   ra.P = h->run_P; ra.K = k; ra.G = h->run_G; ra.t0 = t0;
   memcpy(ra.xcc_lo, h->xcc_lo, 8); memcpy(ra.xcc_n, h->xcc_n, 8);
   ra.thr = h->run_thr;
-  ra.runs = run_split(k, h->run_SA, h->run_SB, h->run_nB, h->run_single);
+  ra.runs = head ? run_split_for_call(k, h->run_SA, h->run_SB, h->run_nB, h->run_single)      // (a long call with no CC4_PERSIST_RUNS given: run_config_for_call's pattern)
+                 : run_split(k, h->run_SA, h->run_SB, h->run_nB, h->run_single);
   return ra;
 }
 

@@ -8,6 +8,28 @@ int timeline_report(cc4_handle* h, int k, bool timed) {
   std::vector<unsigned long long> tl(4 * (size_t)h->run_grid);
   HIPCHK(h, hipMemcpy(tl.data(), h->d_timeline, tl.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
   (void)hipFree(h->d_timeline); h->d_timeline = nullptr;
+#ifdef CC4_BOUNDARY_PROF
+  // the measurement build's words of a k_run_philox1 launch (bit 63 of word 0; persist_loop's tl_flush): the hand-over between two items of a wave in four parts
+  { double sA = 0, sB = 0, sC = 0, sD = 0, sn = 0, items = 0, busy_ticks = 0; int nw = 0; std::vector<double> per;
+    bool head = false;
+    for (int w = 0; w < h->run_grid; ++w) { const unsigned long long* t = &tl[4 * (size_t)w]; if (!(t[0] >> 63)) continue; head = true;
+      const double n = (double)((t[0] >> 32) & 0x7FFFFFFFull); if (n <= 0) continue; ++nw;
+      const double A = (double)(uint32_t)t[1], B = (double)(t[1] >> 32), C = (double)(uint32_t)t[2], D = (double)(t[2] >> 32);
+      sA += A; sB += B; sC += C; sD += D; sn += n; items += (double)(uint32_t)t[3]; busy_ticks += (double)(uint32_t)t[0]; per.push_back((A + B + C + D) / n / 100.0); }
+    if (head) {
+      float ms = 0.f; if (timed) (void)hipEventElapsedTime(&ms, h->evs[0], h->evs[1]);
+      std::sort(per.begin(), per.end());
+      const size_t m = per.size();
+      const RunSplit rs = h->last_runs;
+      if (m) fprintf(stderr, "[cc4 boundary] k=%d runs SA=%d nA=%d SB=%d nB=%d nph=%d: %d waves with a boundary, %.0f boundaries (%.0f items); per boundary, mean us: stage-out drain + publish %.3f, pick %.3f, "
+                      "progress wait + acquire %.3f, stage-in %.3f, all %.3f; per wave all: min %.3f / median %.3f / 90%% %.3f / max %.3f us; boundaries are %.2f %% of the waves' busy time "
+                      "(first item's start to last item's end, mean %.1f us); kernel (events) %.1f us\n", k, rs.SA, rs.nA, rs.SB, rs.nB, rs.nph, nw, sn, items,
+                      sA / sn / 100.0, sB / sn / 100.0, sC / sn / 100.0, sD / sn / 100.0, (sA + sB + sC + sD) / sn / 100.0, per[0], per[m / 2], per[m * 9 / 10], per[m - 1],
+                      100.0 * (sA + sB + sC + sD) / busy_ticks, busy_ticks / nw / 100.0, ms * 1000.0);
+      return 0;
+    }
+  }
+#endif
   unsigned long long e0 = ~0ull, e1 = 0, f1 = 0, l0 = ~0ull, l1 = 0; double fs = 0, ls = 0, items = 0; int nw = 0, idle = 0;
   for (int w = 0; w < h->run_grid; ++w) { const unsigned long long* t = &tl[4 * (size_t)w]; if (!t[0]) continue; ++nw; e0 = t[0] < e0 ? t[0] : e0; e1 = t[0] > e1 ? t[0] : e1; if (!(uint32_t)t[3]) { ++idle; continue; } f1 = t[1] > f1 ? t[1] : f1; l0 = t[2] < l0 ? t[2] : l0; l1 = t[2] > l1 ? t[2] : l1; fs += (double)t[1]; ls += (double)t[2]; items += (double)(uint32_t)t[3]; }
   const int busy = nw - idle;
@@ -115,6 +137,12 @@ int cc4_debug_shadow_handle(cc4_handle* h, cc4_handle** out) {
 int cc4_debug_step_build(cc4_handle* h, int32_t out[3]) {
   if (!h || !out) return -2;
   out[0] = h->philox_lean ? 1 : 0; out[1] = h->philox_minw; out[2] = h->multistep_minb;
+  return 0;
+}
+int cc4_debug_last_run_split(cc4_handle* h, int32_t out[5]) {
+  if (!h || !out) return -2;
+  const RunSplit& r = h->last_runs;
+  out[0] = r.SA; out[1] = r.nA; out[2] = r.SB; out[3] = r.nB; out[4] = r.nph;
   return 0;
 }
 // debug / test hook: every all-gather is preceded by a kernel that keeps the communication stream busy for about `us`

@@ -310,7 +310,10 @@ int persist_launch(cc4_handle* h, StepArgs a, int k, uint32_t t0, const XchgArgs
   unsigned long long* d_tl = nullptr;
   if (getenv("CC4_PERSIST_TIMELINE")) { HIPCHK(h, hipMalloc(&d_tl, 4 * sizeof(unsigned long long) * (size_t)h->run_grid)); HIPCHK(h, hipMemsetAsync(d_tl, 0, 4 * sizeof(unsigned long long) * (size_t)h->run_grid, h->stream)); }
   h->d_timeline = d_tl;
-  RunArgs ra = run_args(h, k, t0);
+  // the headline build knows its call's shape at compile time -- actions drawn in the kernel, none given, no messages, nothing of the debug or
+  // exchange arguments: a call of any other shape takes the build that reads them at run time
+  const bool head = !rollout && !pl && h->cfg.rng_mode != 0 && !h->comm && head_shape(a, x);
+  RunArgs ra = run_args(h, k, t0, head);
   ra.ticket = h->d_pool + (size_t)h->pool_parity * CC4_SLOTS * TK_STRIDE;
   ra.ticket_next = h->d_pool + (size_t)(h->pool_parity ^ 1) * CC4_SLOTS * TK_STRIDE;
   ra.base = h->pool_base;
@@ -321,6 +324,7 @@ int persist_launch(cc4_handle* h, StepArgs a, int k, uint32_t t0, const XchgArgs
     ra.act_ready = h->d_rready; ra.act = h->d_ract; ra.PG = h->rpg;
     ra.act_wait_ticks = (long long)h->rollout_watchdog_ms * wall_khz(h);
   }
+  h->last_runs = ra.runs;
   if (pl) {
     if (h->cfg.rng_mode == 0) hipExtLaunchKernelGGL(k_run_pcgp, dim3(h->run_grid), dim3(WAVE), offsetof(EnvState, hd), h->stream, e0, e1, 0, a, ra, *pl);
     else hipExtLaunchKernelGGL(k_run_philox1p, dim3(h->run_grid), dim3(WAVE), offsetof(EnvState, hd), h->stream, e0, e1, 0, a, ra, *pl);
@@ -332,9 +336,7 @@ int persist_launch(cc4_handle* h, StepArgs a, int k, uint32_t t0, const XchgArgs
     // a rollout leaves `rollout_margin` waves per CU to the caller's policy kernels and the gates (CC4_ROLLOUT_MARGIN)
     const int grid = rollout ? h->run_grid - h->rollout_margin * h->cus : h->run_grid;
     if (rollout) hipExtLaunchKernelGGL(k_run_philox1r, dim3(grid > h->cus ? grid : h->cus), dim3(WAVE), offsetof(EnvState, hd), h->stream, e0, e1, 0, a, ra, x);
-    // the headline build knows its call's shape at compile time -- actions drawn in the kernel, none given, no messages, nothing of the debug or
-    // exchange arguments: a call of any other shape takes the build that reads them at run time
-    else if (head_shape(a, x)) hipExtLaunchKernelGGL(k_run_philox1, dim3(grid), dim3(WAVE), offsetof(EnvState, hd), h->stream, e0, e1, 0, a, ra);
+    else if (head) hipExtLaunchKernelGGL(k_run_philox1, dim3(grid), dim3(WAVE), offsetof(EnvState, hd), h->stream, e0, e1, 0, a, ra);
     else hipExtLaunchKernelGGL(k_run_philox1g, dim3(grid), dim3(WAVE), offsetof(EnvState, hd), h->stream, e0, e1, 0, a, ra, x);
   }
   return 0;

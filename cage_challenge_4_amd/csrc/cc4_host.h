@@ -100,8 +100,9 @@ struct cc4_handle {
   uint8_t xcc_lo[8] = {0}, xcc_n[8] = {0};
   int run_thr = 16;               // a wave helps the partition that lags most once its own is more than this many tickets ahead (CC4_PERSIST_THR)
   uint32_t* d_pool = nullptr;     // [2][CC4_SLOTS][TK_STRIDE] the partitions' ticket counters, one set per call parity
-  int run_SA = 0, run_SB = 1, run_nB = 0, run_single = 0;   // runs of steps (run_split -> RunArgs.runs; CC4_PERSIST_RUNS="SA,SB,nB,single"; SA = 1: every step an item, as in r05;
+  int run_SA = 0, run_SB = 1, run_nB = 0, run_single = 0;   // runs of steps (run_args -> RunArgs.runs; CC4_PERSIST_RUNS="SA,SB,nB,single"; SA = 1: every step an item, as in r05;
                                                             // SA = 0: chosen per call -- 4 steps, 8 in calls of 64 steps and more: profiles/r06_runs_ab.txt, r06_sched_ab2.txt)
+  RunSplit last_runs{};           // the runs of the most recent persistent launch (cc4_debug_last_run_split)
   uint32_t pool_base = 0;         // steps every episode's progress word stands at (the words are not cleared between calls)
   int pool_parity = 0;
   int persist_state = -1;         // -1 off / unavailable, 0 not set up yet (persist_setup on first use), 1 on
@@ -215,7 +216,7 @@ CC4_HOST int sync_all(cc4_handle* h);
 CC4_HOST int wall_khz(cc4_handle* h);
 CC4_HOST int ensure_watchdog_word(cc4_handle* h);
 CC4_HOST StepArgs step_args(const cc4_handle* h);
-CC4_HOST RunArgs run_args(const cc4_handle* h, int k, uint32_t t0);
+CC4_HOST RunArgs run_args(const cc4_handle* h, int k, uint32_t t0, bool head);
 CC4_HOST void launch_group(cc4_handle* h, StepArgs a, int g, bool full, hipEvent_t start, hipEvent_t stop);
 CC4_HOST void launch_range(cc4_handle* h, StepArgs a, int e0, int e1, hipStream_t st, bool full, hipEvent_t start, hipEvent_t stop);
 CC4_HOST int launch_step(cc4_handle* h, const int32_t* d_actions, const uint8_t* d_msgs, bool rand = false, uint64_t seed0 = 0, uint32_t t = 0, bool ext_uploaded = false, bool api_step = false);

@@ -20,6 +20,15 @@
 #pragma once
 #include "cc4_args.h"
 
+// CC4_BOUNDARY_PROF (a measurement build, make EXTRA=-DCC4_BOUNDARY_PROF; tools/persist_boundary.py): the headline kernel splits what a wave pays between
+// the last step of one item and the first step_phase of its next into four sums of wall-clock ticks, kept in lane 0's registers and written once per wave
+// at exit into the CC4_PERSIST_TIMELINE words (timeline_report prints them).  The shipped build compiles none of it.
+#ifdef CC4_BOUNDARY_PROF
+#define CC4_BP(...) do { if constexpr (HEAD) { __VA_ARGS__; } } while (0)
+__shared__ unsigned long long cc4_bp_staged;      // lane 0, philox1_body: the item's rows are in LDS, step_phase is next
+#else
+#define CC4_BP(...) do {} while (0)
+#endif
 
 // uniform blue action index of (episode e, agent b) at step t: Philox key (seed0 + e), counter (t, b, 0xB10E, 0)
 __device__ __forceinline__ int32_t random_blue_action(uint64_t seed0, uint32_t t, int e, int b) {

@@ -107,7 +107,16 @@ __device__ __forceinline__ void persist_loop(StepArgs a, RunArgs ra, const XchgA
   uint32_t seen_gathered = 0;
   unsigned long long tl_first = 0, tl_last = 0, tl_items = 0;
   const unsigned long long tl_entry = ra.timeline ? wall_clock64() : 0;
-  auto tl_flush = [&]() { if (ra.timeline && lane == 0) { unsigned long long* t = ra.timeline + 4 * (size_t)blockIdx.x; t[0] = tl_entry; t[1] = tl_first; t[2] = tl_last; t[3] = tl_items | ((unsigned long long)(my_slot + 1) << 32); } };
+#ifdef CC4_BOUNDARY_PROF
+  // the measurement build (cc4_kernels.h, CC4_BP): the last stamp, the sums of the four parts (A: the stage-out's drain + publish, B: pick up to the drawn
+  // ticket, C: progress wait + acquire, D: stage-in up to step_phase) and the boundaries counted (an item that follows an item on this wave)
+  unsigned long long bp_t = 0, bp_A = 0, bp_B = 0, bp_C = 0, bp_D = 0, bp_n = 0;
+#endif
+  auto tl_flush = [&]() {
+#ifdef CC4_BOUNDARY_PROF
+    if (HEAD && ra.timeline && lane == 0) { unsigned long long* t = ra.timeline + 4 * (size_t)blockIdx.x; t[0] = ((tl_last - tl_first) & 0xFFFFFFFFull) | (bp_n << 32) | (1ull << 63); t[1] = (bp_A & 0xFFFFFFFFull) | (bp_B << 32); t[2] = (bp_C & 0xFFFFFFFFull) | (bp_D << 32); t[3] = tl_items | ((unsigned long long)(my_slot + 1) << 32); return; }
+#endif
+    if (ra.timeline && lane == 0) { unsigned long long* t = ra.timeline + 4 * (size_t)blockIdx.x; t[0] = tl_entry; t[1] = tl_first; t[2] = tl_last; t[3] = tl_items | ((unsigned long long)(my_slot + 1) << 32); } };
   int pend_e = -1; uint32_t pend_k = 0;  // the exchange: the item whose packed row this wave stored last and has not counted yet (its store drains with the next item)
   auto flush_pending = [&]() {
     if (XCHG && x.slab && pend_e >= 0) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); if (lane == 0) xchg_count(x, pend_k, part_of(pend_e, ra.G)); pend_e = -1; }
@@ -127,11 +136,13 @@ __device__ __forceinline__ void persist_loop(StepArgs a, RunArgs ra, const XchgA
   auto claim = [&](int line, int idx, int pg, Item& it) -> int {
     int j, ee;
     if (!draw_ticket(ra, a.n, line, idx, pg, j, ee)) return 0;
+    CC4_BP(const unsigned long long now = wall_clock64(); if (tl_items) bp_B += now - bp_t; bp_t = now);
     int k, len; run_span(ra.runs, j, k, len);
     bool ok;
     const uint32_t w = wait_progress(ra, x, ee, (uint32_t)k, rollout, ok);
     if (!ok) return -1;
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    CC4_BP(const unsigned long long now = wall_clock64(); if (tl_items) bp_C += now - bp_t; bp_t = now);
     if (XCHG && !rollout && x.slab) xchg_wait_slab(x, (uint32_t)k, seen_gathered);      // (a rollout has no `gathered` word: see xchg_wait_slab)
     const uint32_t last = progress_runner(w);
     it.e = ee; it.k = j; it.sh = (last != RUNNER_NONE && last != my_id) ? 1 : 0;     // the episode's last run was on another CU: its lines in this CU's L1 may be stale
@@ -260,6 +271,7 @@ __device__ __forceinline__ void persist_loop(StepArgs a, RunArgs ra, const XchgA
       }
     }
     --item_k;        // the run's last step
+    CC4_BP(if (tl_items) { bp_D += cc4_bp_staged - bp_t; ++bp_n; } bp_t = wall_clock64());
     // ---- release: the item is done when everything it wrote has left this wave: then the next step of the episode may start (on this XCD)
     // Every lane DRAINS its own stores -- an explicit s_waitcnt vmcnt(0): the vector L1 is write-through, so a drained store is in
     // the XCD's L2 --, the barrier collects the lanes, lane 0 publishes.  The consumer is a wave of the same CU unless the partition is
@@ -277,5 +289,6 @@ __device__ __forceinline__ void persist_loop(StepArgs a, RunArgs ra, const XchgA
     // ---- publish progress
     if (lane == 0) __hip_atomic_store(&ra.progress[e], progress_pack(ra.base + item_k + 1u, my_id), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (ra.timeline) { tl_last = wall_clock64(); ++tl_items; }
+    CC4_BP(bp_A += tl_last - bp_t; bp_t = tl_last);
   }
 }

@@ -60,6 +60,9 @@ __device__ __forceinline__ void philox1_body(StepArgs a, const int e, const uint
   unsigned long long* prof = a.prof ? prof_lds : nullptr;
   if (prof && lane < 16) prof_lds[lane] = 0;
   __syncthreads();
+#ifdef CC4_BOUNDARY_PROF
+  if constexpr (HEAD) { if (first && lane == 0) cc4_bp_staged = wall_clock64(); }
+#endif
   EnvState* s = reinterpret_cast<EnvState*>(lds);   // only the part in front of EnvState.hd is valid here
   HostDyn* const hd = a.st[e].hd;                   // the host table stays in HBM / L2
   if (prof && lane == 0) prof[11] += clock64() - t_begin;

@@ -50,6 +50,34 @@ CC4_HD constexpr RunSplit run_split(int k, int cfgSA, int cfgSB, int cfgnB, int 
   single = k - nA * SA - nB * cfgSB;
   return RunSplit{SA, nA, cfgSB > 1 ? cfgSB : 1, nB, nA + nB + single};
 }
+// The pattern of a call, chosen on the host (run_args): an explicit CC4_PERSIST_RUNS passes through; so does the unset one (0,1,0,0) for a call of fewer than
+// RUN_LONG_K steps -- run_split's default above, which every call shape of the tests and the hand-over cells is described by.  A LONG call with no
+// pattern given gets runs of run_long_sa(k) steps, and what they leave over becomes ONE closing run instead of single steps (100 = 12 x 8 + one run of
+// 4: 13 items an episode, not 16; 500 = 20 x 24 + one run of 20: 21, not 66) -- every item pays the hand-over between two items of a wave (DESIGN 3.3:
+// about 8 us of the wave's time), a single step as much as a run of 8.
+// The thresholds and lengths are measured values, profiles/r23_runs_k500.txt: at K = 100 the closing run gains 3.3 % on the default (runs of 8); at
+// K = 500 it gains 1.0 % with runs of 8 and 2.2 - 2.8 % with runs of 16 to 32, a plateau on which 24 measured best in both sweeps -- taken only from
+// the length it was measured at (at 250 and 300 steps longer runs are ahead but inside the noise bound, at 100 and 200 no different).  Longer runs
+// WITHOUT the closing run lose: 24 and 32 leave 20 single steps.
+// For the headline kernel k_run_philox1 ONLY (run_args' `head`, decided in persist_launch).  With the exchange on (k_run_philox1x) a run is held against the
+// ring of 32 step slabs: a wave counts its item's last packed row only with its next item's first step (persist_step_out's pend_e), and that item's
+// claim waits for the slab of ITS first step (xchg_wait_slab).  With runs of 24 the wave that finishes run j of an episode and draws a ticket of run
+// j + 2 -- the ordinary order of 24 waves over a partition's 32 episodes -- waits for the gather of the chunk that ends with step 24 j + 23, which waits
+// for the very count the wave holds: the launch stands until the exchange's watchdog (2 s) gives the exchange up.  Runs of 8 would need a ticket four
+// runs ahead.  The other builds (plan, rollout, numpy stream, caller's actions) are out of this pattern's measurements and keep run_split's default.
+struct RunConfig { int SA, SB, nB, single; };
+constexpr int RUN_LONG_K = 100, RUN_LONG_SA = 8;              // from this many steps: runs of 8 and a closing run
+constexpr int RUN_LONGER_K = 500, RUN_LONGER_SA = 24;         // from this many: runs of 24 and a closing run
+CC4_HD constexpr int run_long_sa(int k) { return k >= RUN_LONGER_K ? RUN_LONGER_SA : RUN_LONG_SA; }
+CC4_HD constexpr RunConfig run_config_for_call(int k, int cfgSA, int cfgSB, int cfgnB, int cfgsingle) {
+  if (cfgSA != 0 || cfgSB != 1 || cfgnB != 0 || cfgsingle != 0 || k < RUN_LONG_K) return RunConfig{cfgSA, cfgSB, cfgnB, cfgsingle};
+  const int SA = run_long_sa(k), rest = k % SA;
+  return rest > 1 ? RunConfig{SA, rest, 1, 0} : RunConfig{SA, 1, 0, 0};       // (rest == 1: the one step left over is a single step)
+}
+CC4_HD constexpr RunSplit run_split_for_call(int k, int cfgSA, int cfgSB, int cfgnB, int cfgsingle) {
+  const RunConfig c = run_config_for_call(k, cfgSA, cfgSB, cfgnB, cfgsingle);
+  return run_split(k, c.SA, c.SB, c.nB, c.single);
+}
 // run j of the call: its first step and its length
 CC4_HD constexpr void run_span(const RunSplit& s, int j, int& k0, int& len) {
   if (j < s.nA) { k0 = j * s.SA; len = s.SA; }
@@ -88,6 +116,9 @@ constexpr bool same_split(const RunSplit& a, int SA, int nA, int SB, int nB, int
 static_assert(same_split(run_split(20, 0, 1, 0, 0), 4, 5, 1, 0, 5), "the default split of 20 steps: five runs of 4");
 static_assert(same_split(run_split(500, 0, 1, 0, 0), 8, 62, 1, 0, 66), "the default split of 500 steps: 62 runs of 8, then 4 single steps");
 static_assert(same_split(run_split(7, 1, 1, 0, 0), 1, 7, 1, 0, 7) && same_split(run_split(30, 8, 2, 3, 1), 8, 2, 2, 3, 13), "SA = 1: every step a run; 8,2,3,1 on 30 steps: 16 + 6 + 8 single");
+static_assert(same_split(run_split_for_call(99, 0, 1, 0, 0), 8, 12, 1, 0, 15) && same_split(run_split_for_call(100, 0, 1, 0, 0), 8, 12, 4, 1, 13) &&
+              same_split(run_split_for_call(500, 0, 1, 0, 0), 24, 20, 20, 1, 21) && same_split(run_split_for_call(505, 0, 1, 0, 0), 24, 21, 1, 0, 22) &&
+              same_split(run_split_for_call(500, 8, 1, 0, 0), 8, 62, 1, 0, 66), "a long call with no pattern given: what is left over is one closing run; an explicit pattern stays");
 static_assert(part_episodes(5000, 256, 135) == 20 && part_episodes(5000, 256, 136) == 19 && part_episodes(3, 8, 5) == 0, "5000 episodes on 256 CUs: 136 partitions of 20, 120 of 19");
 static_assert(ticket_count(5000, 256, 136, 3, 4) == 4u && ticket_count(3, 8, 1, 1, 2) == 0u, "19 episodes in 4 groups: 5 5 5 4; one episode: nothing in group 1");
 static_assert(pgroup_slot(pgroup_episode(700, 256, 4, 3), 256, 4) == part_of(700, 256) * 4 + 3 && xchg_groups32(5000) == 157 && xchg_group32_size(5000, 156) == 8, "");

@@ -41,6 +41,10 @@ int cc4_debug_shadow_handle(cc4_handle* h, cc4_handle** out);
  * one; out[1] the four-wave step kernel's register budget (k_step_philox<., 1 / 7 / 8>: cc4_step_kernel names all three alike); out[2] the multi-step
  * build (5: k_run_philox, 8: k_run_philox8; meaningful where cc4_run_kernel names one of them). */
 int cc4_debug_step_build(cc4_handle* h, int32_t out[3]);
+/* test hook, read-only: the runs of steps the most recent launch of a persistent kernel (k_run_philox1 and its kin, k_run_pcg) was cut into -- out[0] steps
+ * of a run, out[1] how many of them, out[2] / out[3] the same of the closing runs, out[4] the items of an episode (all zero: no such launch yet).  Only the
+ * headline kernel k_run_philox1 takes the long-call pattern (csrc/cc4_sched.h run_config_for_call). */
+int cc4_debug_last_run_split(cc4_handle* h, int32_t out[5]);
 
 #ifdef __cplusplus
 }
