@@ -6,6 +6,7 @@
 #include "cc4_features.h"
 #include "cc4_red_view.h"
 #include "cc4_blue_view.h"
+#include "cc4_reward_terms.h"
 
 static thread_local std::string g_create_err;
 
@@ -656,7 +657,7 @@ int cc4_step_ex(cc4_handle* h, const int32_t* actions, const uint8_t* messages, 
     }
   }
   HIPCHK(h, hipMemcpyAsync(h->d_ext, h->h_ext.data(), h->h_ext.size() * sizeof(ExtAct), hipMemcpyHostToDevice, h->stream));
-  h->ext_seen = true; h->ext_dirty = true; h->ext_green_dirty = green != nullptr;
+  h->ext_seen = true; h->ext_submitted = true; h->ext_dirty = true; h->ext_green_dirty = green != nullptr;
   if (actions) HIPCHK(h, hipMemcpyAsync(h->d_actions, actions, n * NBLUE * sizeof(int32_t), hipMemcpyDefault, h->stream));
   if (messages) HIPCHK(h, hipMemcpyAsync(h->d_msgs, messages, n * NBLUE * MSG_LEN, hipMemcpyDefault, h->stream));
   if (launch_step(h, actions ? h->d_actions : nullptr, messages ? h->d_msgs : nullptr, false, 0, 0, true, true)) return -1;
@@ -706,7 +707,7 @@ int cc4_step_red_device(cc4_handle* h, const int32_t* d_actions, const uint8_t* 
   RedSubmitArgs a{h->d_state, d_red, h->d_ext, n, h->ext_green_dirty ? 1 : 0, h->d_copy_fault};
   hipLaunchKernelGGL(k_red_submit, dim3((n * NRED + 255) / 256), dim3(256), 0, h->stream, a);
   HIPCHK(h, hipGetLastError());
-  h->ext_seen = true; h->ext_dirty = true; h->ext_green_dirty = false;
+  h->ext_seen = true; h->ext_submitted = true; h->ext_dirty = true; h->ext_green_dirty = false;
   return launch_step(h, d_actions, d_messages, false, 0, 0, true, true);
 }
 // What each red agent knows as tensors: one launch on the main stream behind the group streams, no host synchronisation; it only reads rows.
@@ -787,6 +788,62 @@ int cc4_blue_view_from_row(const void* hot_row, const void* cold_row, int32_t st
   free(s);
   return rc;
 }
+// ---- reward terms (include/cc4.h; cc4_k_reward.hip; the definition: cc4_reward_terms.h).
+// The switch: the handle behaves as after a cc4_step_red_device whose records were all "the scripted class acts" -- d_ext filled with none-records,
+// ext_seen set -- so launch_step and the `plain` tests of cc4_api_run.hip select the full builds and pass a.ext with no condition of their own.
+int cc4_enable_reward_terms(cc4_handle* h, int32_t enable) {
+  const char* who = "cc4_enable_reward_terms";
+  if (h->rollout_k > 0) { h->err = std::string(who) + ": a rollout is in flight on this handle: cc4_rollout_end first"; return -2; }
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  if (join_groups(h)) return -1;
+  if (enable) {
+    if (!h->d_ext) HIPCHK(h, hipMalloc(&h->d_ext, (size_t)h->cfg.num_envs * EXT_PER_ENV * sizeof(ExtAct)));
+    if (!h->ext_seen || h->ext_dirty || h->ext_green_dirty) {
+      HIPCHK(h, hipMemsetAsync(h->d_ext, 0xFF, (size_t)h->cfg.num_envs * EXT_PER_ENV * sizeof(ExtAct), h->stream));     // type -1 everywhere: nothing submitted
+      h->ext_dirty = false; h->ext_green_dirty = false;
+    }
+    h->terms_on = true; h->ext_seen = true;
+  } else {
+    h->terms_on = false;
+    h->ext_seen = h->ext_submitted;      // (a handle that has taken red / green actions keeps serving the rates a queued action came with)
+  }
+  return 0;
+}
+int cc4_reward_terms_enabled(cc4_handle* h) { return h && h->terms_on ? 1 : 0; }
+// One launch on the main stream behind the group streams, no host synchronisation; it only reads rows: the hot rows and the record of the cold rows
+// as the last step left them.
+int cc4_reward_terms_device(cc4_handle* h, const void* d_bank, int32_t capacity, const int32_t* d_ids, int32_t n, int32_t* d_terms, int32_t* d_words) {
+  const char* who = "cc4_reward_terms_device";
+  if (h->rollout_k > 0) { h->err = std::string(who) + ": a rollout is in flight on this handle: cc4_rollout_end first"; return -2; }
+  if (n < 0) { h->err = std::string(who) + ": n < 0"; return -2; }
+  if (n == 0) return 0;
+  if (!d_terms || reinterpret_cast<uintptr_t>(d_terms) % 16 || reinterpret_cast<uintptr_t>(d_words) % 16) {
+    h->err = std::string(who) + ": the terms buffer is required and must be 16-byte aligned (the words: 16-byte aligned or NULL)"; return -2;
+  }
+  if (d_bank && capacity < 1) { h->err = std::string(who) + ": a bank needs a capacity of at least one slot"; return -2; }
+  if (reinterpret_cast<uintptr_t>(d_bank) % 64) { h->err = std::string(who) + ": a bank must be 64-byte aligned"; return -2; }
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  if (join_groups(h)) return -1;
+  RewardArgs a{h->d_state, h->d_cold, h->cold_row, static_cast<const uint8_t*>(d_bank), slot_bytes(h->cold_row), d_ids, n,
+               d_bank ? capacity : h->cfg.num_envs, h->cfg.steps, h->cfg.rng_mode, d_terms, d_words, h->d_copy_fault};
+  hipLaunchKernelGGL(k_reward_terms, dim3(n), dim3(WAVE), 0, h->stream, a);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+// The same on the host, from one hot row and (optionally) its cold row: no device, no handle.  Only the record of the cold row is read; it is
+// copied, like the hot row, because the caller's bytes may sit at any address.
+int cc4_reward_terms_from_row(const void* hot_row, const void* cold_row, int32_t steps, int32_t* terms, int32_t* words) {
+  if (!hot_row || !terms || !words) return -2;
+  EnvState* s = row_copy(hot_row);
+  if (!s) return -1;
+  if (steps <= 0) steps = s->steps;
+  if (steps <= 0 || steps > (1 << 20)) { free(s); return -2; }
+  RewardRec rec;
+  if (cold_row) memcpy(&rec, static_cast<const char*>(cold_row) + offsetof(EnvCold, rwd), sizeof(RewardRec));
+  reward_terms_from_row(s, cold_row ? &rec : nullptr, terms, words);
+  free(s);
+  return 0;
+}
 int cc4_red_record_from_row(const void* hot_row, int32_t agent, const int32_t* words, cc4_agent_action* out) {
   if (!hot_row || !words || !out || agent < 0 || agent >= NRED) return -2;
   EnvState* s = row_copy(hot_row);
@@ -813,7 +870,7 @@ int cc4_group_info(cc4_handle* h, int32_t g, int32_t* lo, int32_t* hi, void** hi
 }
 static int group_prologue(cc4_handle* h, int32_t g, const char* who) {
   if (g < 0 || g >= h->ngroups) { h->err = std::string(who) + ": no such group"; return -2; }
-  if (h->comm || h->evlog_on || h->ext_seen) { h->err = std::string(who) + ": group-wise stepping serves handles without a communicator, event log or submitted red / green actions"; return -2; }
+  if (h->comm || h->evlog_on || h->ext_seen) { h->err = std::string(who) + ": group-wise stepping serves handles without a communicator, event log, submitted red / green actions or recorded reward terms (cc4_enable_reward_terms)"; return -2; }
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   if (h->ngroups > 1 && h->main_ahead) {     // e.g. a reset or an upload on the main stream: the group streams start behind it
     HIPCHK(h, hipEventRecord(h->mev, h->stream));

@@ -12,7 +12,7 @@ int cc4_rollout_begin(cc4_handle* h, int32_t k) {
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   if (h->rollout_k > 0) { h->err = "cc4_rollout_begin: a rollout is in flight (cc4_rollout_end)"; return -2; }
   if (k <= 0 || k > ROLLOUT_MAX_K) { h->err = "cc4_rollout_begin: 1 .. 2^20 steps"; return -2; }
-  if (h->cfg.rng_mode != 1 || h->comm || h->evlog_on || h->ext_seen || h->d_prof) { h->err = "cc4_rollout_begin: for counter-mode handles without a communicator, event log or submitted red / green actions"; return -2; }
+  if (h->cfg.rng_mode != 1 || h->comm || h->evlog_on || h->ext_seen || h->d_prof) { h->err = "cc4_rollout_begin: for counter-mode handles without a communicator, event log, submitted red / green actions or recorded reward terms (cc4_enable_reward_terms)"; return -2; }
   if (h->persist_state == 0) { if (persist_setup(h)) return -1; }
   if (h->persist_state != 1) { h->err = "cc4_rollout_begin: this handle has no persistent kernel (a batch the chip holds at once, or a device picture the schedule refuses): step it with cc4_step_device"; return -2; }
   if (join_groups(h)) return -1;

@@ -1,5 +1,5 @@
 // cc4_args.h -- what the host side and the kernels of libcc4.so share: the constants, the argument blocks of the kernels (StepArgs, XchgArgs, RunArgs,
-// PlanArgs, ResetArgs, CopyArgs, FeatArgs, RedSubmitArgs, RedViewArgs, BlueViewArgs), the snapshot-slot layout, and the register budgets of the kernels.  No device helper (cc4_kernels.h) and nothing of
+// PlanArgs, ResetArgs, CopyArgs, FeatArgs, RedSubmitArgs, RedViewArgs, BlueViewArgs, RewardArgs), the snapshot-slot layout, and the register budgets of the kernels.  No device helper (cc4_kernels.h) and nothing of
 // the C++ host library (cc4_host.h).  The index arithmetic of the persistent schedule -- partitions, tickets, runs, the progress word -- is in cc4_sched.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -229,5 +229,17 @@ struct BlueViewArgs {
   int count, cap, steps, rng_mode;
   uint8_t* hosts;                                        // [count][NBLUE][137][8], 8-byte aligned
   int32_t* scal;                                         // [count][NBLUE][16] or null
+  uint32_t* fault;
+};
+
+// ---- reward terms (cc4_k_reward.hip; the definition: cc4_reward_terms.h).  cc4_reward_terms_device: entry i reads episode ids[i] (null: i) of the
+// handle -- of its hot row about 150 bytes, of its cold row the 64-byte record EnvCold.rwd -- or the two rows inside slot ids[i] of a snapshot bank
+struct RewardArgs {
+  const EnvState* st; const EnvCold* cold; size_t cold_row;
+  const uint8_t* bank; size_t slot;
+  const int32_t* ids;
+  int count, cap, steps, rng_mode;
+  int32_t* terms;                                        // [count][9][4], 16-byte aligned
+  int32_t* words;                                        // [count][16], 16-byte aligned, or null
   uint32_t* fault;
 };

@@ -1012,6 +1012,7 @@ CC4_HD void reset_finish(Ctx x, ResetCarry k, int steps, uint32_t topo_seed, boo
   }
   s->done = (uint8_t)(0 >= steps - 1);
   s->n_actions = NBLUE + s->n_green + NRED;
+  x.c->rwd = RewardRec{};                            // the new episode has taken no step: no stamp of the old one may read as one of its own
   if (topo_seed) x.r->s_lo = k.env_key;
   if (rng_is_copy) s->rng = *x.r;
   rng_park(&s->rng);
@@ -2356,7 +2357,12 @@ CC4_HD bool step_phase(Ctx x, bool init_accumulators = true) {
   }
   rng_begin_step(&s->rng, (uint32_t)s->step_count);
   if (x.lg) { x.lg->n = 0; x.lg->step = (uint32_t)s->step_count; }
-  if (x.ext) { x.c->gfail[0] = 0; x.c->gfail[1] = 0; x.c->gfail[2] = 0; }
+  if (x.ext) {
+    x.c->gfail[0] = 0; x.c->gfail[1] = 0; x.c->gfail[2] = 0;
+    RewardRec& w = x.c->rwd;                         // (restore_at is the submissions': they may run beside this function)
+    w.lwf[0] = 0; w.lwf[1] = 0; w.lwf[2] = 0; w.asf[0] = 0; w.asf[1] = 0; w.asf[2] = 0;
+    w.stamp = (uint32_t)s->step_count + 1u;
+  }
   s->action_cost = 0.f;
   if (init_accumulators) {
     s->brm = 0; s->n_restore = 0;
@@ -2408,6 +2414,7 @@ CC4_HD void step_blue_submit(Ctx x, int b, int action_index) {
 #else
     s->n_restore++;
 #endif
+    if (x.ext) x.c->rwd.restore_at[b] = (uint32_t)s->step_count + 1u;   // (step_count: written by step_end only)
   }
   a.ticks = (uint8_t)(dur ? dur : blue_duration(a.type));
   if (!aget<AW_BUSY>(act_load(&s->blue[b].queue))) act_store(&s->blue[b].queue, aset<AW_BUSY>(act_pack(a), 1));
@@ -2578,14 +2585,14 @@ CC4_HD int step_green_exec(Ctx x, int g, const uint32_t* pre = nullptr) {
   const ExtAct* ea = (x.ext && x.ext[NRED + g].type != XA_NONE) ? &x.ext[NRED + g] : nullptr;   // its own rates, if it came with any
   if (act == 0) {
     const bool ok = green_access_service(x, gh, gp, (ea && (ea->flags & XF_RATE0)) ? ea->rate0 : 0.01);
-    if (x.ext && !ok) bit_set_shared(x.c->gfail, g);
+    if (x.ext && !ok) { bit_set_shared(x.c->gfail, g); bit_set_shared(x.c->rwd.asf, g); }
     return ok ? 0 : reward_table(s->phase, own, RW_ASF);
   }
   if (act == 1) {
     bool want_phish = false;
     bool ok = green_local_work(x, gh, gp, &want_phish, (ea && (ea->flags & XF_RATE0)) ? ea->rate0 : 0.01, (ea && (ea->flags & XF_RATE1)) ? ea->rate1 : 0.01);
     if (want_phish) bit_set_shared(x.w->phish_mask, g);   // green agents may be resolved on different lanes
-    if (x.ext && !ok) bit_set_shared(x.c->gfail, g);
+    if (x.ext && !ok) { bit_set_shared(x.c->gfail, g); bit_set_shared(x.c->rwd.lwf, g); }
     return ok ? 0 : reward_table(s->phase, own, RW_LWF);
   }
   return 0;
@@ -2780,7 +2787,12 @@ CC4_HD void step_end(Ctx x, const uint8_t* messages, bool copy_msgs = true, bool
   }
   s->action_cost = -(float)s->n_restore;
   s->reward = (float)brm + s->action_cost;
-  if (x.ext) for (int g = 0; g < s->n_green; ++g) if (x.w->green_act[g] == 3) bit_set_shared(x.c->gfail, g);   // submitted green actions that were invalid
+  if (x.ext) {
+    for (int g = 0; g < s->n_green; ++g) if (x.w->green_act[g] == 3) bit_set_shared(x.c->gfail, g);   // submitted green actions that were invalid
+    // Restore stamps of earlier steps go: what a recording step leaves in EnvCold.rwd depends on that step alone (this step's submissions are all in,
+    // the next step's come behind this function, as for n_restore below)
+    for (int b = 0; b < NBLUE; ++b) if (x.c->rwd.restore_at[b] != (uint32_t)s->step_count) x.c->rwd.restore_at[b] = 0;
+  }
   if (copy_msgs) for (int b = 0; b < NBLUE; ++b) step_messages(s, messages, b);
   s->brm = 0; s->n_restore = 0; s->n_actions = NBLUE + s->n_green + NRED;   // the next step's accumulators (see step_phase)
   rng_park(&s->rng);

@@ -161,6 +161,9 @@ struct cc4_handle {
   bool multistep = false;         // k_run_philox: cc4_run_random_steps as ONE launch, every block looping over the steps of its episode
   ExtAct* d_ext = nullptr;        // [num_envs][EXT_PER_ENV]
   bool ext_seen = false, ext_dirty = false;   // dirty: d_ext holds the records of an earlier step
+  // ext_seen = ext_submitted || terms_on.  ext_submitted: a red or green action was submitted on this handle (cc4_step_ex, cc4_step_red_device): it never
+  // leaves the full builds.  terms_on: cc4_enable_reward_terms -- the same machinery with all-none records, which the switch may take back
+  bool ext_submitted = false, terms_on = false;
   // ext_green_dirty: false only while the GREEN records of d_ext are known to be all XA_NONE; cc4_step_red_device then writes its six red records per episode
   // and nothing else, otherwise it sets the green records to none as well.  True from the start (d_ext not allocated, or allocated and never written: a
   // cc4_step_ex that refused its records has allocated it already).  Cleared by: k_red_submit with clear_green (cc4_step_red_device), the upload of a

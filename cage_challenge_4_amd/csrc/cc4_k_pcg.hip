@@ -409,6 +409,7 @@ __device__ __forceinline__ void pcg_body(StepArgs a, const int e, const int lane
     int32_t act = a.actions ? a.actions[e * NBLUE + b] : -1;
     if (a.rand_out) { act = random_blue_action(a.rand_seed0, a.rand_t, e, b); a.rand_out[e * NBLUE + b] = act; }
     Ctx xb{s, cold_e, &rl, hd, &work};
+    xb.ext = xt;                   // (a submitted Restore is recorded: EnvCold.rwd)
     step_blue_submit(xb, b, act);
   }
   __syncthreads();

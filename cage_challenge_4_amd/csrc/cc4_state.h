@@ -460,6 +460,19 @@ struct alignas(4) EvRec {
 };
 struct alignas(16) EvLog { uint32_t n, step, enabled, pad; EvRec rec[MAX_EV]; };
 
+// The pieces of a step's reward that the step itself throws away (the definition of what is made of them: cc4_reward_terms.h).  Written only by a
+// step that carries submitted-action records (Ctx.ext: the full builds of the step kernels, cc4_step_ex, cc4_enable_reward_terms), zeroed by every
+// regeneration (reset_finish).
+//   lwf / asf     bit g: green_agent_g's action of the step charged the LocalWork-failed / AccessService-failed term of its subnet -- whatever the
+//                 table's value in this phase.  Cleared by step_phase, set by step_green_exec: the green actions run behind barriers in every kernel
+//   stamp         step_count + 1 as step_phase saw it = step_count as step_end leaves it: the record describes the row's last step iff they are equal
+//   restore_at[b] step_count + 1 of the last step in which blue agent b SUBMITTED a Restore (what step_end charges -1 for).  A stamp, not a bit: in
+//                 the lane-parallel kernels a submission may run before lane 0 has finished step_phase (see there), so nothing here is cleared by
+//                 step_phase and set by a submission.  step_end zeroes the entries of earlier steps, so that after a recording step the record is a
+//                 function of that step alone
+struct alignas(16) RewardRec { uint32_t lwf[3], asf[3], stamp, pad0, restore_at[NBLUE], pad1[3]; };
+static_assert(sizeof(RewardRec) == 64 && NBLUE == 5 && MAXG <= 96, "four 16-byte words; three bitmap words cover the green agents");
+
 // The cold row of an episode: a fixed part (this struct) followed by two containers whose capacity depends on the episode length
 // the handle was created for (EnterpriseScenarioGenerator(steps=...)):
 //   uint32_t sus[NBLUE][cold_sus_cap(steps)]    VelociraptorServer.sus_pids of blue agent b: (host << 16) | pid, chronological
@@ -478,6 +491,7 @@ struct alignas(16) EnvCold {
                                      // valid while the agent's queued / executing Act carries AQ_RATE0 / AQ_RATE1)
   uint32_t gfail[4];                 // bit g: green_agent_g's action of the last step returned Observation(False) (what CybORG.step /
                                      // parallel_step report as its 'success'; written by the full builds of the step only; word 3 unused)
+  RewardRec rwd;                     // why the last step's reward was what it was (cc4_reward_terms.h); written by the full builds of the step only
   uint16_t known_sid[NRED][MAX_KS];  // ActionSpace.server_session keys with value True of red agent r, insertion order; entries
                                      // [0, RedHdr.nknown) are valid (RedAgent.known_bm holds the ids < 256 as a bitmap)
   // CybORG.set_seed (env.py:316-325) hands the new Generator to the controller, the state and the hosts
@@ -510,7 +524,7 @@ CC4_HD const uint32_t* cold_povf(const EnvCold* c, int steps, int h) {
 // The LIVE extents of a cold row: what a copy of the episode (cc4_copy_episodes_device) moves.  Everything else in the row is dead --
 // written before it is read again by every path that uses it -- and keeps whatever the destination held:
 //   CS_HS      hs (+ hs_pad)                              CS_EVHDR  the evlog header
-//   CS_EVREC   evlog.rec[0, n) when the log is on         CS_TAIL   xrate, gfail, known_sid, rng2 (contiguous: the end of the fixed part)
+//   CS_EVREC   evlog.rec[0, n) when the log is on         CS_TAIL   xrate, gfail, rwd, known_sid, rng2 (contiguous: the end of the fixed part)
 //   CS_EPH     eph whole, numpy-stream mode only (eph_port / eph_clear return at once in the counter mode)
 //   CS_FIXED + i                  kports[i] for the pool slots i set in spool_used (rs_add clears the row of a new abstract session)
 //   CS_FIXED + RS_POOL + b        sus[b][0, blue[b].nsus)
@@ -523,7 +537,8 @@ CC4_HD ColdSpan cold_live_span(const EnvState* s, int steps, int rng_mode, int e
   constexpr uint32_t o_ev = (uint32_t)offsetof(EnvCold, evlog), o_tail = (uint32_t)offsetof(EnvCold, xrate);
   static_assert(offsetof(EnvCold, eph) % 16 == 0 && offsetof(EnvCold, evlog) % 16 == 0 && offsetof(EnvCold, kports) % 16 == 0 &&
                 offsetof(EnvCold, xrate) % 16 == 0 && (MAXH + 7) % 16 == 0 && offsetof(EvLog, rec) == 16, "live spans start 16-byte aligned");
-  static_assert(offsetof(EnvCold, gfail) > offsetof(EnvCold, xrate) && offsetof(EnvCold, known_sid) > offsetof(EnvCold, gfail) &&
+  static_assert(offsetof(EnvCold, gfail) > offsetof(EnvCold, xrate) && offsetof(EnvCold, rwd) > offsetof(EnvCold, gfail) && offsetof(EnvCold, rwd) % 16 == 0 &&
+                offsetof(EnvCold, known_sid) > offsetof(EnvCold, rwd) &&
                 offsetof(EnvCold, rng2) > offsetof(EnvCold, known_sid), "xrate .. rng2 close the fixed part");
   if (k == CS_HS) return {0u, (uint32_t)offsetof(EnvCold, eph)};
   if (k == CS_EVHDR) return {o_ev, 16u};

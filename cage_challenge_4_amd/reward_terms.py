@@ -1,0 +1,60 @@
+"""Reward terms as fixed-shape arrays: why the team reward of the last step was what it was (include/cc4.h, cc4_reward_terms_device) -- which
+subnet, which kind, whose Restore.  The step adds its reward up from a penalty per failed green action (LocalWork, AccessService), a penalty per
+executed Impact and -1 per submitted Restore, and keeps only the sum; an env that records (enable_reward_terms(), or one that steps with red or
+green actions) keeps the pieces of its last step.
+
+Per subnet  [9, 4] int32   row s = the engine's subnet id (SUBNET_NAMES), columns TERM_COLUMNS: the three penalty sums (<= 0) and the number of
+                           charged events, counted whatever their weight in this mission phase.
+Words       [16] int32     WORDS: valid, step_count, phase, brm, action_cost, the five blue agents' shares (the terms of the subnets the agent
+                           defends, ZONE_OF_SUBNET, plus its own Restore cost), the unowned rest, the five agents' own Restore costs.
+'valid' is 1 iff the record was written by the step that produced the row; otherwise (a regenerated episode, a step taken without recording,
+edit_state(SE_SET_STEP), no cold row) everything but step_count and phase is zero.  With valid set
+    words[brm] + words[action_cost] == reward          and          sum(words[share_0 .. share_4]) + words[unowned] == words[brm] + words[action_cost]
+
+Two ways to the same numbers:
+  CC4VecEnv.reward_terms() / CC4TorchVecEnv.reward_terms()   the HIP kernel over the batch (k_reward_terms)
+  from_row(hot, cold=None, steps=0)   the same definition compiled for the host (cc4_reward_terms_from_row): from cc4_get_state / cc4_get_cold
+                                      rows or a checkpoint, in a process without a GPU"""
+import ctypes
+import numpy as np
+from . import _lib as L
+
+NUM_BLUE, SUBNETS, COLS, NWORDS = L.NUM_BLUE, L.REWARD_SUBNETS, L.REWARD_COLS, L.REWARD_WORDS
+
+TERM_COLUMNS = {'lwf': 0, 'asf': 1, 'ria': 2, 'events': 3}
+WORDS = {'valid': 0, 'step_count': 1, 'phase': 2, 'brm': 3, 'action_cost': 4,
+         'share_0': 5, 'share_1': 6, 'share_2': 7, 'share_3': 8, 'share_4': 9, 'unowned': 10,
+         'restore_0': 11, 'restore_1': 12, 'restore_2': 13, 'restore_3': 14, 'restore_4': 15}
+SHARE_WORDS = slice(5, 10)               # words[..., SHARE_WORDS]: per blue agent
+RESTORE_WORDS = slice(11, 16)
+SUBNET_NAMES = ('restricted_zone_a_subnet', 'operational_zone_a_subnet', 'restricted_zone_b_subnet', 'operational_zone_b_subnet',
+                'contractor_network_subnet', 'public_access_zone_subnet', 'admin_network_subnet', 'office_network_subnet',
+                'internet_subnet')       # SUBNET enum order (wrappers.SUBNET_NAMES)
+ZONE_OF_SUBNET = (0, 1, 2, 3, -1, 4, 4, 4, -1)      # the blue agent that defends the subnet; -1: nobody
+
+
+def _bytes(x, size, what):
+    if isinstance(x, (bytes, bytearray, memoryview)):
+        x = np.frombuffer(x, np.uint8)
+    x = np.ascontiguousarray(x, dtype=np.uint8).ravel()
+    if size is not None and x.size != size:
+        raise ValueError(f'{what} has {size} bytes, got {x.size}')
+    return x
+
+
+def from_row(hot, cold=None, steps=0):
+    """(terms [9, 4] int32, words [16] int32) of one packed hot row (CC4VecEnv.get_state(e)) and its cold row (the second part of
+    CC4VecEnv.snapshot(e)).  cold=None: valid is 0.  steps: the episode length of the env the rows come from; 0: the length the hot row itself
+    records."""
+    lib = L.load()
+    hot = _bytes(hot, lib.cc4_state_bytes(), 'a hot row')
+    if cold is not None:
+        cold = _bytes(cold, None, 'a cold row')         # (the whole cc4_cold_bytes() of its env: the record lies in its fixed part)
+    terms = np.zeros((SUBNETS, COLS), np.int32)
+    words = np.zeros(NWORDS, np.int32)
+    vp = ctypes.c_void_p
+    rc = lib.cc4_reward_terms_from_row(hot.ctypes.data_as(vp), None if cold is None else cold.ctypes.data_as(vp), int(steps),
+                                       terms.ctypes.data_as(vp), words.ctypes.data_as(vp))
+    if rc:
+        raise L.CC4Error(f'cc4_reward_terms_from_row failed (rc={rc})')
+    return terms, words

@@ -62,6 +62,11 @@ class CC4TorchVecEnv:
                                                   entries per host (counts, ports, remote hosts)
     enable_event_log(on=True)                     the per-step event log (full builds of the step kernel, one launch per step)
 
+    Reward terms (include/cc4.h cc4_reward_terms_device; cage_challenge_4_amd.reward_terms):
+    enable_reward_terms(on=True)                  record the pieces of every step's reward (full builds of the step kernel, one launch per step)
+    reward_terms(ids=None, bank=None, out=None) -> (terms [n, 9, 4] int32, words [n, 16] int32)   per subnet the LocalWork / AccessService /
+                                                  Impact penalties and the number of events; brm, action cost, each blue agent's share
+
     Mixed opponents in one batch (include/cc4.h cc4_set_policies_device, cc4_reset_device):
     set_opponents(red=None, green=None, blue=None)   integer tensors [N] on the device: the classes each episode regenerates into from its next
                                                      regeneration on (never mid-episode); None keeps
@@ -384,6 +389,50 @@ class CC4TorchVecEnv:
             s = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
             self.venv._chk(self.lib.cc4_stream_wait(self._h, s), 'cc4_stream_wait')
             self.venv.enable_event_log(on)
+
+    def reward_terms(self, ids=None, bank=None, out=None):
+        """Why the last step's reward was what it was (cc4_reward_terms_device, include/cc4.h; columns and words: reward_terms.TERM_COLUMNS /
+        WORDS) as tensors on the env's device: (terms [n, 9, 4] int32, words [n, 16] int32) -- per subnet the LocalWork-failed,
+        AccessService-failed and Impact penalties and the number of charged events; valid, step_count, phase, brm, action cost, the five blue
+        agents' shares, the unowned rest and the agents' own Restore costs.  words[:, 0] is 1 where the last step recorded
+        (enable_reward_terms(), or an env that steps with red_actions); then words[:, 3] + words[:, 4] == reward.  ids, bank, out and the
+        ordering on the current stream as state_features(); no host copy, no host wait.  A faulty entry gives all-zero rows, and
+        check_errors() raises CC4EngineError for it."""
+        with torch.cuda.device(self.device):
+            s = torch.cuda.current_stream(self.device)
+            vp = ctypes.c_void_p
+            bp, cap = self._bank(bank) if bank is not None else (None, 0)
+            if ids is not None:
+                ids = self._index(ids, 'ids')
+                n, ip = int(ids.numel()), vp(ids.data_ptr())
+            else:
+                n, ip = (cap if bank is not None else self.num_envs), None
+            shapes = ((n, L.REWARD_SUBNETS, L.REWARD_COLS), (n, L.REWARD_WORDS))
+            if out is None:
+                terms = torch.empty(shapes[0], dtype=torch.int32, device=self.device)
+                words = torch.empty(shapes[1], dtype=torch.int32, device=self.device)
+            else:
+                terms, words = out
+                for x, shp in ((terms, shapes[0]), (words, shapes[1])):
+                    if (not torch.is_tensor(x) or tuple(x.shape) != shp or x.dtype != torch.int32 or x.device != self.device or not x.is_contiguous()
+                            or x.data_ptr() % 16):
+                        raise ValueError(f'out must be contiguous, 16-byte aligned int32 tensors ({list(shapes[0])}, {list(shapes[1])}) on {self.device}')
+            lib, h, sp = self.lib, self._h, vp(s.cuda_stream)
+            rc = lib.cc4_stream_wait(h, sp) or lib.cc4_reward_terms_device(h, bp, cap, ip, n, vp(terms.data_ptr()), vp(words.data_ptr()))
+            if rc:
+                self.venv._chk(rc, 'cc4_reward_terms_device')
+            self.venv._chk(lib.cc4_stream_signal(h, sp), 'cc4_stream_signal')
+        return terms, words
+
+    def enable_reward_terms(self, on=True):
+        """CC4VecEnv.enable_reward_terms (cc4_enable_reward_terms): record the pieces of every step's reward, which reward_terms() turns into
+        tensors.  The record has a price: the env runs the full builds of its step kernel, one launch per step, and leaves the one-launch
+        forms of run / plan calls (after a plan only the last step's terms exist).  An env that steps with red_actions records anyway."""
+        with torch.cuda.device(self.device):
+            s = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            self.venv._chk(self.lib.cc4_stream_wait(self._h, s), 'cc4_stream_wait')
+            self.venv.enable_reward_terms(on)
+            self.venv._chk(self.lib.cc4_stream_signal(self._h, s), 'cc4_stream_signal')
 
     def set_opponents(self, red=None, green=None, blue=None):
         """Assign opponent classes per episode from the device (cc4_set_policies_device, include/cc4.h): red (0..3), green (0..1), blue (0..1) each

@@ -562,6 +562,61 @@ class CC4VecEnv:
             raise_on_copy_faults(faults.value)
         return hosts, scal
 
+    def enable_reward_terms(self, on=True):
+        """cc4_enable_reward_terms: record the pieces of every step's reward (reward_terms()).  The env then runs the full builds of its step
+        kernel, one launch per step, and leaves the one-launch forms of run / plan calls and rollouts, as with submitted red / green actions;
+        trajectories do not change.  on=False returns to the fast builds unless red or green actions were ever submitted on this env."""
+        self._chk(self.lib.cc4_enable_reward_terms(self._h, int(bool(on))), 'cc4_enable_reward_terms')
+
+    @property
+    def reward_terms_enabled(self):
+        return bool(self.lib.cc4_reward_terms_enabled(self._h))
+
+    def reward_terms_device(self, d_terms, d_words=None, n=None, d_ids=None, d_bank=None, capacity=0):
+        """cc4_reward_terms_device into device memory of the caller's (device addresses): terms [n, 9, 4] int32 and words [n, 16] int32 (or None),
+        both 16-byte aligned, of episodes d_ids (int32 [n] on the device; None: 0 .. n-1) of the env or of the slots of a snapshot bank.
+        Enqueued, no host wait."""
+        vp = ctypes.c_void_p
+        as_p = lambda x: x if x is None or isinstance(x, vp) else vp(int(x))      # noqa: E731
+        rc = self.lib.cc4_reward_terms_device(self._h, as_p(d_bank), int(capacity), as_p(d_ids), self.num_envs if n is None else int(n),
+                                              as_p(d_terms), as_p(d_words))
+        if rc:
+            self._chk(rc, 'cc4_reward_terms_device')
+
+    def reward_terms(self, ids=None):
+        """Why the last step's reward was what it was (cc4_reward_terms_device, include/cc4.h; columns and words: reward_terms.TERM_COLUMNS /
+        WORDS): (terms [n, 9, 4] int32, words [n, 16] int32) of episodes ids (None: all), as NumPy arrays.  Synchronises, like the other
+        getters.  words[:, 0] says whether the last step recorded (enable_reward_terms(), or an env that steps with red / green actions).  An
+        index out of range gives all-zero rows and raises CC4EngineError after the call."""
+        ids = None if ids is None else np.ascontiguousarray(ids, dtype=np.int32).ravel()
+        n = self.num_envs if ids is None else int(ids.size)
+        terms = np.zeros((n, L.REWARD_SUBNETS, L.REWARD_COLS), np.int32)
+        words = np.zeros((n, L.REWARD_WORDS), np.int32)
+        if n == 0:
+            return terms, words
+        hip, vp = _hip(), ctypes.c_void_p
+        b_ids = ((4 * n + 15) & ~15) if ids is not None else 0          # [ids | terms | words]: every part 16-byte aligned (144 n, 64 n)
+        _hip_chk(hip.hipSetDevice(self._dev), 'hipSetDevice')
+        d = vp()
+        _hip_chk(hip.hipMalloc(ctypes.byref(d), b_ids + terms.nbytes + words.nbytes), 'hipMalloc')
+        try:
+            if ids is not None:
+                _hip_chk(hip.hipMemcpy(d, ids.ctypes.data_as(vp), ids.nbytes, 1), 'hipMemcpy')
+            d_terms, d_words = vp(d.value + b_ids), vp(d.value + b_ids + terms.nbytes)
+            rc = self.lib.cc4_reward_terms_device(self._h, None, 0, d if ids is not None else None, n, d_terms, d_words)
+            rc2 = self.lib.cc4_synchronize(self._h)
+            if rc or rc2:
+                self._chk(rc or rc2, 'cc4_reward_terms_device')
+            _hip_chk(hip.hipMemcpy(terms.ctypes.data_as(vp), d_terms, terms.nbytes, 2), 'hipMemcpy')
+            _hip_chk(hip.hipMemcpy(words.ctypes.data_as(vp), d_words, words.nbytes, 2), 'hipMemcpy')
+        finally:
+            hip.hipFree(d)
+        if ids is not None and ((ids < 0) | (ids >= self.num_envs)).any():
+            faults = ctypes.c_uint32(0)
+            self._chk(self.lib.cc4_copy_faults(self._h, ctypes.byref(faults)), 'cc4_copy_faults')
+            raise_on_copy_faults(faults.value)
+        return terms, words
+
     def plan_kernel_for(self, k):
         """cc4_plan_kernel_for: the kernel a run_plan / step_plan call of k steps launches ('k_run_philox1p' / 'k_run_pcgp': one launch for the
         whole plan; else the step kernel, once per step)."""

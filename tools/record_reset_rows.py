@@ -8,6 +8,11 @@ without / with a topology seed.  Per group 128 seeds; per seed the zlib.crc32 of
 cold row at three stages: after a fresh cc4o_reset, after 12 oracle steps of random actions and a continued reset (continue_stream = 1), after a
 second continued reset.
 
+The cold row is summed as the recorded layout had it.  The fixed part has since grown by the reward record (EnvCold.rwd, between gfail and known_sid:
+csrc/cc4_state.h); whatever the oracle's layout shows between the end of gfail and known_sid must be all zero after a regeneration -- which is the
+record's own contract -- and is left out of the sum, so that every other byte of the row is still compared with the recording.  With an oracle of the
+recorded layout the gap is empty and the sum is the whole row's.
+
   python tools/record_reset_rows.py [--lib oracle/liboracle.so] [--out tests/golden/reset_rows_parent.json]
 """
 import argparse
@@ -57,7 +62,21 @@ def _bind(path):
     lib.cc4o_cold_bytes.argtypes = [vp]
     lib.cc4o_cold_ptr.restype = vp
     lib.cc4o_cold_ptr.argtypes = [vp, ci]
+    lib.cc4o_layout.argtypes = [ctypes.c_char_p, ci]
     return lib
+
+
+GFAIL_BYTES = 16                     # uint32_t gfail[4]
+
+
+def _gap(lib):
+    """[a, b): the bytes of the fixed part of the cold row between the end of gfail and known_sid (none in the recorded layout)."""
+    buf = ctypes.create_string_buffer(8192)
+    n = lib.cc4o_layout(buf, 8192)
+    lay = {k: int(v) for k, v in (ln.split() for ln in buf.raw[:n].decode().splitlines())}
+    a, b = lay['cold.gfail'] + GFAIL_BYTES, lay['cold.known_sid']
+    assert 0 <= b - a <= 64 and (b - a) % 16 == 0, (a, b)
+    return a, b
 
 
 def compute(lib_path):
@@ -66,15 +85,21 @@ def compute(lib_path):
     from oracle_binding import random_actions
     lib = _bind(lib_path)
     nh = lib.cc4o_state_bytes()
+    ga, gb = _gap(lib)
     out = {}
     for name, mode, steps, policy, topo in groups():
         h = ctypes.c_void_p(lib.cc4o_create2(SEEDS, steps))
         lib.cc4o_set_topology_seed(h, topo)
         nc = lib.cc4o_cold_bytes(h)
 
+        def cold_crc(i):
+            c = ctypes.string_at(lib.cc4o_cold_ptr(h, i), nc)
+            if any(c[ga:gb]):
+                raise AssertionError(f'{name}, seed {SEED0 + i}: bytes {ga}..{gb} of the cold row (behind gfail) are not zero after a regeneration')
+            return zlib.crc32(c[:ga] + c[gb:])
+
         def crcs():
-            return [[zlib.crc32(ctypes.string_at(lib.cc4o_state_ptr(h, i), nh)), zlib.crc32(ctypes.string_at(lib.cc4o_cold_ptr(h, i), nc))]
-                    for i in range(SEEDS)]
+            return [[zlib.crc32(ctypes.string_at(lib.cc4o_state_ptr(h, i), nh)), cold_crc(i)] for i in range(SEEDS)]
         rec = {}
         for i in range(SEEDS):
             lib.cc4o_reset(h, i, SEED0 + i, mode, steps, 0, policy)
