@@ -132,6 +132,42 @@ int cc4_debug_shadow_handle(cc4_handle* h, cc4_handle** out) {
   *out = h->shadow;
   return 0;
 }
+// the self-check's digest of one episode on the host (csrc/cc4_digest.h: the definition k_digest runs, its 64 lanes in a loop); needs no device and no handle
+int cc4_debug_digest_rows(const void* hot_row, const void* cold_row, size_t cold_bytes, const int32_t* obs, float reward, uint8_t done, uint32_t err,
+                          const int32_t* actions, uint64_t out[3]) {
+  if (!hot_row || !cold_row || !obs || !actions || !out || cold_bytes % 16) return -2;
+  uint32_t reward_bits;
+  __builtin_memcpy(&reward_bits, &reward, 4);
+  out[0] = digest_row_word(hot_row, sizeof(EnvState) / 16);
+  out[1] = digest_row_word(cold_row, cold_bytes / 16);
+  out[2] = digest_out_word(obs, actions, reward_bits, done, err);
+  return 0;
+}
+// test hook, read-only: k_digest over this handle's episodes as they stand (what a checked call computes of either side)
+int cc4_debug_digest(cc4_handle* h, uint64_t* out /* [N][3] */) {
+  if (!h || !out) return -2;
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  std::vector<uint64_t> d;
+  if (verify_digest(h, d)) return -1;
+  memcpy(out, d.data(), d.size() * sizeof(uint64_t));
+  return 0;
+}
+// test hook: arm (part -1: disarm) the one planted difference of the next checked call (cc4_api_run.hip plant_apply: a byte of the shadow's side, data only)
+int cc4_debug_verify_plant(cc4_handle* h, int32_t part, int32_t env, int64_t offset, int32_t step) {
+  if (!h) return -2;
+  h->plant.part = -1;
+  if (part == -1) return 0;
+  const char* who = "cc4_debug_verify_plant";
+  if (h->is_shadow || h->comm) { h->err = std::string(who) + ": not on a shadow handle or a handle with a communicator (its calls are never checked)"; return -2; }
+  if (!h->verify && h->verify_every <= 0) { h->err = std::string(who) + ": no call of this handle is ever checked (CC4_PERSIST_VERIFY unset, CC4_PERSIST_VERIFY_EVERY=0)"; return -2; }
+  static const int64_t span[10] = {(int64_t)sizeof(EnvState), 0 /* the cold row */, OBS_TOTAL, 1, 1, 1, NBLUE, 1, 1, OBS_PACKED};
+  const bool traj = part >= 7 && part <= 9;
+  if (part < 0 || part > 9 || env < 0 || env >= h->cfg.num_envs || offset < 0 || offset >= (part == 1 ? (int64_t)h->cold_row : span[part]) || step < 0 || (!traj && step != 0)) {
+    h->err = std::string(who) + ": part 0..9 (-1 disarms), env 0..N-1, offset inside the part (0 where it has none), step >= 0 (0 unless part 7..9)"; return -2;
+  }
+  h->plant.part = part; h->plant.env = env; h->plant.offset = offset; h->plant.step = step;
+  return 0;
+}
 // test hook, read-only: the builds launch_range and run_one_launch pick on this handle (the one-wave step kernel or the four-wave one, the four-wave
 // kernel's register budget, the multi-step build) -- cc4_step_kernel has one name for k_step_philox<., 1 / 7 / 8>
 int cc4_debug_step_build(cc4_handle* h, int32_t out[3]) {

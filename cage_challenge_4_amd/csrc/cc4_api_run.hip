@@ -212,7 +212,7 @@ static int run_random_steps_impl(cc4_handle* h, uint64_t seed0, uint32_t t0, int
 // CC4_PERSIST_VERIFY=1 (a self-check mode, not a fast one): a call that takes a one-launch form -- the persistent kernels, whose hand-over
 // between the steps of an episode leans on how a CU's L1 behaves, and the plain multi-step kernels -- is run a second time
 // from the same starting rows with per-step launches on a shadow handle, and the two outcomes are compared episode by episode.
-static int verify_digest(cc4_handle* h, std::vector<uint64_t>& out) {
+int verify_digest(cc4_handle* h, std::vector<uint64_t>& out) {
   const int n = h->cfg.num_envs;
   if (!h->d_digest) HIPCHK(h, hipMalloc(&h->d_digest, 3 * (size_t)n * sizeof(uint64_t)));
   if (join_groups(h)) return -1;
@@ -256,9 +256,46 @@ static int shadow_compare(cc4_handle* h, std::string& what) {
   h->verify_calls++;
   what.clear();
   for (size_t e = 0; e < (size_t)h->cfg.num_envs && what.empty(); ++e) {
-    const bool hot = a[3 * e] != b[3 * e], cold = a[3 * e + 1] != b[3 * e + 1], outp = a[3 * e + 2] != b[3 * e + 2];
-    if (hot || cold || outp) what = "first episode " + std::to_string(e) + " (" + (hot ? "hot row " : "") + (cold ? "cold row " : "") + (outp ? "outputs" : "") + ")";
+    const int d = digest_differs(a.data(), b.data(), e);
+    const bool hot = d & 1, cold = d & 2, outp = d & 4;
+    if (d) what = "first episode " + std::to_string(e) + " (" + (hot ? "hot row " : "") + (cold ? "cold row " : "") + (outp ? "outputs" : "") + ")";
   }
+  return 0;
+}
+// The planted difference of cc4_debug_verify_plant (include/cc4_debug.h), a test hook: data only -- one byte of the SHADOW's side XORed with 1 behind both
+// sides' runs and in front of the digests and the trajectory compare, in memory that nothing steps before the next checked call re-seeds the shadow.
+// plant_refuse: the armed plant does not fit the checked call it met (a trajectory part on a call that records no such row): nothing runs, nothing stays armed
+static int plant_refuse(cc4_handle* h, const char* who) {
+  h->plant.part = -1;
+  h->err = std::string(who) + ": the difference armed with cc4_debug_verify_plant names a trajectory row this call does not record (disarmed; nothing was stepped)";
+  return -2;
+}
+// s_rew / s_done / s_packed: the shadow's recorded trajectory of a plan call (NULL: not recorded, or no plan call)
+static int plant_apply(cc4_handle* h, float* s_rew, uint8_t* s_done, uint8_t* s_packed) {
+  const cc4_handle::VerifyPlant p = h->plant;
+  if (p.part < 0) return 0;
+  h->plant.part = -1;
+  cc4_handle* sh = h->shadow;
+  const size_t n = (size_t)h->cfg.num_envs, e = (size_t)p.env, off = (size_t)p.offset, row = (size_t)p.step * n + e;
+  uint8_t* at = nullptr;
+  switch (p.part) {
+    case 0: at = reinterpret_cast<uint8_t*>(sh->d_state + e) + off; break;
+    case 1: at = reinterpret_cast<uint8_t*>(cold_at(sh->d_cold, e, sh->cold_row)) + off; break;
+    case 2: at = reinterpret_cast<uint8_t*>(sh->d_obs + e * OBS_TOTAL + off); break;
+    case 3: at = reinterpret_cast<uint8_t*>(sh->d_reward + e); break;
+    case 4: at = sh->d_done + e; break;
+    case 5: at = reinterpret_cast<uint8_t*>(sh->d_err + e); break;
+    case 6: at = reinterpret_cast<uint8_t*>(sh->d_actions + e * NBLUE + off); break;
+    case 7: at = reinterpret_cast<uint8_t*>(s_rew + row); break;
+    case 8: at = s_done + row; break;
+    default: at = s_packed + row * OBS_PACKED + off; break;
+  }
+  if (join_groups(sh)) { h->err = "CC4_PERSIST_VERIFY: " + sh->err; return -1; }
+  HIPCHK(h, hipStreamSynchronize(sh->stream));
+  uint8_t byte = 0;
+  HIPCHK(h, hipMemcpy(&byte, at, 1, hipMemcpyDefault));
+  byte ^= 1;
+  HIPCHK(h, hipMemcpy(at, &byte, 1, hipMemcpyDefault));
   return 0;
 }
 // a checked call disagreed with its shadow: counted, said on stderr, the call's return value
@@ -282,12 +319,14 @@ int cc4_run_random_steps(cc4_handle* h, uint64_t seed0, uint32_t t0, int32_t k, 
   if (!check) return run_random_steps_impl(h, seed0, t0, k, ms_step_kernels);
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   if (strncmp(cc4_run_kernel_for(h, k), "k_run_", 6) != 0) return run_random_steps_impl(h, seed0, t0, k, ms_step_kernels);
+  if (h->plant.part >= 7) return plant_refuse(h, "cc4_run_random_steps");
   if (shadow_seed(h)) return -1;
   cc4_handle* sh = h->shadow;
   int rc = run_random_steps_impl(h, seed0, t0, k, ms_step_kernels);
   if (rc) return rc;
   rc = run_random_steps_impl(sh, seed0, t0, k, nullptr);
   if (rc) { h->err = "CC4_PERSIST_VERIFY: the shadow run failed: " + sh->err; return rc; }
+  if (plant_apply(h, nullptr, nullptr, nullptr)) return -1;
   std::string bad;
   if (shadow_compare(h, bad)) return -1;
   if (!bad.empty()) return verify_mismatch(h, std::string(cc4_run_kernel_for(h, k)) + " and the per-step launches disagree after " + std::to_string(k) + " steps: " + bad);
@@ -596,6 +635,8 @@ int cc4_run_plan_device(cc4_handle* h, int32_t k, const int32_t* d_actions, cons
   bool check = h->verify;
   if (!check && h->verify_every > 0 && ++h->persist_calls % (uint64_t)h->verify_every == 0) check = true;
   if (!check) return run_plan_impl(h, k, d_actions, d_messages, d_rewards, d_dones, d_obs_packed, true);
+  if (h->plant.part >= 7 && (h->plant.step >= k || !(h->plant.part == 7 ? (const void*)d_rewards : h->plant.part == 8 ? (const void*)d_dones : (const void*)d_obs_packed)))
+    return plant_refuse(h, who);
   if (shadow_seed(h)) return -1;
   cc4_handle* sh = h->shadow;
   const size_t n = (size_t)h->cfg.num_envs;
@@ -608,6 +649,7 @@ int cc4_run_plan_device(cc4_handle* h, int32_t k, const int32_t* d_actions, cons
   if (rc) { release(); return rc; }
   rc = run_plan_impl(sh, k, d_actions, d_messages, s_rew, s_done, s_packed, false);
   if (rc) { release(); h->err = "CC4_PERSIST_VERIFY: the shadow run failed: " + sh->err; return rc; }
+  if (plant_apply(h, s_rew, s_done, s_packed)) { release(); return -1; }
   std::string bad;
   if (shadow_compare(h, bad)) { release(); return -1; }
   // the trajectory, a step's row at a time (both streams are drained: shadow_compare waited for them) -- whether or not the final digests differ: the

@@ -21,6 +21,7 @@
 #include "cc4_args.h"
 #include "cc4_kernel_decls.h"
 #include "cc4_export.h"
+#include "cc4_digest.h"
 #define CC4_HOST __attribute__((visibility("hidden")))
 
 struct cc4_handle {
@@ -152,6 +153,8 @@ struct cc4_handle {
   uint64_t* d_digest = nullptr;   // [num_envs] per-episode digest
   uint32_t* d_plan_err = nullptr; // [num_envs] cc4_run_plan_device: the error flags the steps of the call in flight raised (zero between calls)
   long long verify_calls = 0, verify_mismatches = 0;
+  // test hook (cc4_debug_verify_plant): ONE difference planted in the shadow's side of the next checked call, between its runs and its compare (part -1: none armed)
+  struct VerifyPlant { int32_t part = -1, env = 0, step = 0; int64_t offset = 0; } plant;
   int persist_min_k = 10;         // shorter calls keep the per-step launches: a launch's ramp and tail cost a few steps' worth (with the tail's items shared
                                   // among the CUs of an XCD: K = 10: 733 vs 685 M, K = 20: 813 vs 742 M, K = 32: 857 vs 756 M; CC4_PERSIST_MIN_K)
   struct EnqPool* pool = nullptr; // one enqueue thread per group stream beyond the first (cc4_run_random_steps; enq_*)
@@ -229,6 +232,7 @@ CC4_HOST void enq_pool_stop(cc4_handle* h);
 CC4_HOST int persist_setup(cc4_handle* h);
 CC4_HOST int persist_launch(cc4_handle* h, StepArgs a, int k, uint32_t t0, const XchgArgs& x, hipEvent_t e0, hipEvent_t e1, bool rollout, const PlanArgs* pl = nullptr);
 CC4_HOST int ensure_shadow(cc4_handle* h);
+CC4_HOST int verify_digest(cc4_handle* h, std::vector<uint64_t>& out);
 // cc4_api_comm.hip: the exchange around a one-launch kernel
 CC4_HOST int xchg_begin(cc4_handle* h, int k, XchgArgs* x);
 CC4_HOST int xchg_enqueue(cc4_handle* h, int k, const XchgArgs& x, int form);

@@ -1,6 +1,7 @@
 // cc4_k_misc.hip -- k_reset and the small kernels of libcc4.so (exchange gate, CU discovery, stand-in policies, seeds, digest, event-log helpers).
 #include "cc4_persist.h"      // (cu_slot: k_discover)
 #include "cc4_kernel_decls.h"
+#include "cc4_digest.h"       // (k_digest)
 
 // The gate of a chunk of steps [k_lo, k_hi] on the communication stream: returns when every group has counted all its episodes in every
 // step of the chunk (counts of one episode's consecutive steps may arrive out of order: each wave counts where ITS stores have drained),
@@ -271,22 +272,13 @@ __global__ __launch_bounds__(WAVE) void k_pack_obs_rows(uint8_t* packed, const i
 // reward / done / error word, the drawn actions -- in three words (hot, cold, outputs), so that a mismatch says where
 __global__ __launch_bounds__(WAVE) void k_digest(const EnvState* st, const EnvCold* cold, size_t cold_row, const int32_t* obs, const float* reward,
                                                  const uint8_t* done, const uint32_t* err, const int32_t* actions, uint64_t* out, int n) {
+  static_assert(DIGEST_LANES == WAVE && DIGEST_OBS == OBS_TOTAL && DIGEST_ACTIONS == NBLUE && sizeof(EnvState) % 16 == 0, "cc4_digest.h states the digest for these shapes");
   const int e = blockIdx.x, lane = threadIdx.x;
   if (e >= n) return;
-  auto mix = [](uint64_t h, uint64_t v) { h ^= v + 0x9E3779B97F4A7C15ull + (h << 6) + (h >> 2); return h * 0xD6E8FEB86659FD93ull; };
-  auto hash_vecs = [&](const uint4* p, size_t nv) {
-    uint64_t h = 0x1234567ull + (uint64_t)lane;
-    for (size_t i = lane; i < nv; i += WAVE) { const uint4 v = p[i]; h = mix(h, ((uint64_t)v.x << 32) | v.y); h = mix(h, ((uint64_t)v.z << 32) | v.w); }
-    for (int off = 32; off >= 1; off >>= 1) h += __shfl_xor(h, off);     // order-independent across lanes, position-dependent within one
-    return h;
-  };
-  const uint64_t h_hot = hash_vecs(reinterpret_cast<const uint4*>(st + e), sizeof(EnvState) / 16);
-  const uint64_t h_cold = hash_vecs(reinterpret_cast<const uint4*>(cold_at(const_cast<EnvCold*>(cold), (size_t)e, cold_row)), cold_row / 16);
-  uint64_t h = 0x89ABCDEFull + (uint64_t)lane;
-  for (int i = lane; i < OBS_TOTAL; i += WAVE) h = mix(h, (uint64_t)(uint32_t)obs[(size_t)e * OBS_TOTAL + i]);
-  if (lane < NBLUE) h = mix(h, (uint64_t)(uint32_t)actions[e * NBLUE + lane]);
-  if (lane == 8) { h = mix(h, (uint64_t)__float_as_uint(reward[e])); h = mix(h, ((uint64_t)done[e] << 32) | err[e]); }
-  for (int off = 32; off >= 1; off >>= 1) h += __shfl_xor(h, off);
+  // the definition: cc4_digest.h (a lane's chains there, the cross-lane sums here)
+  const uint64_t h_hot = digest_wave_sum(digest_row_lane(st + e, sizeof(EnvState) / 16, lane));
+  const uint64_t h_cold = digest_wave_sum(digest_row_lane(cold_at(cold, (size_t)e, cold_row), cold_row / 16, lane));
+  const uint64_t h = digest_wave_sum(digest_out_lane(obs + (size_t)e * OBS_TOTAL, actions + (size_t)e * NBLUE, __float_as_uint(reward[e]), done[e], err[e], lane));
   if (lane == 0) { out[3 * (size_t)e] = h_hot; out[3 * (size_t)e + 1] = h_cold; out[3 * (size_t)e + 2] = h; }
 }
 

@@ -344,6 +344,17 @@ class CC4VecEnv:
         self._chk(self.lib.cc4_verify_stats(self._h, out), 'cc4_verify_stats')
         return int(out[0]), int(out[1])
 
+    def debug_digest(self):
+        """cc4_debug_digest: the self-check's digest of every episode as it stands, [N, 3] uint64 (hot row, cold row, outputs: include/cc4_debug.h)."""
+        out = np.zeros((self.num_envs, 3), np.uint64)
+        self._chk(self.lib.cc4_debug_digest(self._h, out.ctypes.data_as(ctypes.c_void_p)), 'cc4_debug_digest')
+        return out
+
+    def debug_verify_plant(self, part, env=0, offset=0, step=0):
+        """cc4_debug_verify_plant: arm one planted difference in the shadow's side of the next checked call (part -1 disarms); returns the hook's
+        code (0, or -2: refused, nothing armed) instead of raising."""
+        return int(self.lib.cc4_debug_verify_plant(self._h, int(part), int(env), int(offset), int(step)))
+
     def gather_log(self, steps):
         """cc4_debug_gather_log: keep the gathered rows of the next `steps` in-kernel-exchanged steps (0: free the log)."""
         self._chk(self.lib.cc4_debug_gather_log(self._h, int(steps)), 'cc4_debug_gather_log')

@@ -46,6 +46,48 @@ int cc4_debug_step_build(cc4_handle* h, int32_t out[3]);
  * headline kernel k_run_philox1 takes the long-call pattern (csrc/cc4_sched.h run_config_for_call). */
 int cc4_debug_last_run_split(cc4_handle* h, int32_t out[5]);
 
+/* ---- The self-check's digest (CC4_PERSIST_VERIFY / CC4_PERSIST_VERIFY_EVERY, include/cc4.h cc4_verify_stats): what a checked call compares.
+ *
+ * Both sides of a checked call -- the handle after its one-launch kernel, the shadow handle after its per-step launches -- are reduced to THREE
+ * unsigned 64-bit words per episode: word 0 of the hot row, word 1 of the cold row, word 2 of the outputs.  A side's words are [N][3].  Episode e
+ * disagrees where word i of the one side differs from word i of the other: i = 0 is reported as "hot row", 1 as "cold row", 2 as "outputs".
+ * All arithmetic is modulo 2^64.
+ *
+ *   mix(h, v) = (h XOR (v + 0x9E3779B97F4A7C15 + (h << 6) + (h >> 2))) * 0xD6E8FEB86659FD93      (the shifts of h as it came in, logical)
+ *
+ *   A ROW WORD.  The row is nv = bytes / 16 vectors of 16 bytes (hot row: cc4_state_bytes(); cold row: cc4_cold_bytes(h); both multiples of 16).
+ *   Vector i is four little-endian 32-bit words x, y, z, w at its bytes 0, 4, 8, 12.  There are 64 lanes.  Lane L starts from
+ *   h = 0x1234567 + L and takes the vectors i = L, L + 64, L + 128, ... < nv in ascending order; for each, h = mix(h, x * 2^32 + y) and then
+ *   h = mix(h, z * 2^32 + w).  Behind its last vector every lane -- one that had no vector too -- closes with h = mix(h, L).  The row word is the sum of
+ *   the 64 lanes' h.
+ *
+ *   THE OUTPUTS WORD.  Lane L starts from h = 0x89ABCDEF + L and takes the episode's 578 observation values (int32, as cc4_get_obs gives them) of
+ *   index i = L, L + 64, ... < 578 in ascending order: h = mix(h, value as an unsigned 32-bit number).  Then lanes 0..4 take one more value each:
+ *   lane b the action index of blue agent b in the handle's action buffer (cc4_get_actions, int32 as unsigned 32 bits).  Then lane 8 takes two more:
+ *   the reward's float32 bit pattern as an unsigned 32-bit number, then done * 2^32 + err (done: the byte of cc4_fetch, err: the episode's error
+ *   word).  Then every lane closes with h = mix(h, L).  The outputs word is the sum of the 64 lanes' h.
+ *   (The closing round: without it the last value of a lane moved the sum by an amount that did not depend on the lane, and equal changes in two lanes'
+ *   last values gave equal words, opposite ones cancelled.)
+ *
+ * cc4_debug_digest_rows: the three words on the host from one episode's rows and outputs (csrc/cc4_digest.h, the code k_digest runs, lanes in a
+ *   loop); needs no device and no handle.  -2: a NULL argument, cold_bytes no multiple of 16.
+ * cc4_debug_digest: the kernel over this handle's episodes as they stand ([N][3]); changes nothing a step reads. */
+int cc4_debug_digest_rows(const void* hot_row, const void* cold_row, size_t cold_bytes, const int32_t* obs /* [578] */,
+                          float reward, uint8_t done, uint32_t err, const int32_t* actions /* [5] */, uint64_t out[3]);
+int cc4_debug_digest(cc4_handle* h, uint64_t* out /* [N][3] */);
+/* test hook: arms ONE planted difference for the next CHECKED call of this handle (unchecked calls leave it armed; part -1 disarms; arming replaces
+ * what was armed, a refused call of this hook leaves nothing armed).  After both sides have run and before they are digested / their trajectory rows
+ * compared, one byte of the SHADOW's side is XORed with 1:
+ * part 0 hot row byte `offset` of episode `env`; 1 cold row byte `offset`; 2 the low byte of observation value `offset` (0..577); 3 the reward's low
+ * byte; 4 done; 5 the error word's low byte; 6 the low byte of drawn action `offset` (0..4); 7 / 8 / 9 (plan calls only) the shadow's recorded reward
+ * (low byte) / done / packed-row byte `offset` (0..147) of plan step `step`.  offset is 0 for parts 3, 4, 5, 7, 8, step is 0 for parts 0..6.
+ * The byte lies in memory that only the digest and the host's compare read before the next checked call re-seeds the shadow from this handle: it is
+ * never stepped, never written to this handle, and no kernel takes another path for it.  The checked call then returns -5 as for any disagreement.
+ * -2 from this hook: out of range, a shadow handle, a handle with a communicator, a handle none of whose calls is ever checked (CC4_PERSIST_VERIFY
+ * unset and CC4_PERSIST_VERIFY_EVERY=0).  A checked call that meets an armed part 7 / 8 / 9 it cannot apply -- cc4_run_random_steps, a plan call of
+ * `step` steps or fewer, a plan call that does not record that row -- steps nothing, disarms it and returns -2. */
+int cc4_debug_verify_plant(cc4_handle* h, int32_t part, int32_t env, int64_t offset, int32_t step);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,6 +26,9 @@ def test_every_declared_symbol_is_exported():
         assert hasattr(lib, s), f'{s} declared under include/ but not exported by libcc4.so'
     assert set(syms) == set(_lib.SIGNATURES), 'python binding and header disagree on the ABI'
     assert not [s for s in header_symbols(('cc4.h',)) if s.startswith('cc4_debug_')], 'debug hooks belong in include/cc4_debug.h'
+    # the self-check's own test surface: the digest's host twin, the kernel over a handle, the planted difference
+    assert {'cc4_debug_digest_rows', 'cc4_debug_digest', 'cc4_debug_verify_plant'} <= set(header_symbols(('cc4_debug.h',)))
+    assert [len(_lib.SIGNATURES[s][1]) for s in ('cc4_debug_digest_rows', 'cc4_debug_digest', 'cc4_debug_verify_plant')] == [9, 2, 5]
 
 
 def test_constants_agree_with_header():

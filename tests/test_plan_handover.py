@@ -179,6 +179,38 @@ def run_neighbour_cell(cell, traj, reps, monkeypatch):
             B.close()
 
 
+def test_a_real_mismatch_message_is_arbitrated_like_the_canned_one(monkeypatch):
+    """tests/test_plan_handover_cpu.py feeds self_check_verdict a canned message; here the library writes it.  `selfcheck_all` once, with one byte of the
+    SHADOW's recorded packed row of step 69, episode 6 changed between the runs and the compare (cc4_debug_verify_plant, include/cc4_debug.h: data only,
+    never stepped) -- the canned message's trajectory clause.  The call returns -5 with that clause, and the verdict, which sees both sides equal to the
+    oracle in everything fetched, places the difference in the shadow's recorded rows."""
+    cell = H.CELLS['selfcheck_all']
+    traj = H.oracle_trajectory(cell)
+    for k in ('CC4_PERSIST_VERIFY_EVERY', 'CC4_PERSIST_THR', 'CC4_PERSIST_RUNS', 'CC4_PERSIST', 'CC4_PERSIST_MIN_K'):
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setenv(cell.beside.env, cell.beside.value)
+    from cage_challenge_4_amd import CC4VecEnv
+    env = CC4VecEnv(cell.n, steps=cell.steps, rng_mode=cell.rng_mode, autoreset=True, strict=False)
+    try:
+        env.reset(seeds=H.RESET_SEED)
+        assert _prefix_calls(cell, traj, env, 0, 1, 'k_run_philox1p') is None
+        c, act, msg = traj.inputs[-1]
+        assert env.plan_kernel_for(c.k) == H.kernel_name(cell) and (c.k, c.record) == (70, True)
+        assert env.lib.cc4_debug_verify_plant(env._h, 9, 6, 3, 69) == 0
+        res = H.run_plan_raw(env, act, msg, record_obs=True)
+        said = ('CC4_PERSIST_VERIFY: k_run_philox1p and the per-step launches disagree after a plan of 70 steps: first differing trajectory row: packed '
+                'observations of step 69, 1 episode(s) differ in it, first episode 6')
+        assert (res.rc, res.error) == (H.VERIFY_MISMATCH, said)
+        main = H.Side(res.obs_packed, res.rewards, res.dones, H.fetch_final(env.lib, env._h, traj, True))
+        shadow = H.Side(final=H.fetch_final(env.lib, H.shadow_handle(env), traj, True))
+        verdict = H.self_check_verdict(cell, traj, res.rc, res.error, main, shadow)
+        assert verdict.startswith('SHADOW LEFT THE TRAJECTORY') and 'KERNEL' not in verdict and f'"{said}"' in verdict, verdict
+        assert 'the difference lies in its recorded trajectory rows alone' in verdict, verdict
+        assert env.verify_stats() == (len(cell.prefix) + 1, 1)
+    finally:
+        env.close()
+
+
 @pytest.mark.parametrize('cid', list(H.CELLS))
 def test_cell_matches_the_oracle_every_time(cid, monkeypatch):
     import cage_challenge_4_amd.vec_env as V
