@@ -22,6 +22,7 @@ FEAT_HOSTS, FEAT_PER_HOST, FEAT_GLOBAL = 137, 16, 32     # CC4_FEAT_*: the state
 RED_ACT_WORDS, RED_SID_AUTO = 4, -1                       # CC4_RED_*: red actions from the device (cc4_step_red_device) ...
 RED_VIEW_HOSTS, RED_VIEW_PER_HOST, RED_VIEW_SCALARS = 137, 8, 16     # ... and the red agents' view tensors (red_view.py)
 BLUE_VIEW_HOSTS, BLUE_VIEW_PER_HOST, BLUE_VIEW_SCALARS = 137, 8, 16  # CC4_BLUE_VIEW_*: blue's own knowledge as tensors (blue_view.py)
+BLUE_EDGES_MAX, BLUE_EDGES_COLUMNS, BLUE_EDGES_WORDS = 160, 8, 8       # CC4_BLUE_EDGES_*: the Monitor's connections as edge lists (blue_edges.py)
 REWARD_SUBNETS, REWARD_COLS, REWARD_WORDS = 9, 4, 16                # CC4_REWARD_*: the pieces of the step reward as tensors (reward_terms.py)
 POLICY_KEEP, POLICY_DEFAULT = -1, -2                    # CC4_POLICY_*: per-episode opponent classes (cc4_set_policies)
 OBS_LEN = (92, 92, 92, 92, 210)
@@ -95,6 +96,8 @@ SIGNATURES = {
     'cc4_red_record_from_row': (ctypes.c_int, [_P, ctypes.c_int32, _P, _P]),
     'cc4_blue_view_device': (ctypes.c_int, [_P, _P, ctypes.c_int32, _P, ctypes.c_int32, _P, _P]),
     'cc4_blue_view_from_row': (ctypes.c_int, [_P, _P, ctypes.c_int32, _P, _P]),
+    'cc4_blue_edges_device': (ctypes.c_int, [_P, _P, ctypes.c_int32, _P, ctypes.c_int32, ctypes.c_int32, _P, _P]),
+    'cc4_blue_edges_from_row': (ctypes.c_int, [_P, _P, ctypes.c_int32, ctypes.c_int32, _P, _P]),
     'cc4_enable_reward_terms': (ctypes.c_int, [_P, ctypes.c_int32]),
     'cc4_reward_terms_enabled': (ctypes.c_int, [_P]),
     'cc4_reward_terms_device': (ctypes.c_int, [_P, _P, ctypes.c_int32, _P, ctypes.c_int32, _P, _P]),

@@ -6,6 +6,7 @@
 #include "cc4_features.h"
 #include "cc4_red_view.h"
 #include "cc4_blue_view.h"
+#include "cc4_blue_edges.h"
 #include "cc4_reward_terms.h"
 
 static thread_local std::string g_create_err;
@@ -784,6 +785,50 @@ int cc4_blue_view_from_row(const void* hot_row, const void* cold_row, int32_t st
       blue_view_from_row(s, lg, sus, steps, hosts, scalars);
     }
     free(lg); free(sus);
+  }
+  free(s);
+  return rc;
+}
+// ---- the Monitor's connections as edge lists (include/cc4.h; cc4_k_edges.hip; the definition: cc4_blue_edges.h).  One launch on the main stream behind
+// the group streams, no host synchronisation; it only reads rows: of the hot rows exists and step_count, of the cold rows the event log.
+int cc4_blue_edges_device(cc4_handle* h, const void* d_bank, int32_t capacity, const int32_t* d_ids, int32_t n, int32_t max_edges, int32_t* d_edges,
+                          int32_t* d_counts) {
+  const char* who = "cc4_blue_edges_device";
+  if (h->rollout_k > 0) { h->err = std::string(who) + ": a rollout is in flight on this handle: cc4_rollout_end first"; return -2; }
+  if (n < 0) { h->err = std::string(who) + ": n < 0"; return -2; }
+  if (max_edges < 1 || max_edges > BE_MAX) { h->err = std::string(who) + ": max_edges must be 1 .. " + std::to_string((int)BE_MAX); return -2; }
+  if (n == 0) return 0;
+  if (!d_edges || reinterpret_cast<uintptr_t>(d_edges) % 16 || reinterpret_cast<uintptr_t>(d_counts) % 4) {
+    h->err = std::string(who) + ": the edge buffer is required and must be 16-byte aligned (the counts: 4-byte aligned or NULL)"; return -2;
+  }
+  if (d_bank && capacity < 1) { h->err = std::string(who) + ": a bank needs a capacity of at least one slot"; return -2; }
+  if (reinterpret_cast<uintptr_t>(d_bank) % 64) { h->err = std::string(who) + ": a bank must be 64-byte aligned"; return -2; }
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  if (join_groups(h)) return -1;
+  BlueEdgesArgs a{h->d_state, h->d_cold, h->cold_row, static_cast<const uint8_t*>(d_bank), slot_bytes(h->cold_row), d_ids, n,
+                  d_bank ? capacity : h->cfg.num_envs, h->cfg.steps, h->cfg.rng_mode, max_edges, d_edges, d_counts, h->d_copy_fault};
+  hipLaunchKernelGGL(k_blue_edges, dim3(n), dim3(WAVE), 0, h->stream, a);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+// The same on the host, from one hot row and (optionally) its cold row: no device, no handle.  Only the event log of the cold row is read; it is
+// copied, like the hot row, because the caller's bytes may sit at any address.
+int cc4_blue_edges_from_row(const void* hot_row, const void* cold_row, int32_t steps, int32_t max_edges, int32_t* edges, int32_t* counts) {
+  if (!hot_row || !edges || max_edges < 1 || max_edges > BE_MAX) return -2;
+  EnvState* s = row_copy(hot_row);
+  if (!s) return -1;
+  if (steps <= 0) steps = s->steps;
+  if (steps <= 0 || steps > (1 << 20)) { free(s); return -2; }
+  int rc = 0;
+  if (!cold_row) blue_edges_from_row(s, nullptr, max_edges, edges, counts);
+  else {
+    EvLog* lg = static_cast<EvLog*>(aligned_alloc(alignof(EvLog), sizeof(EvLog)));
+    if (!lg) rc = -1;
+    else {
+      memcpy(lg, static_cast<const char*>(cold_row) + offsetof(EnvCold, evlog), sizeof(EvLog));
+      blue_edges_from_row(s, lg, max_edges, edges, counts);
+    }
+    free(lg);
   }
   free(s);
   return rc;

@@ -1,5 +1,5 @@
 // cc4_args.h -- what the host side and the kernels of libcc4.so share: the constants, the argument blocks of the kernels (StepArgs, XchgArgs, RunArgs,
-// PlanArgs, ResetArgs, CopyArgs, FeatArgs, RedSubmitArgs, RedViewArgs, BlueViewArgs, RewardArgs), the snapshot-slot layout, and the register budgets of the kernels.  No device helper (cc4_kernels.h) and nothing of
+// PlanArgs, ResetArgs, CopyArgs, FeatArgs, RedSubmitArgs, RedViewArgs, BlueViewArgs, BlueEdgesArgs, RewardArgs), the snapshot-slot layout, and the register budgets of the kernels.  No device helper (cc4_kernels.h) and nothing of
 // the C++ host library (cc4_host.h).  The index arithmetic of the persistent schedule -- partitions, tickets, runs, the progress word -- is in cc4_sched.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -229,6 +229,18 @@ struct BlueViewArgs {
   int count, cap, steps, rng_mode;
   uint8_t* hosts;                                        // [count][NBLUE][137][8], 8-byte aligned
   int32_t* scal;                                         // [count][NBLUE][16] or null
+  uint32_t* fault;
+};
+
+// ---- the Monitor's connections as edge lists (cc4_k_edges.hip; the definition: cc4_blue_edges.h).  cc4_blue_edges_device: the rows of entry i as for
+// BlueViewArgs
+struct BlueEdgesArgs {
+  const EnvState* st; const EnvCold* cold; size_t cold_row;
+  const uint8_t* bank; size_t slot;
+  const int32_t* ids;
+  int count, cap, steps, rng_mode, max_edges;
+  int32_t* edges;                                        // [count][max_edges][8], 16-byte aligned
+  int32_t* counts;                                       // [count][8] or null
   uint32_t* fault;
 };
 

@@ -222,12 +222,14 @@ CC4_HD int eph_port(Ctx x, int h, int salt = 0) {
   // Counter mode: the port value is unobservable on the flat-observation path, so nothing is drawn.  With the event log on
   // (dict observations) it is taken from a sibling of the acting agent's stream -- block (current draw position, salt) of stream
   // id | 0x8000 -- which consumes nothing of the agent's own stream: logging never changes a trajectory.  `salt` tells apart
-  // the ports one action draws between two draws of its stream.  (No per-host uniqueness re-draw: agents resolved on different
-  // lanes would race for it; a collision among 10848 ports is as unobservable as it is rare.)
+  // the ports one action draws between two draws of its stream.  The position is counted in WORDS handed out (blocks computed x 4 - words
+  // still waiting), not in blocks computed: a stream whose block 0 was preloaded (rng_preload: the lane-parallel kernels) has a block
+  // computed before its first draw, one that was not has none, and the two must name the same port.  (No per-host uniqueness re-draw:
+  // agents resolved on different lanes would race for it; a collision among 10848 ports is as unobservable as it is rare.)
   if (x.r->mode != 0) {
     if (!x.lg) return 49152;
     uint32_t c[4];
-    rng_block(x.r, x.r->ndraw | 0x8000u, (uint32_t)(x.r->s_hi * 64u + (uint32_t)salt), c);
+    rng_block(x.r, x.r->ndraw | 0x8000u, (uint32_t)(((uint32_t)x.r->s_hi * 4u - x.r->has64) * 64u + (uint32_t)salt), c);
     return 49152 + (int)(((uint64_t)c[0] * (60000u - 49152u)) >> 32);
   }
   uint32_t p = rng_below(x.r, EPH_RANGE);

@@ -58,6 +58,8 @@ __global__ void k_red_submit(RedSubmitArgs a);
 __global__ void k_red_view(RedViewArgs a);
 // blue's own knowledge (cc4_k_blue.hip): one wavefront per requested episode or bank slot
 __global__ void k_blue_view(BlueViewArgs a);
+// the Monitor's connections as edge lists (cc4_k_edges.hip): one wavefront per requested episode or bank slot
+__global__ void k_blue_edges(BlueEdgesArgs a);
 // reward terms (cc4_k_reward.hip): one wavefront per requested episode or bank slot
 __global__ void k_reward_terms(RewardArgs a);
 // per-episode opponent classes (cc4_k_misc.hip): one lane per episode

@@ -16,6 +16,7 @@
 //   cc4_k_feat.hip     the true state as tensors: k_state_features (cc4_state_features_device; needs none of the helpers here, only cc4_features.h)
 //   cc4_k_red.hip      the red agents as learners: k_red_submit (cc4_step_red_device), k_red_view (cc4_red_view_device); only cc4_red_view.h
 //   cc4_k_blue.hip     blue's own knowledge as tensors: k_blue_view (cc4_blue_view_device); only cc4_blue_view.h
+//   cc4_k_edges.hip    the Monitor's connections as edge lists: k_blue_edges (cc4_blue_edges_device); only cc4_blue_edges.h
 //   cc4_k_reward.hip   the pieces of the step reward as tensors: k_reward_terms (cc4_reward_terms_device); only cc4_reward_terms.h
 // cc4_kernel_decls.h declares them for the host side.  No MFMA anywhere: the path is integer / indexing.
 #pragma once

@@ -61,6 +61,9 @@ class CC4TorchVecEnv:
                                                   what Analyse found, the deployed decoy, suspicious pids; with enable_event_log() the Monitor's
                                                   entries per host (counts, ports, remote hosts)
     enable_event_log(on=True)                     the per-step event log (full builds of the step kernel, one launch per step)
+    blue_edges(ids=None, bank=None, out=None, max_edges=160) -> (edges [n, max_edges, 8] int32, counts [n, 8] int32)   the Monitor's connection
+                                                  entries as a sorted, merged edge list: who talked to whom on which ports (needs the event log;
+                                                  cage_challenge_4_amd.blue_edges, to_edge_index for a graph layer)
 
     Reward terms (include/cc4.h cc4_reward_terms_device; cage_challenge_4_amd.reward_terms):
     enable_reward_terms(on=True)                  record the pieces of every step's reward (full builds of the step kernel, one launch per step)
@@ -379,6 +382,45 @@ class CC4TorchVecEnv:
                 self.venv._chk(rc, 'cc4_blue_view_device')
             self.venv._chk(lib.cc4_stream_signal(h, sp), 'cc4_stream_signal')
         return hosts, scal
+
+    def blue_edges(self, ids=None, bank=None, out=None, max_edges=L.BLUE_EDGES_MAX):
+        """The Monitor's connection entries of the step just taken as edge lists (cc4_blue_edges_device, include/cc4.h; columns and words:
+        blue_edges.COLUMNS / WORDS) as tensors on the env's device: (edges [n, max_edges, 8] int32, counts [n, 8] int32) -- agent, reporting
+        host, local host, remote host, the two ports, how often, the slot within the agent's segment; sorted, merged, -1 past the last edge
+        (edges[..., 0] >= 0 is the mask; counts[:, 5] > max_edges shows a truncated list).  blue_edges.to_edge_index() makes the [2, M] node
+        pairs of a graph layer from it.  The per-step log must be on (enable_event_log(): the env then runs the full builds of its step kernel,
+        one launch per step, and leaves the one-launch forms of run / plan calls); without it every row is -1 and counts[:, 6] is 0.
+        ids, bank, out and the ordering on the current stream as state_features(); no host copy, no host wait.  A faulty entry gives -1 rows
+        and zero counts, and check_errors() raises CC4EngineError for it."""
+        max_edges = int(max_edges)
+        if not 1 <= max_edges <= L.BLUE_EDGES_MAX:
+            raise ValueError(f'max_edges must be 1 .. {L.BLUE_EDGES_MAX}, got {max_edges}')
+        with torch.cuda.device(self.device):
+            s = torch.cuda.current_stream(self.device)
+            vp = ctypes.c_void_p
+            bp, cap = self._bank(bank) if bank is not None else (None, 0)
+            if ids is not None:
+                ids = self._index(ids, 'ids')
+                n, ip = int(ids.numel()), vp(ids.data_ptr())
+            else:
+                n, ip = (cap if bank is not None else self.num_envs), None
+            shapes = ((n, max_edges, L.BLUE_EDGES_COLUMNS), (n, L.BLUE_EDGES_WORDS))
+            if out is None:
+                edges = torch.empty(shapes[0], dtype=torch.int32, device=self.device)
+                counts = torch.empty(shapes[1], dtype=torch.int32, device=self.device)
+            else:
+                edges, counts = out
+                for x, shp in ((edges, shapes[0]), (counts, shapes[1])):
+                    if not torch.is_tensor(x) or tuple(x.shape) != shp or x.dtype != torch.int32 or x.device != self.device or not x.is_contiguous():
+                        raise ValueError(f'out must be contiguous int32 tensors ({list(shapes[0])}, {list(shapes[1])}) on {self.device}')
+                if edges.data_ptr() % 16:
+                    raise ValueError('out: the edges tensor must be 16-byte aligned')
+            lib, h, sp = self.lib, self._h, vp(s.cuda_stream)
+            rc = lib.cc4_stream_wait(h, sp) or lib.cc4_blue_edges_device(h, bp, cap, ip, n, max_edges, vp(edges.data_ptr()), vp(counts.data_ptr()))
+            if rc:
+                self.venv._chk(rc, 'cc4_blue_edges_device')
+            self.venv._chk(lib.cc4_stream_signal(h, sp), 'cc4_stream_signal')
+        return edges, counts
 
     def enable_event_log(self, on=True):
         """CC4VecEnv.enable_event_log (cc4_enable_event_log): record the HostEvents entries of every step, which fills the event columns of

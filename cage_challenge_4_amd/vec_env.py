@@ -573,6 +573,56 @@ class CC4VecEnv:
             raise_on_copy_faults(faults.value)
         return hosts, scal
 
+    def blue_edges_device(self, d_edges, d_counts=None, n=None, d_ids=None, d_bank=None, capacity=0, max_edges=L.BLUE_EDGES_MAX):
+        """cc4_blue_edges_device into device memory of the caller's (device addresses): edges [n, max_edges, 8] int32, 16-byte aligned, counts
+        [n, 8] int32 or None, of episodes d_ids (int32 [n] on the device; None: 0 .. n-1) of the env or of the slots of a snapshot bank.
+        Enqueued, no host wait."""
+        vp = ctypes.c_void_p
+        as_p = lambda x: x if x is None or isinstance(x, vp) else vp(int(x))      # noqa: E731
+        rc = self.lib.cc4_blue_edges_device(self._h, as_p(d_bank), int(capacity), as_p(d_ids), self.num_envs if n is None else int(n),
+                                            int(max_edges), as_p(d_edges), as_p(d_counts))
+        if rc:
+            self._chk(rc, 'cc4_blue_edges_device')
+
+    def blue_edges(self, ids=None, max_edges=L.BLUE_EDGES_MAX):
+        """The Monitor's connection entries of the step just taken as edge lists (cc4_blue_edges_device, include/cc4.h; columns and words:
+        blue_edges.COLUMNS / WORDS): (edges [n, max_edges, 8] int32, counts [n, 8] int32) of episodes ids (None: all), as NumPy arrays.  Rows past
+        an episode's edges are -1; counts[:, 5] > max_edges shows a truncated list.  Synchronises, like the other getters.
+        The per-step log must be on (enable_event_log()) -- an env with the log on runs the full builds of its step kernel, one launch per step,
+        and leaves the one-launch forms of run / plan calls; without it every row is -1 and counts[:, 6] is 0.  An index out of range gives
+        -1 rows and zero counts and raises CC4EngineError after the call."""
+        max_edges = int(max_edges)
+        if not 1 <= max_edges <= L.BLUE_EDGES_MAX:
+            raise ValueError(f'max_edges must be 1 .. {L.BLUE_EDGES_MAX}, got {max_edges}')
+        ids = None if ids is None else np.ascontiguousarray(ids, dtype=np.int32).ravel()
+        n = self.num_envs if ids is None else int(ids.size)
+        edges = np.full((n, max_edges, L.BLUE_EDGES_COLUMNS), -1, np.int32)
+        counts = np.zeros((n, L.BLUE_EDGES_WORDS), np.int32)
+        if n == 0:
+            return edges, counts
+        hip, vp = _hip(), ctypes.c_void_p
+        b_ids = ((4 * n + 15) & ~15) if ids is not None else 0          # [ids | edges | counts]: every part 16-byte aligned
+        _hip_chk(hip.hipSetDevice(self._dev), 'hipSetDevice')
+        d = vp()
+        _hip_chk(hip.hipMalloc(ctypes.byref(d), b_ids + edges.nbytes + counts.nbytes), 'hipMalloc')
+        try:
+            if ids is not None:
+                _hip_chk(hip.hipMemcpy(d, ids.ctypes.data_as(vp), ids.nbytes, 1), 'hipMemcpy')
+            d_edges, d_counts = vp(d.value + b_ids), vp(d.value + b_ids + edges.nbytes)
+            rc = self.lib.cc4_blue_edges_device(self._h, None, 0, d if ids is not None else None, n, max_edges, d_edges, d_counts)
+            rc2 = self.lib.cc4_synchronize(self._h)
+            if rc or rc2:
+                self._chk(rc or rc2, 'cc4_blue_edges_device')
+            _hip_chk(hip.hipMemcpy(edges.ctypes.data_as(vp), d_edges, edges.nbytes, 2), 'hipMemcpy')
+            _hip_chk(hip.hipMemcpy(counts.ctypes.data_as(vp), d_counts, counts.nbytes, 2), 'hipMemcpy')
+        finally:
+            hip.hipFree(d)
+        if ids is not None and ((ids < 0) | (ids >= self.num_envs)).any():
+            faults = ctypes.c_uint32(0)
+            self._chk(self.lib.cc4_copy_faults(self._h, ctypes.byref(faults)), 'cc4_copy_faults')
+            raise_on_copy_faults(faults.value)
+        return edges, counts
+
     def enable_reward_terms(self, on=True):
         """cc4_enable_reward_terms: record the pieces of every step's reward (reward_terms()).  The env then runs the full builds of its step
         kernel, one launch per step, and leaves the one-launch forms of run / plan calls and rollouts, as with submitted red / green actions;

@@ -1,0 +1,300 @@
+"""GPU: the Monitor's connection entries as edge lists from the device.  cc4_blue_edges_device (k_blue_edges) against the list derived from the
+REFERENCE's dict observation (tests/blue_edges_util.py) on the 120 recorded steps of blueobs_seed123_random.json; against the host statement of
+the same definition (blue_edges.from_row) byte for byte on a batch with the event log on, against the NumPy restatement from the true-state
+document, and against the host statement on the rows of the CPU oracle stepped alongside -- the oracle appends its log serially, the device by
+atomics, so that is the order-independence of the list in vivo; id lists, snapshot banks, no counts, faults, refusals, the log off; and logs
+planted into the cold rows at every length the kernel treats differently (its rounds of 64 entries), which real episodes do not reach."""
+import ctypes
+import json
+import os
+
+import numpy as np
+import pytest
+
+import blue_edges_util as EU
+import capacity_util
+import golden_util
+from cage_challenge_4_amd import blue_edges as BE
+from oracle_binding import OracleVecEnv, random_actions
+from test_state_features import DevMem, _dev, _faults
+
+pytestmark = pytest.mark.gpu
+
+VP = ctypes.c_void_p
+CF_RANGE, CF_SLOT_EMPTY = 1, 8
+EVREC = np.dtype([('host', 'u1'), ('kind', 'u1'), ('laddr', 'u1'), ('raddr', 'u1'), ('lport', '<u2'), ('rport', '<u2'), ('pid', '<u2'), ('rep', 'u1'),
+                  ('order', 'u1')])
+assert EVREC.itemsize == 12
+
+
+def _edges(dev, n, E=160, ids=None, bank=None, cap=0, fill=0, counts=True):
+    """cc4_blue_edges_device into a fresh device buffer [edges | counts], then synchronise and copy down."""
+    buf = DevMem(n * (E * 32 + 32), fill)
+    assert buf.hip.hipDeviceSynchronize() == 0          # the fill runs on the null stream, the kernel on the handle's: the fill first
+    d_ids = None
+    if ids is not None:
+        d_ids = DevMem(4 * max(len(ids), 1))
+        d_ids.up(np.asarray(ids, np.int32))
+    dev.blue_edges_device(buf.p, buf.at(n * E * 32) if counts else None, n=n, d_ids=d_ids.p if d_ids else None,
+                          d_bank=bank.p if bank is not None else None, capacity=cap, max_edges=E)
+    dev.synchronize()
+    edges, cnt = buf.down(np.int32, (n, E, 8)), buf.down(np.int32, (n, 8), n * E * 32)
+    if d_ids:
+        d_ids.free()
+    buf.free()
+    return edges, cnt
+
+
+def _from_rows(env, episodes, steps, E=160):
+    ec = [BE.from_row(env.get_state(e), env.get_cold(e), steps, E) for e in episodes]
+    return np.stack([e for e, _ in ec]), np.stack([c for _, c in ec])
+
+
+def test_device_edges_match_the_reference_dict_observation():
+    """(a) One episode on the numpy stream, the reference's own trajectory: the kernel's list at each of the 120 recorded steps against the list
+    derived from the reference's dict observation of that step."""
+    gold = json.load(open(os.path.join(golden_util.GOLDEN_DIR, 'blueobs_seed123_random.json')))
+    fix = golden_util.load(os.path.join(golden_util.GOLDEN_DIR, gold['fixture']))
+    dev = _dev(1, steps=fix['steps'])
+    dev.reset(seeds=fix['seed'])
+    dev.reset(seeds=None)
+    dev.enable_event_log(True)
+    stats = EU.new_stats()
+    for t, want in enumerate(gold['steps']):
+        dev.step(fix['actions'][t][None, :])
+        edges, counts = dev.blue_edges()
+        assert edges.shape == (1, 160, 8) and edges.dtype == np.int32 and counts.shape == (1, 8) and counts.dtype == np.int32
+        assert counts[0, 6] == 1 and counts[0, 7] == t + 1, t
+        EU.compare(edges[0], counts[0], want, json.loads(dev.true_state_json(0)), t, stats)
+    assert stats['entries'] >= 600 and stats['merged'] >= 10 and stats['third_party'] >= 10 and stats['remote_outside'] >= 200, stats
+    dev.close()
+
+
+def test_device_edges_equal_the_host_function_the_document_and_the_oracle_with_ids_banks_faults_and_the_log_off(oracle_lib):
+    n, steps, seed, T = 64, 60, 4700, 40
+    dev = _dev(n, steps=steps, rng_mode=1, strict=False)
+    dev.reset(seeds=seed)
+    dev.enable_event_log(True)
+    ora = OracleVecEnv(n, steps=steps, rng_mode=1)
+    ora.reset(seeds=seed)
+    ora.enable_event_log(True)
+    lib, h = dev.lib, dev._h
+    everyone = range(n)
+    seen = EU.new_stats()
+    all_e = all_c = None
+    for t in range(T):
+        a = random_actions(seed, t, n)
+        dev.step(a)
+        ora.step(a)
+        if t % 5 == 4:
+            edges, counts = dev.blue_edges()
+            all_e, all_c = _from_rows(dev, everyone, steps)
+            bad = np.argwhere(edges != all_e)
+            assert bad.size == 0, (t, [tuple(map(int, b)) + (int(edges[tuple(b)]), int(all_e[tuple(b)])) for b in bad[:8]])
+            assert np.array_equal(counts, all_c), (t, np.argwhere(counts != all_c)[:8].tolist())
+            assert (counts[:, 6] == 1).all() and (counts[:, 7] == t + 1).all(), t
+            for e in everyone:
+                d_e, d_c = BE.from_true_state(dev.true_state_json(e))
+                assert np.array_equal(d_e, edges[e]) and np.array_equal(d_c, counts[e]), (t, e)
+            ora_e, ora_c = _from_rows(ora, everyone, steps)                     # the same multiset, appended in the serial walk's order
+            assert np.array_equal(edges, ora_e) and np.array_equal(counts, ora_c), (t, np.argwhere(counts != ora_c)[:8].tolist())
+            e32, c32 = dev.blue_edges(max_edges=7)
+            assert np.array_equal(e32, edges[:, :7]) and np.array_equal(c32, counts), t
+            EU.edge_stats(edges, seen)
+    ora.close()
+    assert seen['entries'] > 100 and seen['merged'] > 0 and seen['remote_outside'] > 0, seen
+
+    # (c) shuffled and repeated id lists of 3, 1 and 5
+    rng = np.random.default_rng(5)
+    for ids in (rng.permutation(n)[:3], rng.permutation(n)[:1], np.array([63, 0, 63, 31, 31], np.int64)):
+        ids = ids.astype(np.int32)
+        edges, counts = _edges(dev, len(ids), ids=ids, fill=0x77)
+        assert np.array_equal(edges, all_e[ids]) and np.array_equal(counts, all_c[ids]), ids.tolist()
+        edges, counts = dev.blue_edges(ids, max_edges=33)
+        assert np.array_equal(edges, all_e[ids][:, :33]) and np.array_equal(counts, all_c[ids]), ids.tolist()
+    # no counts wanted: the counts' place stays as it was
+    edges, counts = _edges(dev, 3, ids=[7, 8, 9], fill=0x5A, counts=False)
+    assert np.array_equal(edges, all_e[7:10]) and (counts.view(np.uint8) == 0x5A).all()
+
+    # episodes into a bank: the list from the bank equals the live one; the env steps on and the slots still show the list at the save
+    slot, cap = int(lib.cc4_snapshot_bytes(h)), 12
+    bank = DevMem(cap * slot)
+    src = np.array([3, 17, 40, 41, 63, 0, 9, 22], np.int32)
+    dst = rng.permutation(8).astype(np.int32)
+    idx = DevMem(4 * 32)
+    idx.up(src); idx.up(dst, 64)
+    assert lib.cc4_copy_episodes_device(h, len(src), None, 0, idx.p, bank.p, cap, idx.at(64), None) == 0, lib.cc4_last_error(h)
+    edges, counts = _edges(dev, len(dst), ids=dst, bank=bank, cap=cap)
+    assert np.array_equal(edges, all_e[src]) and np.array_equal(counts, all_c[src])
+    assert (all_c[src][:, 5] > 0).any()                                             # the log travelled with the copy
+    for t in range(T, T + 3):
+        dev.step(random_actions(seed, t, n))
+    now_e, now_c = dev.blue_edges()
+    assert (now_c[:, 7] == T + 3).all() and not np.array_equal(now_e[src], all_e[src])
+    edges, counts = _edges(dev, len(dst), ids=dst, bank=bank, cap=cap, E=9)
+    assert np.array_equal(edges, all_e[src][:, :9]) and np.array_equal(counts, all_c[src])
+    inv = np.argsort(dst)
+    edges, counts = _edges(dev, len(dst), bank=bank, cap=cap, counts=False)         # no id list: slots 0 .. 7
+    assert np.array_equal(edges, all_e[src[inv]])
+    assert _faults(dev) == 0
+
+    # an id of -1, an id of N, a slot never written: -1 rows and zero counts, the other entries right, the fault in cc4_copy_faults, once
+    by_slot = {int(d): int(s) for s, d in zip(src, dst)}
+    for bad_id, bit in ((10, CF_SLOT_EMPTY), (cap, CF_RANGE), (-1, CF_RANGE)):
+        edges, counts = _edges(dev, 3, ids=[2, bad_id, 5], bank=bank, cap=cap, fill=0x77, E=20)
+        assert (edges[1] == -1).all() and not counts[1].any(), bad_id
+        assert np.array_equal(edges[0], all_e[by_slot[2]][:20]) and np.array_equal(edges[2], all_e[by_slot[5]][:20]) and np.array_equal(counts[2], all_c[by_slot[5]])
+        assert _faults(dev) == bit, (bad_id, bit)
+    edges, counts = _edges(dev, 4, ids=[n, 1, -1, 46], fill=0x77)
+    assert (edges[0] == -1).all() and (edges[2] == -1).all() and not counts[0].any() and not counts[2].any()
+    assert np.array_equal(edges[1], now_e[1]) and np.array_equal(edges[3], now_e[46]) and np.array_equal(counts[3], now_c[46])
+    assert _faults(dev) == CF_RANGE and _faults(dev) == 0
+    with pytest.raises(Exception, match='INDEX_OUT_OF_RANGE'):
+        dev.blue_edges([0, n])
+
+    # refusals: -2, nothing enqueued, the output untouched; n = 0 a no-op
+    out = DevMem(2 * (160 * 32 + 32), 0xC3)
+    d_cnt = out.at(2 * 160 * 32)
+    assert lib.cc4_blue_edges_device(h, None, 0, None, -1, 160, out.p, d_cnt) == -2
+    assert lib.cc4_blue_edges_device(h, None, 0, None, 2, 160, None, d_cnt) == -2
+    assert lib.cc4_blue_edges_device(h, None, 0, None, 2, 0, out.p, d_cnt) == -2 and b'max_edges' in lib.cc4_last_error(h)
+    assert lib.cc4_blue_edges_device(h, None, 0, None, 2, 161, out.p, d_cnt) == -2 and b'max_edges' in lib.cc4_last_error(h)
+    assert lib.cc4_blue_edges_device(h, None, 0, None, 2, -5, out.p, d_cnt) == -2
+    assert lib.cc4_blue_edges_device(h, None, 0, None, 2, 160, out.at(8), d_cnt) == -2 and b'aligned' in lib.cc4_last_error(h)
+    assert lib.cc4_blue_edges_device(h, bank.p, 0, None, 2, 160, out.p, d_cnt) == -2 and b'capacity' in lib.cc4_last_error(h)
+    assert lib.cc4_blue_edges_device(h, bank.p, -3, None, 2, 160, out.p, d_cnt) == -2
+    assert lib.cc4_blue_edges_device(h, None, 0, None, 0, 160, out.p, d_cnt) == 0
+    dev.synchronize()
+    assert (out.down(np.uint8, out.nbytes) == 0xC3).all() and _faults(dev) == 0
+    assert dev.blue_edges(np.zeros(0, np.int32))[0].shape == (0, 160, 8)
+    with pytest.raises(ValueError, match='max_edges'):
+        dev.blue_edges(max_edges=161)
+    assert lib.cc4_blue_edges_device(h, None, 0, None, 1, 5, out.at(16), d_cnt) == 0          # 16-byte alignment is what the kernel needs
+    dev.synchronize()
+    assert np.array_equal(out.down(np.int32, (1, 5, 8), 16), now_e[:1, :5]) and (out.down(np.uint8, 16) == 0xC3).all()
+    assert (out.down(np.uint8, 32, 16 + 5 * 32) == 0xC3).all()
+
+    # the same handle with the log off: every row -1, events_valid 0, step_count right
+    dev.enable_event_log(False)
+    for t in range(T + 3, T + 6):
+        dev.step(random_actions(seed, t, n))
+    edges, counts = dev.blue_edges()
+    off_e, off_c = _from_rows(dev, everyone, steps)
+    assert np.array_equal(edges, off_e) and np.array_equal(counts, off_c)
+    assert (edges == -1).all() and not counts[:, :7].any() and (counts[:, 7] == T + 6).all()
+    for m in (bank, idx, out):
+        m.free()
+    dev.close()
+
+
+def _planted(rng, zone_hosts, n, dup):
+    missing = [h for h in range(137) if EU.ZONE_OF_SUBNET[h // 17] >= 0 and h not in zone_hosts]
+    """n log entries over existing zone hosts: connection entries drawn from a small pool of (host, local, ports, remote) so that keys repeat
+    (dup: one in `dup` entries copies an earlier one's key under another order byte and pid), with entries that do not qualify mixed in."""
+    rec = np.zeros(n, EVREC)
+    for i in range(n):
+        h = int(rng.choice(zone_hosts))
+        kind = 0
+        r = int(rng.integers(20))
+        rec[i] = (h, 0, h if rng.integers(3) else int(rng.integers(137)), int(rng.choice([1, 18, 70, 136, 86, 120])), int(rng.choice([22, 80, 443, 0])),
+                  int(50000 + rng.integers(4)), int(rng.integers(3000)), int(rng.choice([1, 1, 1, 10, 255])), int(rng.integers(206)))
+        if r == 0:
+            rec[i]['kind'] = kind + 1 + int(rng.integers(2))          # a process / decoy entry
+        elif r == 1:
+            rec[i]['raddr'] = int(rng.choice([255, 137]))             # no remote address
+        elif r == 2:
+            rec[i]['host'] = int(rng.choice([70, 136, 137, 255]))     # no zone / past the table
+        elif r == 3:
+            rec[i]['rep'] = 0
+        elif r == 4:
+            rec[i]['laddr'] = int(rng.choice([137, 255]))             # qualifies: column 2 is -1
+        elif r == 5 and missing:
+            rec[i]['host'] = int(rng.choice(missing))                 # a host of a zone's subnet that this episode's topology lacks
+        if i and dup and rng.integers(dup) == 0:
+            j = int(rng.integers(i))
+            keep = (rec[i]['pid'], rec[i]['order'])
+            rec[i] = rec[j]
+            rec[i]['pid'], rec[i]['order'] = keep
+    return rec
+
+
+def _dictionary(rec, n_valid, exists, E, step):
+    """The definition restated over planted records with a dictionary (blue_edges_util.edges_of_multiset does the sort)."""
+    ms = {}
+    if n_valid:
+        for e in rec:
+            host, raddr = int(e['host']), int(e['raddr'])
+            if e['kind'] != 0 or e['rep'] == 0 or host >= 137 or host not in exists or raddr >= 137 or EU.ZONE_OF_SUBNET[host // 17] < 0:
+                continue
+            k = (EU.ZONE_OF_SUBNET[host // 17], host, raddr, int(e['laddr']), int(e['lport']), int(e['rport']))
+            ms[k] = ms.get(k, 0) + int(e['rep'])
+    return EU.edges_of_multiset(ms, E, int(n_valid), step)
+
+
+def test_planted_logs_at_every_length_and_in_every_order(oracle_lib):
+    """(d) Logs written into the cold rows: 0, 1, 63, 64, 65, 128, 160 entries and 161 (truncated: not valid), then one multiset in three
+    physical orders."""
+    n, steps = 8, 60
+    lens = (0, 1, 63, 64, 65, 128, 160, 161)
+    dev = _dev(n, steps=steps, rng_mode=1, strict=False)
+    dev.reset(seeds=991)
+    dev.enable_event_log(True)
+    dev.step(random_actions(991, 0, n))
+    off = capacity_util.layout()['cold.evlog']
+    rng = np.random.default_rng(17)
+    docs = [json.loads(dev.true_state_json(e)) for e in range(n)]
+
+    def plant(e, rec, count):
+        cold = dev.get_cold(e)
+        hdr = cold[off:off + 16].view(np.uint32)
+        assert hdr[2] == 1 and hdr[1] == docs[e]['step'] - 1 == 0, hdr.tolist()
+        hdr[0] = count
+        body = np.zeros(160, EVREC)
+        body[:min(len(rec), 160)] = rec[:160]
+        cold[off + 16:off + 16 + 160 * 12] = body.view(np.uint8)
+        dev._chk(dev.lib.cc4_set_cold(dev._h, int(e), cold.ctypes.data_as(VP)), 'cc4_set_cold')
+
+    recs, exists = [], []
+    for e, ln in enumerate(lens):
+        exists.append({hd['h'] for hd in docs[e]['hosts']})
+        zone_hosts = sorted(h for h in exists[e] if EU.ZONE_OF_SUBNET[h // 17] >= 0)
+        recs.append(_planted(rng, zone_hosts, ln, 4))
+        plant(e, recs[e], ln)
+    totals = None
+    for E in (160, 7, 1):
+        edges, counts = _edges(dev, n, E=E, fill=0x77)
+        host_e, host_c = _from_rows(dev, range(n), steps, E)
+        assert np.array_equal(edges, host_e) and np.array_equal(counts, host_c), (E, np.argwhere(counts != host_c)[:8].tolist())
+        for e, ln in enumerate(lens):
+            want_e, want_c = _dictionary(recs[e], ln <= 160, exists[e], E, 1)
+            assert np.array_equal(counts[e], want_c), (E, ln, counts[e].tolist(), want_c.tolist())
+            bad = np.argwhere((edges[e] != want_e).any(axis=1))
+            assert bad.size == 0, (E, ln, [(int(i), edges[e, i].tolist(), want_e[i].tolist()) for i in bad[:6, 0]])
+            total = int(counts[e, 5])
+            assert (edges[e, min(total, E):] == -1).all() and (edges[e, :min(total, E), 0] >= 0).all() and counts[e, :5].sum() == total, (E, ln)
+            live = edges[e, :min(total, E)]
+            first = np.r_[True, live[1:, 0] != live[:-1, 0]] if len(live) else np.zeros(0, bool)
+            assert (live[first, 7] == 0).all() and (live[~first, 7] == live[np.nonzero(~first)[0] - 1, 7] + 1).all(), (E, ln)      # slot restarts per agent
+        if E == 160:
+            totals = counts[:, 5].copy()
+    assert totals[0] == 0 and totals[7] == 0 and counts[7, 6] == 0 and counts[6, 6] == 1, totals.tolist()
+    assert totals[6] > 64 and totals[4] < 65 and (totals[2:7] > 0).all(), totals.tolist()      # more than a round of distinct keys; merged keys
+    full = _edges(dev, n, E=160)[0]
+    assert len(set(full[6, :totals[6], 0].tolist())) >= 3, 'the long list spans several agents'
+    # total - 1 and total: the last edge is dropped / kept, the counts stay
+    for E in (int(totals[6]) - 1, int(totals[6])):
+        edges, counts = _edges(dev, n, E=E, fill=0x77)
+        assert np.array_equal(edges[6], full[6, :E]) and counts[6, 5] == totals[6] and (edges[6, :, 0] >= 0).all(), E
+    # one multiset in three physical orders: identical output
+    # (in the same episode: which hosts exist is the episode's own)
+    ref = {E: _edges(dev, n, E=E) for E in (160, 7)}
+    for perm in (rng.permutation(160), np.arange(160)[::-1]):
+        plant(6, recs[6][perm], 160)
+        for E in (160, 7):
+            edges, counts = _edges(dev, n, E=E, fill=0x11)
+            differ = sorted({int(e) for e in np.argwhere(edges != ref[E][0])[:, 0]} | {int(e) for e in np.argwhere(counts != ref[E][1])[:, 0]})
+            assert not differ, (E, differ, edges[differ[0], :3].tolist(), ref[E][0][differ[0], :3].tolist(), counts[differ[0]].tolist())
+            host_e, host_c = _from_rows(dev, range(n), steps, E)
+            assert np.array_equal(edges, host_e) and np.array_equal(counts, host_c), E
+    assert _faults(dev) == 0
+    dev.close()
