@@ -18,16 +18,14 @@ Three ways to the same numbers:
   from_true_state(doc, max_edges)         a NumPy restatement from the true-state document only: independent of the packed rows
 and to_edge_index(edges) turns a batch of lists into the [2, M] node-id pairs a PyG-style layer takes."""
 import ctypes
-import json
 import numpy as np
 from . import _lib as L
+from ._view_util import MAX_EVENTS, ZONE_OF_SUBNET, _bytes, _doc, events_valid  # noqa: F401  (MAX_EVENTS: part of this module's surface)
 
 NUM_BLUE, MAX_EDGES, EDGE_COLUMNS, EDGE_WORDS = L.NUM_BLUE, L.BLUE_EDGES_MAX, L.BLUE_EDGES_COLUMNS, L.BLUE_EDGES_WORDS
 HOSTS = 137
 COLUMNS = {'agent': 0, 'host': 1, 'local': 2, 'remote': 3, 'local_port': 4, 'remote_port': 5, 'count': 6, 'slot': 7}
 WORDS = {'edges_0': 0, 'edges_1': 1, 'edges_2': 2, 'edges_3': 3, 'edges_4': 4, 'total': 5, 'events_valid': 6, 'step_count': 7}
-MAX_EVENTS = 160                         # entries the per-step log holds (a larger total: truncated, not valid)
-_ZONE_OF_SUBNET = (0, 1, 2, 3, -1, 4, 4, 4, -1)
 
 
 def _check_max(max_edges):
@@ -43,11 +41,9 @@ def from_row(hot, cold, steps=0, max_edges=MAX_EDGES):
     env the rows come from; 0: the length the hot row itself records."""
     lib = L.load()
     max_edges = _check_max(max_edges)
-    hot = np.ascontiguousarray(np.frombuffer(hot, np.uint8) if isinstance(hot, (bytes, bytearray, memoryview)) else hot, dtype=np.uint8).ravel()
-    if hot.size != lib.cc4_state_bytes():
-        raise ValueError(f'a hot row has {lib.cc4_state_bytes()} bytes, got {hot.size}')
+    hot = _bytes(hot, lib.cc4_state_bytes(), 'a hot row')
     if cold is not None:
-        cold = np.ascontiguousarray(np.frombuffer(cold, np.uint8) if isinstance(cold, (bytes, bytearray, memoryview)) else cold, dtype=np.uint8).ravel()
+        cold = _bytes(cold, None, 'a cold row')
     edges = np.zeros((max_edges, EDGE_COLUMNS), np.int32)
     counts = np.zeros(EDGE_WORDS, np.int32)
     vp = ctypes.c_void_p
@@ -58,12 +54,6 @@ def from_row(hot, cold, steps=0, max_edges=MAX_EDGES):
     return edges, counts
 
 
-def _doc(doc):
-    if isinstance(doc, (str, bytes)):
-        return json.loads(doc)
-    return doc if isinstance(doc, dict) else doc.raw
-
-
 def from_true_state(doc, max_edges=MAX_EDGES):
     """The same arrays from a true-state document (the JSON text of cc4_get_true_state, its parsed form, or true_state.TrueState): from
     "events" / "events_step" / "events_total", "step" and the ids of "hosts" only, with a dictionary and a Python sort."""
@@ -71,7 +61,7 @@ def from_true_state(doc, max_edges=MAX_EDGES):
     max_edges = _check_max(max_edges)
     edges = np.full((max_edges, EDGE_COLUMNS), -1, np.int32)
     counts = np.zeros(EDGE_WORDS, np.int32)
-    valid = 'events' in d and d['step'] >= 1 and d['events_step'] + 1 == d['step'] and d['events_total'] <= MAX_EVENTS
+    valid = events_valid(d)
     counts[6], counts[7] = int(valid), d['step']
     if not valid:
         return edges, counts
@@ -80,7 +70,7 @@ def from_true_state(doc, max_edges=MAX_EDGES):
     for _order, _seq, host, kind, laddr, lport, raddr, rport, _pid, rep in d['events']:
         if kind != 0 or rep <= 0 or host >= HOSTS or host not in exists or raddr >= HOSTS:
             continue
-        b = _ZONE_OF_SUBNET[host // 17]
+        b = ZONE_OF_SUBNET[host // 17]
         if b < 0:
             continue
         key = (b, host, raddr, laddr, lport, rport)

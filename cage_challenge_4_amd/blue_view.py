@@ -16,9 +16,9 @@ Three ways to the same numbers:
   from_true_state(doc)                a NumPy restatement from the true-state document only: independent of the packed rows.  The document does not
                                       carry the queued action, so words 1..3 of the scalars (DOC_UNDEFINED_WORDS) stay zero."""
 import ctypes
-import json
 import numpy as np
 from . import _lib as L
+from ._view_util import MAX_EVENTS, ZONE_OF_SUBNET, _bytes, _doc, events_valid  # noqa: F401  (MAX_EVENTS, events_valid: part of this module's surface)
 
 NUM_BLUE, VIEW_HOSTS, VIEW_PER_HOST, VIEW_SCALARS = L.NUM_BLUE, L.BLUE_VIEW_HOSTS, L.BLUE_VIEW_PER_HOST, L.BLUE_VIEW_SCALARS
 
@@ -32,17 +32,6 @@ PORT_BITS = {22: 1, 80: 2, 3390: 4, 25: 8, 1: 16, 443: 32}
 PORT_PID, OWN_DECOY = 0x40, 0x80         # CC4_BLUE_VIEW_PORT_PID, CC4_BLUE_VIEW_OWN_DECOY
 T_TRUE, T_UNKNOWN, T_FALSE, T_IN_PROGRESS = 1, 2, 3, 4
 SLEEP, MONITOR, ANALYSE, REMOVE, RESTORE, DECOY, BLOCK, ALLOW = range(8)
-MAX_EVENTS = 160                         # entries the per-step log holds (a larger total: truncated, not valid)
-_ZONE_OF_SUBNET = (0, 1, 2, 3, -1, 4, 4, 4, -1)
-
-
-def _bytes(x, size, what):
-    if isinstance(x, (bytes, bytearray, memoryview)):
-        x = np.frombuffer(x, np.uint8)
-    x = np.ascontiguousarray(x, dtype=np.uint8).ravel()
-    if size is not None and x.size != size:
-        raise ValueError(f'{what} has {size} bytes, got {x.size}')
-    return x
 
 
 def from_row(hot, cold=None, steps=0):
@@ -64,18 +53,6 @@ def from_row(hot, cold=None, steps=0):
     return hosts, scal
 
 
-def _doc(doc):
-    if isinstance(doc, (str, bytes)):
-        return json.loads(doc)
-    return doc if isinstance(doc, dict) else doc.raw
-
-
-def events_valid(doc):
-    """The document's event log describes the step just taken and is complete."""
-    d = _doc(doc)
-    return 'events' in d and d['step'] >= 1 and d['events_step'] + 1 == d['step'] and d['events_total'] <= MAX_EVENTS
-
-
 def from_true_state(doc):
     """The same arrays from a true-state document (the JSON text of cc4_get_true_state, its parsed form, or true_state.TrueState): from the
     "blue" entries (busy / traffic_ok / sus / parent), "last_blue", the hosts' "ev" / "files", "events" / "events_step" / "events_total", "phase"
@@ -84,7 +61,7 @@ def from_true_state(doc):
     hosts = np.zeros((NUM_BLUE, VIEW_HOSTS, VIEW_PER_HOST), np.uint8)
     scal = np.zeros((NUM_BLUE, VIEW_SCALARS), np.int32)
     info = {hd['h']: hd for hd in d['hosts']}
-    zone = {h: _ZONE_OF_SUBNET[h // 17] for h in info}
+    zone = {h: ZONE_OF_SUBNET[h // 17] for h in info}
     count = np.zeros((NUM_BLUE, VIEW_HOSTS, 4), np.int64)            # sus, conn, proc, remote
     for h, hd in info.items():
         if zone[h] >= 0:

@@ -1,13 +1,9 @@
 // cc4_api.hip -- the host side of libcc4.so, its core: create / destroy, the episode groups and their streams, the launches of one step (launch_step),
-// reset, the step entry points and the getters, episode copies, state features, state get / set, the event log and the replay.  The handle itself: cc4_host.h; k steps
-// per call: cc4_api_run.hip; rollouts: cc4_api_rollout.hip; the communicator and the exchange: cc4_api_comm.hip; debug hooks: cc4_api_debug.hip.
+// reset, the step entry points and the getters, episode copies, state get / set, the event log and the replay.  The handle itself: cc4_host.h; k steps
+// per call: cc4_api_run.hip; rollouts: cc4_api_rollout.hip; the communicator and the exchange: cc4_api_comm.hip; the derived views: cc4_api_views.hip;
+// debug hooks: cc4_api_debug.hip.
 #include "cc4_host.h"
 #include "cc4_export.h"
-#include "cc4_features.h"
-#include "cc4_red_view.h"
-#include "cc4_blue_view.h"
-#include "cc4_blue_edges.h"
-#include "cc4_reward_terms.h"
 
 static thread_local std::string g_create_err;
 
@@ -711,194 +707,6 @@ int cc4_step_red_device(cc4_handle* h, const int32_t* d_actions, const uint8_t* 
   h->ext_seen = true; h->ext_submitted = true; h->ext_dirty = true; h->ext_green_dirty = false;
   return launch_step(h, d_actions, d_messages, false, 0, 0, true, true);
 }
-// What each red agent knows as tensors: one launch on the main stream behind the group streams, no host synchronisation; it only reads rows.
-int cc4_red_view_device(cc4_handle* h, const void* d_bank, int32_t capacity, const int32_t* d_ids, int32_t n, uint8_t* d_hosts, int32_t* d_scalars) {
-  const char* who = "cc4_red_view_device";
-  if (h->rollout_k > 0) { h->err = std::string(who) + ": a rollout is in flight on this handle: cc4_rollout_end first"; return -2; }
-  if (n < 0) { h->err = std::string(who) + ": n < 0"; return -2; }
-  if (n == 0) return 0;
-  if (!d_hosts || reinterpret_cast<uintptr_t>(d_hosts) % 16 || reinterpret_cast<uintptr_t>(d_scalars) % 4) {
-    h->err = std::string(who) + ": the host-view buffer is required and must be 16-byte aligned (the agent words: 4-byte aligned or NULL)"; return -2;
-  }
-  if (d_bank && capacity < 1) { h->err = std::string(who) + ": a bank needs a capacity of at least one slot"; return -2; }
-  if (reinterpret_cast<uintptr_t>(d_bank) % 64) { h->err = std::string(who) + ": a bank must be 64-byte aligned"; return -2; }
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  if (join_groups(h)) return -1;
-  RedViewArgs a{h->d_state, static_cast<const uint8_t*>(d_bank), slot_bytes(h->cold_row), d_ids, n, d_bank ? capacity : h->cfg.num_envs,
-                h->cfg.steps, h->cfg.rng_mode, d_hosts, d_scalars, h->d_copy_fault};
-  hipLaunchKernelGGL(k_red_view, dim3(n), dim3(WAVE), 0, h->stream, a);
-  HIPCHK(h, hipGetLastError());
-  return 0;
-}
-// The same definitions on the host, from one hot row (cc4_get_state, a checkpoint): no device, no handle.
-static EnvState* row_copy(const void* hot_row) {
-  EnvState* s = static_cast<EnvState*>(aligned_alloc(alignof(EnvState), sizeof(EnvState)));   // (the caller's bytes may sit at any address)
-  if (s) memcpy(s, hot_row, sizeof(EnvState));
-  return s;
-}
-int cc4_red_view_from_row(const void* hot_row, uint8_t* hosts, int32_t* scalars) {
-  if (!hot_row || !hosts) return -2;
-  EnvState* s = row_copy(hot_row);
-  if (!s) return -1;
-  red_view_from_row(s, hosts, scalars);
-  free(s);
-  return 0;
-}
-// ---- blue's own knowledge (include/cc4.h; cc4_k_blue.hip; the definition: cc4_blue_view.h).  One launch on the main stream behind the group streams,
-// no host synchronisation; it only reads rows: the hot rows and, of the cold rows, the event log and the sus lists as the last step left them.
-int cc4_blue_view_device(cc4_handle* h, const void* d_bank, int32_t capacity, const int32_t* d_ids, int32_t n, uint8_t* d_hosts, int32_t* d_scalars) {
-  const char* who = "cc4_blue_view_device";
-  if (h->rollout_k > 0) { h->err = std::string(who) + ": a rollout is in flight on this handle: cc4_rollout_end first"; return -2; }
-  if (n < 0) { h->err = std::string(who) + ": n < 0"; return -2; }
-  if (n == 0) return 0;
-  if (!d_hosts || reinterpret_cast<uintptr_t>(d_hosts) % 8 || reinterpret_cast<uintptr_t>(d_scalars) % 4) {
-    h->err = std::string(who) + ": the host-view buffer is required and must be 8-byte aligned (the agent words: 4-byte aligned or NULL)"; return -2;
-  }
-  if (d_bank && capacity < 1) { h->err = std::string(who) + ": a bank needs a capacity of at least one slot"; return -2; }
-  if (reinterpret_cast<uintptr_t>(d_bank) % 64) { h->err = std::string(who) + ": a bank must be 64-byte aligned"; return -2; }
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  if (join_groups(h)) return -1;
-  BlueViewArgs a{h->d_state, h->d_cold, h->cold_row, static_cast<const uint8_t*>(d_bank), slot_bytes(h->cold_row), d_ids, n,
-                 d_bank ? capacity : h->cfg.num_envs, h->cfg.steps, h->cfg.rng_mode, d_hosts, d_scalars, h->d_copy_fault};
-  hipLaunchKernelGGL(k_blue_view, dim3(n), dim3(WAVE), 0, h->stream, a);
-  HIPCHK(h, hipGetLastError());
-  return 0;
-}
-// The same on the host, from one hot row and (optionally) its cold row: no device, no handle.  Only the event log and the sus lists of the cold row
-// are read; they are copied, like the hot row, because the caller's bytes may sit at any address.
-int cc4_blue_view_from_row(const void* hot_row, const void* cold_row, int32_t steps, uint8_t* hosts, int32_t* scalars) {
-  if (!hot_row || !hosts) return -2;
-  EnvState* s = row_copy(hot_row);
-  if (!s) return -1;
-  if (steps <= 0) steps = s->steps;                  // (the episode length the row itself was generated for)
-  if (steps <= 0 || steps > (1 << 20)) { free(s); return -2; }
-  int rc = 0;
-  if (!cold_row) blue_view_from_row(s, nullptr, nullptr, steps, hosts, scalars);
-  else {
-    const size_t b_sus = sizeof(uint32_t) * (size_t)NBLUE * (size_t)cold_sus_cap(steps);
-    EvLog* lg = static_cast<EvLog*>(aligned_alloc(alignof(EvLog), sizeof(EvLog)));
-    uint32_t* sus = static_cast<uint32_t*>(malloc(b_sus));
-    if (!lg || !sus) rc = -1;
-    else {
-      memcpy(lg, static_cast<const char*>(cold_row) + offsetof(EnvCold, evlog), sizeof(EvLog));
-      memcpy(sus, static_cast<const char*>(cold_row) + sizeof(EnvCold), b_sus);
-      blue_view_from_row(s, lg, sus, steps, hosts, scalars);
-    }
-    free(lg); free(sus);
-  }
-  free(s);
-  return rc;
-}
-// ---- the Monitor's connections as edge lists (include/cc4.h; cc4_k_edges.hip; the definition: cc4_blue_edges.h).  One launch on the main stream behind
-// the group streams, no host synchronisation; it only reads rows: of the hot rows exists and step_count, of the cold rows the event log.
-int cc4_blue_edges_device(cc4_handle* h, const void* d_bank, int32_t capacity, const int32_t* d_ids, int32_t n, int32_t max_edges, int32_t* d_edges,
-                          int32_t* d_counts) {
-  const char* who = "cc4_blue_edges_device";
-  if (h->rollout_k > 0) { h->err = std::string(who) + ": a rollout is in flight on this handle: cc4_rollout_end first"; return -2; }
-  if (n < 0) { h->err = std::string(who) + ": n < 0"; return -2; }
-  if (max_edges < 1 || max_edges > BE_MAX) { h->err = std::string(who) + ": max_edges must be 1 .. " + std::to_string((int)BE_MAX); return -2; }
-  if (n == 0) return 0;
-  if (!d_edges || reinterpret_cast<uintptr_t>(d_edges) % 16 || reinterpret_cast<uintptr_t>(d_counts) % 4) {
-    h->err = std::string(who) + ": the edge buffer is required and must be 16-byte aligned (the counts: 4-byte aligned or NULL)"; return -2;
-  }
-  if (d_bank && capacity < 1) { h->err = std::string(who) + ": a bank needs a capacity of at least one slot"; return -2; }
-  if (reinterpret_cast<uintptr_t>(d_bank) % 64) { h->err = std::string(who) + ": a bank must be 64-byte aligned"; return -2; }
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  if (join_groups(h)) return -1;
-  BlueEdgesArgs a{h->d_state, h->d_cold, h->cold_row, static_cast<const uint8_t*>(d_bank), slot_bytes(h->cold_row), d_ids, n,
-                  d_bank ? capacity : h->cfg.num_envs, h->cfg.steps, h->cfg.rng_mode, max_edges, d_edges, d_counts, h->d_copy_fault};
-  hipLaunchKernelGGL(k_blue_edges, dim3(n), dim3(WAVE), 0, h->stream, a);
-  HIPCHK(h, hipGetLastError());
-  return 0;
-}
-// The same on the host, from one hot row and (optionally) its cold row: no device, no handle.  Only the event log of the cold row is read; it is
-// copied, like the hot row, because the caller's bytes may sit at any address.
-int cc4_blue_edges_from_row(const void* hot_row, const void* cold_row, int32_t steps, int32_t max_edges, int32_t* edges, int32_t* counts) {
-  if (!hot_row || !edges || max_edges < 1 || max_edges > BE_MAX) return -2;
-  EnvState* s = row_copy(hot_row);
-  if (!s) return -1;
-  if (steps <= 0) steps = s->steps;
-  if (steps <= 0 || steps > (1 << 20)) { free(s); return -2; }
-  int rc = 0;
-  if (!cold_row) blue_edges_from_row(s, nullptr, max_edges, edges, counts);
-  else {
-    EvLog* lg = static_cast<EvLog*>(aligned_alloc(alignof(EvLog), sizeof(EvLog)));
-    if (!lg) rc = -1;
-    else {
-      memcpy(lg, static_cast<const char*>(cold_row) + offsetof(EnvCold, evlog), sizeof(EvLog));
-      blue_edges_from_row(s, lg, max_edges, edges, counts);
-    }
-    free(lg);
-  }
-  free(s);
-  return rc;
-}
-// ---- reward terms (include/cc4.h; cc4_k_reward.hip; the definition: cc4_reward_terms.h).
-// The switch: the handle behaves as after a cc4_step_red_device whose records were all "the scripted class acts" -- d_ext filled with none-records,
-// ext_seen set -- so launch_step and the `plain` tests of cc4_api_run.hip select the full builds and pass a.ext with no condition of their own.
-int cc4_enable_reward_terms(cc4_handle* h, int32_t enable) {
-  const char* who = "cc4_enable_reward_terms";
-  if (h->rollout_k > 0) { h->err = std::string(who) + ": a rollout is in flight on this handle: cc4_rollout_end first"; return -2; }
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  if (join_groups(h)) return -1;
-  if (enable) {
-    if (!h->d_ext) HIPCHK(h, hipMalloc(&h->d_ext, (size_t)h->cfg.num_envs * EXT_PER_ENV * sizeof(ExtAct)));
-    if (!h->ext_seen || h->ext_dirty || h->ext_green_dirty) {
-      HIPCHK(h, hipMemsetAsync(h->d_ext, 0xFF, (size_t)h->cfg.num_envs * EXT_PER_ENV * sizeof(ExtAct), h->stream));     // type -1 everywhere: nothing submitted
-      h->ext_dirty = false; h->ext_green_dirty = false;
-    }
-    h->terms_on = true; h->ext_seen = true;
-  } else {
-    h->terms_on = false;
-    h->ext_seen = h->ext_submitted;      // (a handle that has taken red / green actions keeps serving the rates a queued action came with)
-  }
-  return 0;
-}
-int cc4_reward_terms_enabled(cc4_handle* h) { return h && h->terms_on ? 1 : 0; }
-// One launch on the main stream behind the group streams, no host synchronisation; it only reads rows: the hot rows and the record of the cold rows
-// as the last step left them.
-int cc4_reward_terms_device(cc4_handle* h, const void* d_bank, int32_t capacity, const int32_t* d_ids, int32_t n, int32_t* d_terms, int32_t* d_words) {
-  const char* who = "cc4_reward_terms_device";
-  if (h->rollout_k > 0) { h->err = std::string(who) + ": a rollout is in flight on this handle: cc4_rollout_end first"; return -2; }
-  if (n < 0) { h->err = std::string(who) + ": n < 0"; return -2; }
-  if (n == 0) return 0;
-  if (!d_terms || reinterpret_cast<uintptr_t>(d_terms) % 16 || reinterpret_cast<uintptr_t>(d_words) % 16) {
-    h->err = std::string(who) + ": the terms buffer is required and must be 16-byte aligned (the words: 16-byte aligned or NULL)"; return -2;
-  }
-  if (d_bank && capacity < 1) { h->err = std::string(who) + ": a bank needs a capacity of at least one slot"; return -2; }
-  if (reinterpret_cast<uintptr_t>(d_bank) % 64) { h->err = std::string(who) + ": a bank must be 64-byte aligned"; return -2; }
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  if (join_groups(h)) return -1;
-  RewardArgs a{h->d_state, h->d_cold, h->cold_row, static_cast<const uint8_t*>(d_bank), slot_bytes(h->cold_row), d_ids, n,
-               d_bank ? capacity : h->cfg.num_envs, h->cfg.steps, h->cfg.rng_mode, d_terms, d_words, h->d_copy_fault};
-  hipLaunchKernelGGL(k_reward_terms, dim3(n), dim3(WAVE), 0, h->stream, a);
-  HIPCHK(h, hipGetLastError());
-  return 0;
-}
-// The same on the host, from one hot row and (optionally) its cold row: no device, no handle.  Only the record of the cold row is read; it is
-// copied, like the hot row, because the caller's bytes may sit at any address.
-int cc4_reward_terms_from_row(const void* hot_row, const void* cold_row, int32_t steps, int32_t* terms, int32_t* words) {
-  if (!hot_row || !terms || !words) return -2;
-  EnvState* s = row_copy(hot_row);
-  if (!s) return -1;
-  if (steps <= 0) steps = s->steps;
-  if (steps <= 0 || steps > (1 << 20)) { free(s); return -2; }
-  RewardRec rec;
-  if (cold_row) memcpy(&rec, static_cast<const char*>(cold_row) + offsetof(EnvCold, rwd), sizeof(RewardRec));
-  reward_terms_from_row(s, cold_row ? &rec : nullptr, terms, words);
-  free(s);
-  return 0;
-}
-int cc4_red_record_from_row(const void* hot_row, int32_t agent, const int32_t* words, cc4_agent_action* out) {
-  if (!hot_row || !words || !out || agent < 0 || agent >= NRED) return -2;
-  EnvState* s = row_copy(hot_row);
-  if (!s) return -1;
-  ExtActW rec;
-  const bool ok = red_record(s, agent, words[0], words[1], words[2], words[3], &rec);
-  memcpy(out, rec.w, sizeof(*out));
-  free(s);
-  return ok ? 0 : 1;
-}
 
 // ---- group-wise stepping for a policy that lives on the GPU.  A step of a large batch is one launch per episode group, each group on its
 // own stream, and the groups never wait for each other -- unless the caller's policy makes them: a policy kernel over the WHOLE batch
@@ -1122,36 +930,6 @@ int cc4_clone_episodes(cc4_handle* h, int32_t n, const int32_t* src, const int32
   if (seeds) HIPCHK(h, hipMemcpyAsync(h->d_copy_seeds, seeds, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
   if (int rc = cc4_copy_episodes_device(h, n, nullptr, 0, h->d_copy_idx, nullptr, 0, h->d_copy_idx + N, seeds ? h->d_copy_seeds : nullptr)) return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));     // (the host arrays may go away once the call returns)
-  return 0;
-}
-// ---- the true state as tensors (cc4_k_feat.hip; the definition: cc4_features.h).  One launch on the main stream behind the group streams, no host
-// synchronisation; it only reads rows, so the next step launches need no ordering behind it beyond the main stream's own.
-int cc4_state_features_device(cc4_handle* h, const void* d_bank, int32_t capacity, const int32_t* d_ids, int32_t n, uint8_t* d_hosts, int32_t* d_global) {
-  const char* who = "cc4_state_features_device";
-  if (h->rollout_k > 0) { h->err = std::string(who) + ": a rollout is in flight on this handle: cc4_rollout_end first"; return -2; }
-  if (n < 0) { h->err = std::string(who) + ": n < 0"; return -2; }
-  if (n == 0) return 0;
-  if (!d_hosts || reinterpret_cast<uintptr_t>(d_hosts) % 16 || reinterpret_cast<uintptr_t>(d_global) % 4) {
-    h->err = std::string(who) + ": the host-feature buffer is required and must be 16-byte aligned (the episode words: 4-byte aligned or NULL)"; return -2;
-  }
-  if (d_bank && capacity < 1) { h->err = std::string(who) + ": a bank needs a capacity of at least one slot"; return -2; }
-  if (reinterpret_cast<uintptr_t>(d_bank) % 64) { h->err = std::string(who) + ": a bank must be 64-byte aligned"; return -2; }
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  if (join_groups(h)) return -1;
-  FeatArgs a{h->d_state, static_cast<const uint8_t*>(d_bank), slot_bytes(h->cold_row), d_ids, n, d_bank ? capacity : h->cfg.num_envs,
-             h->cfg.steps, h->cfg.rng_mode, d_hosts, d_global, h->d_copy_fault};
-  hipLaunchKernelGGL(k_state_features, dim3(n), dim3(WAVE), 0, h->stream, a);
-  HIPCHK(h, hipGetLastError());
-  return 0;
-}
-// The same definition on the host, from one hot row (cc4_get_state, a checkpoint): no device, no handle.
-int cc4_state_features_from_row(const void* hot_row, uint8_t* hosts, int32_t* global) {
-  if (!hot_row || !hosts) return -2;
-  EnvState* s = static_cast<EnvState*>(aligned_alloc(alignof(EnvState), sizeof(EnvState)));   // (the caller's bytes may sit at any address)
-  if (!s) return -1;
-  memcpy(s, hot_row, sizeof(EnvState));
-  feat_from_row(s, hosts, global);
-  free(s);
   return 0;
 }
 int cc4_synchronize(cc4_handle* h) {

@@ -1,5 +1,5 @@
 // cc4_args.h -- what the host side and the kernels of libcc4.so share: the constants, the argument blocks of the kernels (StepArgs, XchgArgs, RunArgs,
-// PlanArgs, ResetArgs, CopyArgs, FeatArgs, RedSubmitArgs, RedViewArgs, BlueViewArgs, BlueEdgesArgs, RewardArgs), the snapshot-slot layout, and the register budgets of the kernels.  No device helper (cc4_kernels.h) and nothing of
+// PlanArgs, ResetArgs, CopyArgs, RedSubmitArgs, and ViewSrc with the five view blocks FeatArgs, RedViewArgs, BlueViewArgs, BlueEdgesArgs, RewardArgs), the snapshot-slot layout, and the register budgets of the kernels.  No device helper (cc4_kernels.h) and nothing of
 // the C++ host library (cc4_host.h).  The index arithmetic of the persistent schedule -- partitions, tickets, runs, the progress word -- is in cc4_sched.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -177,6 +177,12 @@ CC4_HD size_t slot_bytes(size_t cold_row) { return slot_out_off(cold_row) + SLOT
 static_assert(OBS_PACKED + 12 <= (int)SLOT_OUT_BYTES && sizeof(SlotHdr) % 64 == 0 && sizeof(EnvState) % 64 == 0, "slot layout");
 enum : uint32_t { CF_RANGE = CC4_COPY_RANGE, CF_DUP_DST = CC4_COPY_DUP_DST, CF_SRC_IS_DST = CC4_COPY_SRC_IS_DST, CF_SLOT_EMPTY = CC4_COPY_SLOT_EMPTY,
                   CF_SLOT_CONFIG = CC4_COPY_SLOT_CONFIG };   // cc4_copy_faults bits
+// The test of a slot's header before anything reads the slot: 0, or the fault bit of a slot that was never written / that a handle of another
+// configuration wrote (the derived views' view_rows and k_copy_episodes)
+CC4_HD uint32_t slot_hdr_fault(const SlotHdr* hdr, int steps, int rng_mode) {
+  if (hdr->magic != SLOT_MAGIC || hdr->version != SLOT_VERSION) return CF_SLOT_EMPTY;
+  return hdr->steps != steps || hdr->rng_mode != rng_mode ? CF_SLOT_CONFIG : 0u;
+}
 struct CopyArgs {
   EnvState* st; EnvCold* cold; size_t cold_row;          // the handle's episodes
   int32_t* obs; float* reward; uint8_t* done; uint32_t* err; uint8_t* mask; uint8_t* mask_stale;
@@ -188,16 +194,23 @@ struct CopyArgs {
   uint32_t* fault;
 };
 
-// ---- state features (cc4_state_features_device, cc4_k_feat.hip; the definition: cc4_features.h).  Entry i reads episode ids[i] (null: i) of the handle,
-// or the hot row inside slot ids[i] of a snapshot bank, and writes hosts[i] / glob[i].
-struct FeatArgs {
-  const EnvState* st;                                    // the handle's hot rows (bank == null)
+// ---- the derived views (cc4_state_features_device, cc4_red_view_device, cc4_blue_view_device, cc4_blue_edges_device, cc4_reward_terms_device): kernels
+// that read tensors out of the batch without stepping it, one wavefront per entry.  Their common call shape, stated once: entry i reads episode
+// ids[i] (null: i) of the handle -- its hot row and, at cold_at(cold, e, cold_row), its cold row -- or the two rows inside slot ids[i] of a snapshot
+// bank; an index out of range, a slot that was never written or one of another configuration gives the view's empty output and raises its CF_* bit in
+// the handle's fault word.  ViewSrc is that source, the first member of every view's argument block; view_rows (cc4_kernels.h) resolves an entry.
+struct ViewSrc {
+  const EnvState* st; const EnvCold* cold; size_t cold_row;   // the handle's rows (bank == null)
   const uint8_t* bank; size_t slot;                      // or a snapshot bank and the bytes per slot
   const int32_t* ids;                                    // [count] or null
   int count, cap, steps, rng_mode;                       // cap: episodes of the handle / slots of the bank
+  uint32_t* fault;
+};
+// state features (cc4_k_feat.hip; the definition: cc4_features.h): the hot row only
+struct FeatArgs {
+  ViewSrc src;
   uint8_t* hosts;                                        // [count][137][16], 16-byte aligned
   int32_t* glob;                                         // [count][32] or null
-  uint32_t* fault;
 };
 
 // ---- the red agents as learners (cc4_k_red.hip; the definition: cc4_red_view.h).  cc4_step_red_device: red[e][r] = (type, host, arg, session) becomes
@@ -209,49 +222,28 @@ struct RedSubmitArgs {
   int n, clear_green;
   uint32_t* fault;
 };
-// cc4_red_view_device: entry i reads episode ids[i] (null: i) of the handle, or the hot row inside slot ids[i] of a snapshot bank, as FeatArgs does
+// what each red agent knows (the same file and definition): the hot row only
 struct RedViewArgs {
-  const EnvState* st;
-  const uint8_t* bank; size_t slot;
-  const int32_t* ids;
-  int count, cap, steps, rng_mode;
+  ViewSrc src;
   uint8_t* hosts;                                        // [count][NRED][137][8], 16-byte aligned
   int32_t* scal;                                         // [count][NRED][16] or null
-  uint32_t* fault;
 };
-
-// ---- blue's own knowledge (cc4_k_blue.hip; the definition: cc4_blue_view.h).  cc4_blue_view_device: entry i reads episode ids[i] (null: i) of the
-// handle -- its hot row and, at cold_at(cold, e, cold_row), its cold row -- or the two rows inside slot ids[i] of a snapshot bank
+// blue's own knowledge (cc4_k_blue.hip; the definition: cc4_blue_view.h): of the cold row the event log and the sus lists
 struct BlueViewArgs {
-  const EnvState* st; const EnvCold* cold; size_t cold_row;
-  const uint8_t* bank; size_t slot;
-  const int32_t* ids;
-  int count, cap, steps, rng_mode;
+  ViewSrc src;
   uint8_t* hosts;                                        // [count][NBLUE][137][8], 8-byte aligned
   int32_t* scal;                                         // [count][NBLUE][16] or null
-  uint32_t* fault;
 };
-
-// ---- the Monitor's connections as edge lists (cc4_k_edges.hip; the definition: cc4_blue_edges.h).  cc4_blue_edges_device: the rows of entry i as for
-// BlueViewArgs
+// the Monitor's connections as edge lists (cc4_k_edges.hip; the definition: cc4_blue_edges.h): of the cold row the event log
 struct BlueEdgesArgs {
-  const EnvState* st; const EnvCold* cold; size_t cold_row;
-  const uint8_t* bank; size_t slot;
-  const int32_t* ids;
-  int count, cap, steps, rng_mode, max_edges;
+  ViewSrc src;
+  int max_edges;
   int32_t* edges;                                        // [count][max_edges][8], 16-byte aligned
   int32_t* counts;                                       // [count][8] or null
-  uint32_t* fault;
 };
-
-// ---- reward terms (cc4_k_reward.hip; the definition: cc4_reward_terms.h).  cc4_reward_terms_device: entry i reads episode ids[i] (null: i) of the
-// handle -- of its hot row about 150 bytes, of its cold row the 64-byte record EnvCold.rwd -- or the two rows inside slot ids[i] of a snapshot bank
+// reward terms (cc4_k_reward.hip; the definition: cc4_reward_terms.h): of the hot row about 150 bytes, of the cold row the 64-byte record EnvCold.rwd
 struct RewardArgs {
-  const EnvState* st; const EnvCold* cold; size_t cold_row;
-  const uint8_t* bank; size_t slot;
-  const int32_t* ids;
-  int count, cap, steps, rng_mode;
+  ViewSrc src;
   int32_t* terms;                                        // [count][9][4], 16-byte aligned
   int32_t* words;                                        // [count][16], 16-byte aligned, or null
-  uint32_t* fault;
 };

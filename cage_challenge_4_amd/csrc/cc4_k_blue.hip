@@ -1,7 +1,7 @@
 // cc4_k_blue.hip -- blue's own knowledge as device tensors: the kernel beside the step (the definition: cc4_blue_view.h, shared with the host function).
 //   k_blue_view   cc4_blue_view_device: one wavefront per requested episode or bank slot, a streaming kernel like k_red_view (the rows are read where
-//                 they lie: the handle's hot and cold rows, or the rows inside a snapshot slot -- a copy carries the log header, the live log entries and
-//                 the live sus spans at the same offsets).
+//                 view_rows, cc4_view_src.h, finds them -- a snapshot slot carries the log header, the live log entries and the live sus spans at the
+//                 same offsets).
 //                   1. the summary is zeroed in LDS: two words per host, a half word per (agent, host), two words per agent -- 2508 bytes, two of the
 //                      1280-byte granules LDS is handed out in (cc4_blue_view.h: why not two words per pair);
 //                   2. the lanes stride over the entries of the step's event log (when it is valid: at most MAX_EV, 12 bytes each) and over the five sus
@@ -10,9 +10,8 @@
 //                   3. the lanes stride over the 685 (agent, host) rows: one 8-byte store per lane, consecutive lanes, consecutive addresses (5 x 137 is
 //                      odd: the block of an odd output index is 8- but not 16-byte aligned, so there is no two-rows-per-store form as in k_red_view);
 //                   4. the lanes write the 80 agent words.
-//                 An entry whose index is out of range, or whose slot was never written or comes from another configuration, gets all-zero output rows
-//                 and raises its CF_* bit in the handle's fault word.
-#include "cc4_args.h"
+//                 The empty output of a refused entry: all-zero rows.
+#include "cc4_view_src.h"
 #include "cc4_blue_view.h"
 #include "cc4_kernel_decls.h"
 
@@ -24,25 +23,17 @@ __global__ __launch_bounds__(WAVE) void k_blue_view(BlueViewArgs a) {
   __shared__ uint32_t rem[BV_REM_WORDS];                // the remote count of every (agent, host), two to a word
   __shared__ uint32_t agt[2 * NBLUE];                   // dec[b], tot[b]
   const int i = (int)blockIdx.x, lane = (int)threadIdx.x;
-  if (i >= a.count) return;
+  if (i >= a.src.count) return;
   uint2* const out = reinterpret_cast<uint2*>(a.hosts + (size_t)i * BV_HOST_BYTES);
   int32_t* const os = a.scal ? a.scal + (size_t)i * (NBLUE * BV_SCALARS) : nullptr;
-  const int e = a.ids ? a.ids[i] : i;
-  uint32_t f = 0;                                       // (wave-uniform: every lane reads the same words)
-  if (e < 0 || e >= a.cap) f = CF_RANGE;
-  else if (a.bank) {
-    const SlotHdr* hdr = reinterpret_cast<const SlotHdr*>(a.bank + (size_t)e * a.slot);
-    if (hdr->magic != SLOT_MAGIC || hdr->version != SLOT_VERSION) f = CF_SLOT_EMPTY;
-    else if (hdr->steps != a.steps || hdr->rng_mode != a.rng_mode) f = CF_SLOT_CONFIG;
-  }
-  if (f) {
-    if (lane == 0) atomicOr(a.fault, f);
+  const ViewRows vr = view_rows(a.src, i, lane);        // (wave-uniform: cc4_view_src.h)
+  if (vr.fault) {
     for (int k = lane; k < BV_ROWS; k += WAVE) out[k] = make_uint2(0u, 0u);
     if (os) for (int k = lane; k < NBLUE * BV_SCALARS; k += WAVE) os[k] = 0;
     return;
   }
-  const EnvState* const s = a.bank ? reinterpret_cast<const EnvState*>(a.bank + (size_t)e * a.slot + sizeof(SlotHdr)) : a.st + e;
-  const EnvCold* const c = a.bank ? reinterpret_cast<const EnvCold*>(a.bank + (size_t)e * a.slot + slot_cold_off()) : cold_at(a.cold, (size_t)e, a.cold_row);
+  const EnvState* const s = vr.s;
+  const EnvCold* const c = vr.c;
   uint32_t* const dec = agt, * const tot = agt + NBLUE;
 
   for (int k = lane; k < BV_HW_WORDS; k += WAVE) hw[k] = 0u;
@@ -56,8 +47,8 @@ __global__ __launch_bounds__(WAVE) void k_blue_view(BlueViewArgs a) {
     for (int k = lane; k < n; k += WAVE) bv_fold_event(s, lg->rec[k], (uint32_t)k, hw, rem, dec, tot);
   }
   for (int b = 0; b < NBLUE; ++b) {
-    const uint32_t* const p = cold_sus(c, a.steps, b);
-    const int n = bv_nsus(s, b, a.steps);
+    const uint32_t* const p = cold_sus(c, a.src.steps, b);
+    const int n = bv_nsus(s, b, a.src.steps);
     for (int k = lane; k < n; k += WAVE) bv_fold_sus(s, b, p[k], hw);
   }
   __syncthreads();

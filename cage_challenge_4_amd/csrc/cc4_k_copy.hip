@@ -52,11 +52,7 @@ __global__ __launch_bounds__(CT) void k_copy_episodes(CopyArgs a) {
         const uint32_t sc = __hip_atomic_load(a.claim + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (sc == once || sc == many) f |= CF_SRC_IS_DST;
       }
-      if (a.src_bank) {
-        const SlotHdr* hdr = reinterpret_cast<const SlotHdr*>(a.src_bank + (size_t)s * a.slot);
-        if (hdr->magic != SLOT_MAGIC || hdr->version != SLOT_VERSION) f |= CF_SLOT_EMPTY;
-        else if (hdr->steps != a.steps || hdr->rng_mode != a.rng_mode) f |= CF_SLOT_CONFIG;
-      }
+      if (a.src_bank) f |= slot_hdr_fault(reinterpret_cast<const SlotHdr*>(a.src_bank + (size_t)s * a.slot), a.steps, a.rng_mode);
     }
     if (f) atomicOr(a.fault, f);
     ok = f == 0;

@@ -1,8 +1,7 @@
 // cc4_k_edges.hip -- the Monitor's connection entries as device edge lists: the kernel beside the step (the definition: cc4_blue_edges.h, shared with
 // the host function).
-//   k_blue_edges  cc4_blue_edges_device: one wavefront per requested episode or bank slot, with k_blue_view's call shape (the rows are read where they
-//                 lie: the handle's hot and cold rows, or the rows inside a snapshot slot -- a copy carries the log header and the live log entries at
-//                 the same offsets).  A keyed merge of at most MAX_EV = 160 entries, by ranking in LDS:
+//   k_blue_edges  cc4_blue_edges_device: one wavefront per requested episode or bank slot, the rows read where view_rows (cc4_view_src.h) finds
+//                 them -- a snapshot slot carries the log header and the live log entries at the same offsets.  A keyed merge of at most MAX_EV = 160 entries, by ranking in LDS:
 //                   1. the lanes stride over the entries of the step's event log (when it is valid: at most MAX_EV, 12 bytes each); the qualifying ones
 //                      are compacted into LDS -- 64-bit key, rep -- by ballot and prefix popcount, in three rounds of 64;
 //                   2. each lane marks which of its (at most three) entries is the first of its key (the head);
@@ -11,9 +10,8 @@
 //                      32-byte row as two 16-byte stores; the heads count themselves per agent with LDS atomics;
 //                   4. the lanes write -1 into rows [min(total, max_edges), max_edges), 16 bytes a store, and the eight count words.
 //                 LDS: 160 keys, 160 rep words, 8 counters = 1952 bytes, two of the 1280-byte granules.
-//                 An entry whose index is out of range, or whose slot was never written or comes from another configuration, gets all -1 rows and zero
-//                 counts and raises its CF_* bit in the handle's fault word.
-#include "cc4_args.h"
+//                 The empty output of a refused entry: all -1 rows and zero counts.
+#include "cc4_view_src.h"
 #include "cc4_blue_edges.h"
 #include "cc4_kernel_decls.h"
 
@@ -26,27 +24,19 @@ __global__ __launch_bounds__(WAVE) void k_blue_edges(BlueEdgesArgs a) {
   __shared__ uint32_t reps[BE_MAX];
   __shared__ uint32_t seg[BE_WORDS];                       // heads per agent (words 0 .. NBLUE - 1)
   const int i = (int)blockIdx.x, lane = (int)threadIdx.x;
-  if (i >= a.count) return;
+  if (i >= a.src.count) return;
   const int E = a.max_edges;
   int4* const out = reinterpret_cast<int4*>(a.edges + (size_t)i * (size_t)E * BE_COLS);      // two int4 per row
   int32_t* const oc = a.counts ? a.counts + (size_t)i * BE_WORDS : nullptr;
-  const int e = a.ids ? a.ids[i] : i;
-  uint32_t f = 0;                                          // (wave-uniform: every lane reads the same words)
-  if (e < 0 || e >= a.cap) f = CF_RANGE;
-  else if (a.bank) {
-    const SlotHdr* hdr = reinterpret_cast<const SlotHdr*>(a.bank + (size_t)e * a.slot);
-    if (hdr->magic != SLOT_MAGIC || hdr->version != SLOT_VERSION) f = CF_SLOT_EMPTY;
-    else if (hdr->steps != a.steps || hdr->rng_mode != a.rng_mode) f = CF_SLOT_CONFIG;
-  }
+  const ViewRows vr = view_rows(a.src, i, lane);        // (wave-uniform: cc4_view_src.h)
   const int4 none = make_int4(-1, -1, -1, -1);
-  if (f) {
-    if (lane == 0) atomicOr(a.fault, f);
+  if (vr.fault) {
     for (int k = lane; k < 2 * E; k += WAVE) out[k] = none;
     if (oc && lane < BE_WORDS) oc[lane] = 0;
     return;
   }
-  const EnvState* const s = a.bank ? reinterpret_cast<const EnvState*>(a.bank + (size_t)e * a.slot + sizeof(SlotHdr)) : a.st + e;
-  const EnvCold* const c = a.bank ? reinterpret_cast<const EnvCold*>(a.bank + (size_t)e * a.slot + slot_cold_off()) : cold_at(a.cold, (size_t)e, a.cold_row);
+  const EnvState* const s = vr.s;
+  const EnvCold* const c = vr.c;
   const EvLog* const lg = &c->evlog;
   const bool valid = bv_events_valid(s, lg);
   const int n = valid ? (int)lg->n : 0;                    // (<= MAX_EV: bv_events_valid)

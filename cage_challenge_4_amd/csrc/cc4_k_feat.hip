@@ -5,10 +5,9 @@
 //   2. the lanes stride over the hosts: the second 32 bytes of the HostDyn row (svcs, nproc, nsf) as two 16-byte loads, the host's 16 bytes as
 //      one 16-byte store -- consecutive lanes, consecutive hosts;
 //   3. lanes 0..31 write the episode words.
-// A streaming kernel: the hot row is read where it lies (the handle's rows, or the row inside a snapshot slot, [SlotHdr | hot row | ..]), nothing is staged.
-// An entry whose index is out of range, or whose slot was never written or comes from another configuration, gets an all-zero output row and
-// raises its CF_* bit in the handle's fault word.
-#include "cc4_args.h"
+// A streaming kernel: the hot row is read where view_rows (cc4_view_src.h) finds it, nothing is staged.  The empty output of a refused entry: an
+// all-zero row.
+#include "cc4_view_src.h"
 #include "cc4_features.h"
 #include "cc4_kernel_decls.h"
 
@@ -18,24 +17,16 @@ __global__ __launch_bounds__(WAVE) void k_state_features(FeatArgs a) {
   __shared__ uint32_t sum[MAXH + 10];                   // sessions per host, then the two host bitmaps
   uint32_t* const cnt = sum; uint32_t* const rootm = sum + MAXH; uint32_t* const greenm = sum + MAXH + 5;
   const int i = (int)blockIdx.x, lane = (int)threadIdx.x;
-  if (i >= a.count) return;
+  if (i >= a.src.count) return;
   uint4* const out = reinterpret_cast<uint4*>(a.hosts + (size_t)i * (FEAT_HOSTS * FEAT_PER_HOST));
   int32_t* const og = a.glob ? a.glob + (size_t)i * FEAT_GLOBAL : nullptr;
-  const int e = a.ids ? a.ids[i] : i;
-  uint32_t f = 0;                                       // (wave-uniform: every lane reads the same words)
-  if (e < 0 || e >= a.cap) f = CF_RANGE;
-  else if (a.bank) {
-    const SlotHdr* hdr = reinterpret_cast<const SlotHdr*>(a.bank + (size_t)e * a.slot);
-    if (hdr->magic != SLOT_MAGIC || hdr->version != SLOT_VERSION) f = CF_SLOT_EMPTY;
-    else if (hdr->steps != a.steps || hdr->rng_mode != a.rng_mode) f = CF_SLOT_CONFIG;
-  }
-  if (f) {
-    if (lane == 0) atomicOr(a.fault, f);
+  const ViewRows vr = view_rows(a.src, i, lane);        // (wave-uniform: cc4_view_src.h)
+  if (vr.fault) {
     for (int h = lane; h < FEAT_HOSTS; h += WAVE) out[h] = make_uint4(0u, 0u, 0u, 0u);
     if (og && lane < FEAT_GLOBAL) og[lane] = 0;
     return;
   }
-  const EnvState* const s = a.bank ? reinterpret_cast<const EnvState*>(a.bank + (size_t)e * a.slot + sizeof(SlotHdr)) : a.st + e;
+  const EnvState* const s = vr.s;
 
   for (int k = lane; k < MAXH + 10; k += WAVE) sum[k] = 0u;
   __syncthreads();

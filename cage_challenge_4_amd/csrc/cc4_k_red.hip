@@ -3,15 +3,14 @@
 //                 d_ext -- validated (a refused record becomes XA_NONE and raises CF_RANGE), CC4_RED_SID_AUTO resolved from the episode's row as it stands
 //                 before the step -- and, when the buffer may hold green records of an earlier cc4_step_ex, sets the episode's green records to none
 //                 (lane r those of green agents r, r + 6, ..).  The step kernels then read the records as they read uploaded ones.
-//   k_red_view    cc4_red_view_device: one wavefront per requested episode, a streaming kernel like k_state_features (the row is read where it lies: the
-//                 handle's rows, or the row inside a snapshot slot).
+//   k_red_view    cc4_red_view_device: one wavefront per requested episode, a streaming kernel like k_state_features (the row is read where
+//                 view_rows, cc4_view_src.h, finds it).
 //                   1. the lanes stride over the six agents' session lists (6 x 64 entries) and observation entries (6 x 32): sessions per (agent, host),
 //                      "a root session", "an abstract session" and the observation byte go into one LDS word per pair with LDS atomics;
 //                   2. the lanes stride over the 822 (agent, host) rows two at a time: one 16-byte store per lane, consecutive lanes, consecutive addresses;
 //                   3. lanes 0..63 and 0..31 write the 96 agent words.
-//                 An entry whose index is out of range, or whose slot was never written or comes from another configuration, gets all-zero output rows
-//                 and raises its CF_* bit in the handle's fault word.
-#include "cc4_args.h"
+//                 The empty output of a refused entry: all-zero rows.
+#include "cc4_view_src.h"
 #include "cc4_red_view.h"
 #include "cc4_kernel_decls.h"
 
@@ -35,24 +34,16 @@ __global__ __launch_bounds__(256) void k_red_submit(RedSubmitArgs a) {
 __global__ __launch_bounds__(WAVE) void k_red_view(RedViewArgs a) {
   __shared__ uint32_t sum[NRED * MAXH];                 // the summary word of every (agent, host)
   const int i = (int)blockIdx.x, lane = (int)threadIdx.x;
-  if (i >= a.count) return;
+  if (i >= a.src.count) return;
   uint4* const out = reinterpret_cast<uint4*>(a.hosts + (size_t)i * RV_HOST_BYTES);
   int32_t* const os = a.scal ? a.scal + (size_t)i * (NRED * RV_SCALARS) : nullptr;
-  const int e = a.ids ? a.ids[i] : i;
-  uint32_t f = 0;                                       // (wave-uniform: every lane reads the same words)
-  if (e < 0 || e >= a.cap) f = CF_RANGE;
-  else if (a.bank) {
-    const SlotHdr* hdr = reinterpret_cast<const SlotHdr*>(a.bank + (size_t)e * a.slot);
-    if (hdr->magic != SLOT_MAGIC || hdr->version != SLOT_VERSION) f = CF_SLOT_EMPTY;
-    else if (hdr->steps != a.steps || hdr->rng_mode != a.rng_mode) f = CF_SLOT_CONFIG;
-  }
-  if (f) {
-    if (lane == 0) atomicOr(a.fault, f);
+  const ViewRows vr = view_rows(a.src, i, lane);        // (wave-uniform: cc4_view_src.h)
+  if (vr.fault) {
     for (int k = lane; k < RV_HOST_VECS; k += WAVE) out[k] = make_uint4(0u, 0u, 0u, 0u);
     if (os) for (int k = lane; k < NRED * RV_SCALARS; k += WAVE) os[k] = 0;
     return;
   }
-  const EnvState* const s = a.bank ? reinterpret_cast<const EnvState*>(a.bank + (size_t)e * a.slot + sizeof(SlotHdr)) : a.st + e;
+  const EnvState* const s = vr.s;
 
   for (int k = lane; k < NRED * MAXH; k += WAVE) sum[k] = 0u;
   __syncthreads();

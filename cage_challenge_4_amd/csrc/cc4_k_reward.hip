@@ -1,8 +1,7 @@
 // cc4_k_reward.hip -- the pieces of the step reward as device tensors: the kernel beside the step (the definition: cc4_reward_terms.h, shared with the
 // host function).
-//   k_reward_terms   cc4_reward_terms_device: one wavefront per requested episode or bank slot, with k_blue_view's call shape (the rows are read where
-//                    they lie: the handle's hot and cold rows, or the rows inside a snapshot slot -- a copy carries the record in the tail of the
-//                    fixed part of the cold row).
+//   k_reward_terms   cc4_reward_terms_device: one wavefront per requested episode or bank slot, the rows read where view_rows (cc4_view_src.h)
+//                    finds them -- a snapshot slot carries the record in the tail of the fixed part of the cold row.
 //                      1. the 36 cells are zeroed in LDS (144 bytes: one of the 1280-byte granules LDS is handed out in);
 //                      2. when the record describes the row's last step: one green agent per lane (agents 64.. in a second pass of 16 lanes) tests its
 //                         bit in the two bitmaps and adds its subnet's table value and an event to its cells with LDS atomics; lanes 0..5 add the six red
@@ -10,9 +9,8 @@
 //                      3. lanes 0..8 store one subnet's four cells each, lanes 16..19 four of the 16 words each: 16-byte stores from consecutive lanes
 //                         to consecutive addresses, 144 + 64 bytes.
 //                    Read per episode: phase, step_count, n_green, green_host, the red headers' exec / nsess words, and the 64-byte record.
-//                    An entry whose index is out of range, or whose slot was never written or comes from another configuration, gets all-zero output
-//                    and raises its CF_* bit in the handle's fault word.
-#include "cc4_args.h"
+//                    The empty output of a refused entry: all zero.
+#include "cc4_view_src.h"
 #include "cc4_reward_terms.h"
 #include "cc4_kernel_decls.h"
 
@@ -22,25 +20,17 @@ static_assert(RT_SUBNETS <= 16 && RT_WORDS / 4 <= WAVE - 16 && MAXG <= 2 * WAVE 
 __global__ __launch_bounds__(WAVE) void k_reward_terms(RewardArgs a) {
   __shared__ int32_t cells[RT_CELLS];
   const int i = (int)blockIdx.x, lane = (int)threadIdx.x;
-  if (i >= a.count) return;
+  if (i >= a.src.count) return;
   uint4* const ot = reinterpret_cast<uint4*>(a.terms + (size_t)i * RT_CELLS);
   uint4* const ow = a.words ? reinterpret_cast<uint4*>(a.words + (size_t)i * RT_WORDS) : nullptr;
-  const int e = a.ids ? a.ids[i] : i;
-  uint32_t f = 0;                                       // (wave-uniform: every lane reads the same words)
-  if (e < 0 || e >= a.cap) f = CF_RANGE;
-  else if (a.bank) {
-    const SlotHdr* hdr = reinterpret_cast<const SlotHdr*>(a.bank + (size_t)e * a.slot);
-    if (hdr->magic != SLOT_MAGIC || hdr->version != SLOT_VERSION) f = CF_SLOT_EMPTY;
-    else if (hdr->steps != a.steps || hdr->rng_mode != a.rng_mode) f = CF_SLOT_CONFIG;
-  }
-  if (f) {
-    if (lane == 0) atomicOr(a.fault, f);
+  const ViewRows vr = view_rows(a.src, i, lane);        // (wave-uniform: cc4_view_src.h)
+  if (vr.fault) {
     if (lane < RT_SUBNETS) ot[lane] = make_uint4(0u, 0u, 0u, 0u);
     else if (ow && lane >= 16 && lane < 16 + RT_WORDS / 4) ow[lane - 16] = make_uint4(0u, 0u, 0u, 0u);
     return;
   }
-  const EnvState* const s = a.bank ? reinterpret_cast<const EnvState*>(a.bank + (size_t)e * a.slot + sizeof(SlotHdr)) : a.st + e;
-  const EnvCold* const c = a.bank ? reinterpret_cast<const EnvCold*>(a.bank + (size_t)e * a.slot + slot_cold_off()) : cold_at(a.cold, (size_t)e, a.cold_row);
+  const EnvState* const s = vr.s;
+  const EnvCold* const c = vr.c;
   const RewardRec* const r = &c->rwd;
 
   if (lane < RT_CELLS) cells[lane] = 0;

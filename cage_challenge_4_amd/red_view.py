@@ -16,9 +16,9 @@ Three ways to the same numbers:
 A red action is four int32 words (type, host, arg, session), ACTION_WORDS; type ACT_NONE lets the agent's scripted policy act, session SID_AUTO
 stands for the agent's first listed session (auto_sid)."""
 import ctypes
-import json
 import numpy as np
 from . import _lib as L
+from ._view_util import _bytes, _doc
 
 NUM_RED, VIEW_HOSTS, VIEW_PER_HOST, VIEW_SCALARS = L.NUM_RED, L.RED_VIEW_HOSTS, L.RED_VIEW_PER_HOST, L.RED_VIEW_SCALARS
 ACT_WORDS, SID_AUTO, ACT_NONE = L.RED_ACT_WORDS, L.RED_SID_AUTO, -1
@@ -36,12 +36,7 @@ _RS_ABSTRACT, _RS_ROOT = 1, 2
 
 def _row(row_bytes):
     lib = L.load()
-    if isinstance(row_bytes, (bytes, bytearray, memoryview)):
-        row_bytes = np.frombuffer(row_bytes, np.uint8)
-    row = np.ascontiguousarray(row_bytes, dtype=np.uint8).ravel()
-    if row.size != lib.cc4_state_bytes():
-        raise ValueError(f'a hot row has {lib.cc4_state_bytes()} bytes, got {row.size}')
-    return lib, row
+    return lib, _bytes(row_bytes, lib.cc4_state_bytes(), 'a hot row')
 
 
 def from_row(row_bytes):
@@ -69,12 +64,6 @@ def record_from_row(row_bytes, agent, words):
     if rc not in (0, 1):
         raise L.CC4Error(f'cc4_red_record_from_row failed (rc={rc})')
     return rec, bool(rc)
-
-
-def _doc(doc):
-    if isinstance(doc, (str, bytes)):
-        return json.loads(doc)
-    return doc if isinstance(doc, dict) else doc.raw
 
 
 def auto_sid(doc, r, none=0):

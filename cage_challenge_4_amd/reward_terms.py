@@ -18,6 +18,7 @@ Two ways to the same numbers:
 import ctypes
 import numpy as np
 from . import _lib as L
+from ._view_util import ZONE_OF_SUBNET, _bytes  # noqa: F401  (ZONE_OF_SUBNET: part of this module's surface)
 
 NUM_BLUE, SUBNETS, COLS, NWORDS = L.NUM_BLUE, L.REWARD_SUBNETS, L.REWARD_COLS, L.REWARD_WORDS
 
@@ -30,16 +31,6 @@ RESTORE_WORDS = slice(11, 16)
 SUBNET_NAMES = ('restricted_zone_a_subnet', 'operational_zone_a_subnet', 'restricted_zone_b_subnet', 'operational_zone_b_subnet',
                 'contractor_network_subnet', 'public_access_zone_subnet', 'admin_network_subnet', 'office_network_subnet',
                 'internet_subnet')       # SUBNET enum order (wrappers.SUBNET_NAMES)
-ZONE_OF_SUBNET = (0, 1, 2, 3, -1, 4, 4, 4, -1)      # the blue agent that defends the subnet; -1: nobody
-
-
-def _bytes(x, size, what):
-    if isinstance(x, (bytes, bytearray, memoryview)):
-        x = np.frombuffer(x, np.uint8)
-    x = np.ascontiguousarray(x, dtype=np.uint8).ravel()
-    if size is not None and x.size != size:
-        raise ValueError(f'{what} has {size} bytes, got {x.size}')
-    return x
 
 
 def from_row(hot, cold=None, steps=0):

@@ -13,6 +13,7 @@ Three ways to the same numbers:
 import ctypes
 import numpy as np
 from . import _lib as L
+from ._view_util import _bytes
 
 FEAT_HOSTS, FEAT_PER_HOST, FEAT_GLOBAL = L.FEAT_HOSTS, L.FEAT_PER_HOST, L.FEAT_GLOBAL
 
@@ -29,11 +30,7 @@ _RS_ROOT = 2
 def from_row(row_bytes):
     """(hosts [137, 16] uint8, glob [32] int32) of one packed hot row (CC4VecEnv.get_state(e), a row of get_states())."""
     lib = L.load()
-    if isinstance(row_bytes, (bytes, bytearray, memoryview)):
-        row_bytes = np.frombuffer(row_bytes, np.uint8)
-    row = np.ascontiguousarray(row_bytes, dtype=np.uint8).ravel()
-    if row.size != lib.cc4_state_bytes():
-        raise ValueError(f'a hot row has {lib.cc4_state_bytes()} bytes, got {row.size}')
+    row = _bytes(row_bytes, lib.cc4_state_bytes(), 'a hot row')
     hosts = np.zeros((FEAT_HOSTS, FEAT_PER_HOST), np.uint8)
     glob = np.zeros(FEAT_GLOBAL, np.int32)
     vp = ctypes.c_void_p

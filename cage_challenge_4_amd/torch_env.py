@@ -291,6 +291,36 @@ class CC4TorchVecEnv:
     def load_episodes(self, bank, slots, env_ids, seeds=None):
         return self._copy(slots, env_ids, src_bank=bank, seeds=seeds)
 
+    def _view(self, entry, ids, bank, out, specs, *extra):
+        """What the tensor methods of the derived views share.  entry: the cc4_*_device entry point; ids, bank, out as state_features() documents
+        them; specs: (shape of one entry, dtype, required alignment in bytes) of the view's two tensors; extra: arguments in front of the two output
+        pointers.  Ordered on the current stream both ways like step(); no host copy, no host wait."""
+        with torch.cuda.device(self.device):
+            s = torch.cuda.current_stream(self.device)
+            vp = ctypes.c_void_p
+            bp, cap = self._bank(bank) if bank is not None else (None, 0)
+            if ids is not None:
+                ids = self._index(ids, 'ids')
+                n, ip = int(ids.numel()), vp(ids.data_ptr())
+            else:
+                n, ip = (cap if bank is not None else self.num_envs), None
+            shapes = [(n,) + tuple(tail) for tail, _dt, _al in specs]
+            if out is None:
+                a, b = (torch.empty(shp, dtype=dt, device=self.device) for shp, (_tail, dt, _al) in zip(shapes, specs))
+            else:
+                a, b = out
+                for x, shp, (_tail, dt, al) in zip((a, b), shapes, specs):
+                    if (not torch.is_tensor(x) or tuple(x.shape) != shp or x.dtype != dt or x.device != self.device or not x.is_contiguous()
+                            or x.data_ptr() % al):
+                        want = ', '.join(f'{str(dt_).replace("torch.", "")} {list(shp_)} ({al_}-byte aligned)' for shp_, (_t, dt_, al_) in zip(shapes, specs))
+                        raise ValueError(f'out must be contiguous tensors ({want}) on {self.device}')
+            lib, h, sp = self.lib, self._h, vp(s.cuda_stream)
+            rc = lib.cc4_stream_wait(h, sp) or getattr(lib, entry)(h, bp, cap, ip, n, *extra, vp(a.data_ptr()), vp(b.data_ptr()))
+            if rc:
+                self.venv._chk(rc, entry)
+            self.venv._chk(lib.cc4_stream_signal(h, sp), 'cc4_stream_signal')
+        return a, b
+
     def state_features(self, ids=None, bank=None, out=None):
         """The privileged global state (cc4_state_features_device, include/cc4.h; columns and words: state_features.HOST_COLUMNS / GLOBAL_WORDS)
         as tensors on the env's device: (hosts [n, 137, 16] uint8, glob [n, 32] int32).  ids: 1-D integer tensor on the device -- episodes of
@@ -298,59 +328,14 @@ class CC4TorchVecEnv:
         out=(hosts, glob) reuses the caller's tensors.  Ordered on the current stream both ways like step(); no host copy, no host wait.  A
         faulty entry (an index out of range, a slot never written or written by another configuration) gives an all-zero row, and
         check_errors() raises CC4EngineError for it."""
-        with torch.cuda.device(self.device):
-            s = torch.cuda.current_stream(self.device)
-            vp = ctypes.c_void_p
-            bp, cap = self._bank(bank) if bank is not None else (None, 0)
-            if ids is not None:
-                ids = self._index(ids, 'ids')
-                n, ip = int(ids.numel()), vp(ids.data_ptr())
-            else:
-                n, ip = (cap if bank is not None else self.num_envs), None
-            shapes = ((n, L.FEAT_HOSTS, L.FEAT_PER_HOST), (n, L.FEAT_GLOBAL))
-            if out is None:
-                hosts = torch.empty(shapes[0], dtype=torch.uint8, device=self.device)
-                glob = torch.empty(shapes[1], dtype=torch.int32, device=self.device)
-            else:
-                hosts, glob = out
-                for x, shp, dt in ((hosts, shapes[0], torch.uint8), (glob, shapes[1], torch.int32)):
-                    if not torch.is_tensor(x) or tuple(x.shape) != shp or x.dtype != dt or x.device != self.device or not x.is_contiguous():
-                        raise ValueError(f'out must be contiguous tensors (uint8 {list(shapes[0])}, int32 {list(shapes[1])}) on {self.device}')
-            lib, h, sp = self.lib, self._h, vp(s.cuda_stream)
-            rc = lib.cc4_stream_wait(h, sp) or lib.cc4_state_features_device(h, bp, cap, ip, n, vp(hosts.data_ptr()), vp(glob.data_ptr()))
-            if rc:
-                self.venv._chk(rc, 'cc4_state_features_device')
-            self.venv._chk(lib.cc4_stream_signal(h, sp), 'cc4_stream_signal')
-        return hosts, glob
+        return self._view('cc4_state_features_device', ids, bank, out, (((L.FEAT_HOSTS, L.FEAT_PER_HOST), torch.uint8, 1), ((L.FEAT_GLOBAL,), torch.int32, 1)))
 
     def red_view(self, ids=None, bank=None, out=None):
         """What each red agent knows (cc4_red_view_device, include/cc4.h; columns and words: red_view.HOST_COLUMNS / SCALAR_WORDS) as tensors on
         the env's device: (hosts [n, 6, 137, 8] uint8, scalars [n, 6, 16] int32).  ids, bank, out and the ordering on the current stream as
         state_features(); no host copy, no host wait.  A faulty entry gives all-zero rows, and check_errors() raises CC4EngineError for it."""
-        with torch.cuda.device(self.device):
-            s = torch.cuda.current_stream(self.device)
-            vp = ctypes.c_void_p
-            bp, cap = self._bank(bank) if bank is not None else (None, 0)
-            if ids is not None:
-                ids = self._index(ids, 'ids')
-                n, ip = int(ids.numel()), vp(ids.data_ptr())
-            else:
-                n, ip = (cap if bank is not None else self.num_envs), None
-            shapes = ((n, L.NUM_RED, L.RED_VIEW_HOSTS, L.RED_VIEW_PER_HOST), (n, L.NUM_RED, L.RED_VIEW_SCALARS))
-            if out is None:
-                hosts = torch.empty(shapes[0], dtype=torch.uint8, device=self.device)
-                scal = torch.empty(shapes[1], dtype=torch.int32, device=self.device)
-            else:
-                hosts, scal = out
-                for x, shp, dt in ((hosts, shapes[0], torch.uint8), (scal, shapes[1], torch.int32)):
-                    if not torch.is_tensor(x) or tuple(x.shape) != shp or x.dtype != dt or x.device != self.device or not x.is_contiguous():
-                        raise ValueError(f'out must be contiguous tensors (uint8 {list(shapes[0])}, int32 {list(shapes[1])}) on {self.device}')
-            lib, h, sp = self.lib, self._h, vp(s.cuda_stream)
-            rc = lib.cc4_stream_wait(h, sp) or lib.cc4_red_view_device(h, bp, cap, ip, n, vp(hosts.data_ptr()), vp(scal.data_ptr()))
-            if rc:
-                self.venv._chk(rc, 'cc4_red_view_device')
-            self.venv._chk(lib.cc4_stream_signal(h, sp), 'cc4_stream_signal')
-        return hosts, scal
+        return self._view('cc4_red_view_device', ids, bank, out, (((L.NUM_RED, L.RED_VIEW_HOSTS, L.RED_VIEW_PER_HOST), torch.uint8, 1),
+                                                                 ((L.NUM_RED, L.RED_VIEW_SCALARS), torch.int32, 1)))
 
     def blue_view(self, ids=None, bank=None, out=None):
         """Blue's own knowledge (cc4_blue_view_device, include/cc4.h; columns and words: blue_view.HOST_COLUMNS / SCALAR_WORDS) as tensors on the
@@ -358,30 +343,8 @@ class CC4TorchVecEnv:
         the deployed decoy, suspicious pids, and with enable_event_log() the Monitor's entries per host (scalars[..., 10]: whether they are
         filled).  ids, bank, out and the ordering on the current stream as state_features(); no host copy, no host wait.  A faulty entry gives
         all-zero rows, and check_errors() raises CC4EngineError for it."""
-        with torch.cuda.device(self.device):
-            s = torch.cuda.current_stream(self.device)
-            vp = ctypes.c_void_p
-            bp, cap = self._bank(bank) if bank is not None else (None, 0)
-            if ids is not None:
-                ids = self._index(ids, 'ids')
-                n, ip = int(ids.numel()), vp(ids.data_ptr())
-            else:
-                n, ip = (cap if bank is not None else self.num_envs), None
-            shapes = ((n, L.NUM_BLUE, L.BLUE_VIEW_HOSTS, L.BLUE_VIEW_PER_HOST), (n, L.NUM_BLUE, L.BLUE_VIEW_SCALARS))
-            if out is None:
-                hosts = torch.empty(shapes[0], dtype=torch.uint8, device=self.device)
-                scal = torch.empty(shapes[1], dtype=torch.int32, device=self.device)
-            else:
-                hosts, scal = out
-                for x, shp, dt in ((hosts, shapes[0], torch.uint8), (scal, shapes[1], torch.int32)):
-                    if not torch.is_tensor(x) or tuple(x.shape) != shp or x.dtype != dt or x.device != self.device or not x.is_contiguous():
-                        raise ValueError(f'out must be contiguous tensors (uint8 {list(shapes[0])}, int32 {list(shapes[1])}) on {self.device}')
-            lib, h, sp = self.lib, self._h, vp(s.cuda_stream)
-            rc = lib.cc4_stream_wait(h, sp) or lib.cc4_blue_view_device(h, bp, cap, ip, n, vp(hosts.data_ptr()), vp(scal.data_ptr()))
-            if rc:
-                self.venv._chk(rc, 'cc4_blue_view_device')
-            self.venv._chk(lib.cc4_stream_signal(h, sp), 'cc4_stream_signal')
-        return hosts, scal
+        return self._view('cc4_blue_view_device', ids, bank, out, (((L.NUM_BLUE, L.BLUE_VIEW_HOSTS, L.BLUE_VIEW_PER_HOST), torch.uint8, 1),
+                                                                  ((L.NUM_BLUE, L.BLUE_VIEW_SCALARS), torch.int32, 1)))
 
     def blue_edges(self, ids=None, bank=None, out=None, max_edges=L.BLUE_EDGES_MAX):
         """The Monitor's connection entries of the step just taken as edge lists (cc4_blue_edges_device, include/cc4.h; columns and words:
@@ -395,32 +358,8 @@ class CC4TorchVecEnv:
         max_edges = int(max_edges)
         if not 1 <= max_edges <= L.BLUE_EDGES_MAX:
             raise ValueError(f'max_edges must be 1 .. {L.BLUE_EDGES_MAX}, got {max_edges}')
-        with torch.cuda.device(self.device):
-            s = torch.cuda.current_stream(self.device)
-            vp = ctypes.c_void_p
-            bp, cap = self._bank(bank) if bank is not None else (None, 0)
-            if ids is not None:
-                ids = self._index(ids, 'ids')
-                n, ip = int(ids.numel()), vp(ids.data_ptr())
-            else:
-                n, ip = (cap if bank is not None else self.num_envs), None
-            shapes = ((n, max_edges, L.BLUE_EDGES_COLUMNS), (n, L.BLUE_EDGES_WORDS))
-            if out is None:
-                edges = torch.empty(shapes[0], dtype=torch.int32, device=self.device)
-                counts = torch.empty(shapes[1], dtype=torch.int32, device=self.device)
-            else:
-                edges, counts = out
-                for x, shp in ((edges, shapes[0]), (counts, shapes[1])):
-                    if not torch.is_tensor(x) or tuple(x.shape) != shp or x.dtype != torch.int32 or x.device != self.device or not x.is_contiguous():
-                        raise ValueError(f'out must be contiguous int32 tensors ({list(shapes[0])}, {list(shapes[1])}) on {self.device}')
-                if edges.data_ptr() % 16:
-                    raise ValueError('out: the edges tensor must be 16-byte aligned')
-            lib, h, sp = self.lib, self._h, vp(s.cuda_stream)
-            rc = lib.cc4_stream_wait(h, sp) or lib.cc4_blue_edges_device(h, bp, cap, ip, n, max_edges, vp(edges.data_ptr()), vp(counts.data_ptr()))
-            if rc:
-                self.venv._chk(rc, 'cc4_blue_edges_device')
-            self.venv._chk(lib.cc4_stream_signal(h, sp), 'cc4_stream_signal')
-        return edges, counts
+        return self._view('cc4_blue_edges_device', ids, bank, out, (((max_edges, L.BLUE_EDGES_COLUMNS), torch.int32, 16), ((L.BLUE_EDGES_WORDS,), torch.int32, 1)),
+                          max_edges)
 
     def enable_event_log(self, on=True):
         """CC4VecEnv.enable_event_log (cc4_enable_event_log): record the HostEvents entries of every step, which fills the event columns of
@@ -440,31 +379,7 @@ class CC4TorchVecEnv:
         (enable_reward_terms(), or an env that steps with red_actions); then words[:, 3] + words[:, 4] == reward.  ids, bank, out and the
         ordering on the current stream as state_features(); no host copy, no host wait.  A faulty entry gives all-zero rows, and
         check_errors() raises CC4EngineError for it."""
-        with torch.cuda.device(self.device):
-            s = torch.cuda.current_stream(self.device)
-            vp = ctypes.c_void_p
-            bp, cap = self._bank(bank) if bank is not None else (None, 0)
-            if ids is not None:
-                ids = self._index(ids, 'ids')
-                n, ip = int(ids.numel()), vp(ids.data_ptr())
-            else:
-                n, ip = (cap if bank is not None else self.num_envs), None
-            shapes = ((n, L.REWARD_SUBNETS, L.REWARD_COLS), (n, L.REWARD_WORDS))
-            if out is None:
-                terms = torch.empty(shapes[0], dtype=torch.int32, device=self.device)
-                words = torch.empty(shapes[1], dtype=torch.int32, device=self.device)
-            else:
-                terms, words = out
-                for x, shp in ((terms, shapes[0]), (words, shapes[1])):
-                    if (not torch.is_tensor(x) or tuple(x.shape) != shp or x.dtype != torch.int32 or x.device != self.device or not x.is_contiguous()
-                            or x.data_ptr() % 16):
-                        raise ValueError(f'out must be contiguous, 16-byte aligned int32 tensors ({list(shapes[0])}, {list(shapes[1])}) on {self.device}')
-            lib, h, sp = self.lib, self._h, vp(s.cuda_stream)
-            rc = lib.cc4_stream_wait(h, sp) or lib.cc4_reward_terms_device(h, bp, cap, ip, n, vp(terms.data_ptr()), vp(words.data_ptr()))
-            if rc:
-                self.venv._chk(rc, 'cc4_reward_terms_device')
-            self.venv._chk(lib.cc4_stream_signal(h, sp), 'cc4_stream_signal')
-        return terms, words
+        return self._view('cc4_reward_terms_device', ids, bank, out, (((L.REWARD_SUBNETS, L.REWARD_COLS), torch.int32, 16), ((L.REWARD_WORDS,), torch.int32, 16)))
 
     def enable_reward_terms(self, on=True):
         """CC4VecEnv.enable_reward_terms (cc4_enable_reward_terms): record the pieces of every step's reward, which reward_terms() turns into

@@ -441,38 +441,52 @@ class CC4VecEnv:
         raise_on_copy_faults(faults.value)
         return self._check_err()[0]
 
-    def state_features(self, env_ids=None):
-        """The privileged global state of the batch (cc4_state_features_device, include/cc4.h; columns and words: state_features.HOST_COLUMNS /
-        GLOBAL_WORDS): (hosts [n, 137, 16] uint8, glob [n, 32] int32) of episodes env_ids (None: all), as NumPy arrays.  Synchronises, like
-        the other getters.  An index out of range gives an all-zero row and raises CC4EngineError after the call."""
-        ids = None if env_ids is None else np.ascontiguousarray(env_ids, dtype=np.int32).ravel()
+    def _view(self, entry, ids, outs, *extra):
+        """What the NumPy getters of the derived views share.  entry: the cc4_*_device entry point; ids: episodes (None: all); outs: (shape of one
+        entry, dtype, the fill of the view's empty output) of its two arrays; extra: arguments in front of the two output pointers.  One device
+        allocation [ids | first | second], every part aligned as the entry point asks, the call, a synchronise like the other getters, two copies
+        down.  An index out of range leaves the empty output in its row and raises CC4EngineError after the call."""
+        ids = None if ids is None else np.ascontiguousarray(ids, dtype=np.int32).ravel()
         n = self.num_envs if ids is None else int(ids.size)
-        hosts = np.zeros((n, L.FEAT_HOSTS, L.FEAT_PER_HOST), np.uint8)
-        glob = np.zeros((n, L.FEAT_GLOBAL), np.int32)
+        a, b = (np.full((n,) + tuple(shape), fill, dtype) for shape, dtype, fill in outs)
         if n == 0:
-            return hosts, glob
+            return a, b
         hip, vp = _hip(), ctypes.c_void_p
-        b_ids = ((4 * n + 15) & ~15) if ids is not None else 0          # [ids | hosts | glob]: every part 16-byte aligned
+        b_ids = ((4 * n + 15) & ~15) if ids is not None else 0
         _hip_chk(hip.hipSetDevice(self._dev), 'hipSetDevice')
         d = vp()
-        _hip_chk(hip.hipMalloc(ctypes.byref(d), b_ids + hosts.nbytes + glob.nbytes), 'hipMalloc')
+        _hip_chk(hip.hipMalloc(ctypes.byref(d), b_ids + a.nbytes + b.nbytes), 'hipMalloc')
         try:
             if ids is not None:
                 _hip_chk(hip.hipMemcpy(d, ids.ctypes.data_as(vp), ids.nbytes, 1), 'hipMemcpy')
-            d_hosts, d_glob = vp(d.value + b_ids), vp(d.value + b_ids + hosts.nbytes)
-            rc = self.lib.cc4_state_features_device(self._h, None, 0, d if ids is not None else None, n, d_hosts, d_glob)
+            d_a, d_b = vp(d.value + b_ids), vp(d.value + b_ids + a.nbytes)
+            rc = getattr(self.lib, entry)(self._h, None, 0, d if ids is not None else None, n, *extra, d_a, d_b)
             rc2 = self.lib.cc4_synchronize(self._h)
             if rc or rc2:
-                self._chk(rc or rc2, 'cc4_state_features_device')
-            _hip_chk(hip.hipMemcpy(hosts.ctypes.data_as(vp), d_hosts, hosts.nbytes, 2), 'hipMemcpy')
-            _hip_chk(hip.hipMemcpy(glob.ctypes.data_as(vp), d_glob, glob.nbytes, 2), 'hipMemcpy')
+                self._chk(rc or rc2, entry)
+            _hip_chk(hip.hipMemcpy(a.ctypes.data_as(vp), d_a, a.nbytes, 2), 'hipMemcpy')
+            _hip_chk(hip.hipMemcpy(b.ctypes.data_as(vp), d_b, b.nbytes, 2), 'hipMemcpy')
         finally:
             hip.hipFree(d)
         if ids is not None and ((ids < 0) | (ids >= self.num_envs)).any():
             faults = ctypes.c_uint32(0)
             self._chk(self.lib.cc4_copy_faults(self._h, ctypes.byref(faults)), 'cc4_copy_faults')
             raise_on_copy_faults(faults.value)
-        return hosts, glob
+        return a, b
+
+    def _view_device(self, entry, d_a, d_b, n, d_ids, d_bank, capacity, *extra):
+        """The *_device forms of the views: the entry point on device addresses of the caller's (int or ctypes.c_void_p).  Enqueued, no host wait."""
+        vp = ctypes.c_void_p
+        as_p = lambda x: x if x is None or isinstance(x, vp) else vp(int(x))      # noqa: E731
+        rc = getattr(self.lib, entry)(self._h, as_p(d_bank), int(capacity), as_p(d_ids), self.num_envs if n is None else int(n), *extra, as_p(d_a), as_p(d_b))
+        if rc:
+            self._chk(rc, entry)
+
+    def state_features(self, env_ids=None):
+        """The privileged global state of the batch (cc4_state_features_device, include/cc4.h; columns and words: state_features.HOST_COLUMNS /
+        GLOBAL_WORDS): (hosts [n, 137, 16] uint8, glob [n, 32] int32) of episodes env_ids (None: all), as NumPy arrays.  Synchronises, like
+        the other getters.  An index out of range gives an all-zero row and raises CC4EngineError after the call."""
+        return self._view('cc4_state_features_device', env_ids, (((L.FEAT_HOSTS, L.FEAT_PER_HOST), np.uint8, 0), ((L.FEAT_GLOBAL,), np.int32, 0)))
 
     def step_red_device(self, d_actions, d_messages, d_red):
         """cc4_step_red_device: a step with the blue indices [N, 5] int32, the messages [N, 5, 8] bytes (or None) and the red actions
@@ -488,101 +502,34 @@ class CC4VecEnv:
         """cc4_red_view_device into device memory of the caller's (device addresses): hosts [n, 6, 137, 8] uint8, 16-byte aligned, scalars
         [n, 6, 16] int32 or None, of episodes d_ids (int32 [n] on the device; None: 0 .. n-1) of the env or of the slots of a snapshot bank.
         Enqueued, no host wait."""
-        vp = ctypes.c_void_p
-        as_p = lambda x: x if x is None or isinstance(x, vp) else vp(int(x))      # noqa: E731
-        rc = self.lib.cc4_red_view_device(self._h, as_p(d_bank), int(capacity), as_p(d_ids), self.num_envs if n is None else int(n),
-                                          as_p(d_hosts), as_p(d_scalars))
-        if rc:
-            self._chk(rc, 'cc4_red_view_device')
+        self._view_device('cc4_red_view_device', d_hosts, d_scalars, n, d_ids, d_bank, capacity)
 
     def red_view(self, env_ids=None):
         """What each red agent knows (cc4_red_view_device, include/cc4.h; columns and words: red_view.HOST_COLUMNS / SCALAR_WORDS):
         (hosts [n, 6, 137, 8] uint8, scalars [n, 6, 16] int32) of episodes env_ids (None: all), as NumPy arrays.  Synchronises, like the other
         getters.  An index out of range gives all-zero rows and raises CC4EngineError after the call."""
-        ids = None if env_ids is None else np.ascontiguousarray(env_ids, dtype=np.int32).ravel()
-        n = self.num_envs if ids is None else int(ids.size)
-        hosts = np.zeros((n, L.NUM_RED, L.RED_VIEW_HOSTS, L.RED_VIEW_PER_HOST), np.uint8)
-        scal = np.zeros((n, L.NUM_RED, L.RED_VIEW_SCALARS), np.int32)
-        if n == 0:
-            return hosts, scal
-        hip, vp = _hip(), ctypes.c_void_p
-        b_ids = ((4 * n + 15) & ~15) if ids is not None else 0          # [ids | hosts | scalars]: every part 16-byte aligned
-        _hip_chk(hip.hipSetDevice(self._dev), 'hipSetDevice')
-        d = vp()
-        _hip_chk(hip.hipMalloc(ctypes.byref(d), b_ids + hosts.nbytes + scal.nbytes), 'hipMalloc')
-        try:
-            if ids is not None:
-                _hip_chk(hip.hipMemcpy(d, ids.ctypes.data_as(vp), ids.nbytes, 1), 'hipMemcpy')
-            d_hosts, d_scal = vp(d.value + b_ids), vp(d.value + b_ids + hosts.nbytes)
-            rc = self.lib.cc4_red_view_device(self._h, None, 0, d if ids is not None else None, n, d_hosts, d_scal)
-            rc2 = self.lib.cc4_synchronize(self._h)
-            if rc or rc2:
-                self._chk(rc or rc2, 'cc4_red_view_device')
-            _hip_chk(hip.hipMemcpy(hosts.ctypes.data_as(vp), d_hosts, hosts.nbytes, 2), 'hipMemcpy')
-            _hip_chk(hip.hipMemcpy(scal.ctypes.data_as(vp), d_scal, scal.nbytes, 2), 'hipMemcpy')
-        finally:
-            hip.hipFree(d)
-        if ids is not None and ((ids < 0) | (ids >= self.num_envs)).any():
-            faults = ctypes.c_uint32(0)
-            self._chk(self.lib.cc4_copy_faults(self._h, ctypes.byref(faults)), 'cc4_copy_faults')
-            raise_on_copy_faults(faults.value)
-        return hosts, scal
+        return self._view('cc4_red_view_device', env_ids, (((L.NUM_RED, L.RED_VIEW_HOSTS, L.RED_VIEW_PER_HOST), np.uint8, 0),
+                                                          ((L.NUM_RED, L.RED_VIEW_SCALARS), np.int32, 0)))
 
     def blue_view_device(self, d_hosts, d_scalars=None, n=None, d_ids=None, d_bank=None, capacity=0):
         """cc4_blue_view_device into device memory of the caller's (device addresses): hosts [n, 5, 137, 8] uint8, 8-byte aligned, scalars
         [n, 5, 16] int32 or None, of episodes d_ids (int32 [n] on the device; None: 0 .. n-1) of the env or of the slots of a snapshot bank.
         Enqueued, no host wait."""
-        vp = ctypes.c_void_p
-        as_p = lambda x: x if x is None or isinstance(x, vp) else vp(int(x))      # noqa: E731
-        rc = self.lib.cc4_blue_view_device(self._h, as_p(d_bank), int(capacity), as_p(d_ids), self.num_envs if n is None else int(n),
-                                           as_p(d_hosts), as_p(d_scalars))
-        if rc:
-            self._chk(rc, 'cc4_blue_view_device')
+        self._view_device('cc4_blue_view_device', d_hosts, d_scalars, n, d_ids, d_bank, capacity)
 
     def blue_view(self, env_ids=None):
         """Blue's own knowledge (cc4_blue_view_device, include/cc4.h; columns and words: blue_view.HOST_COLUMNS / SCALAR_WORDS):
         (hosts [n, 5, 137, 8] uint8, scalars [n, 5, 16] int32) of episodes env_ids (None: all), as NumPy arrays.  Synchronises, like the other
         getters.  The event columns need enable_event_log(); scalars[..., 10] says whether they are filled.  An index out of range gives
         all-zero rows and raises CC4EngineError after the call."""
-        ids = None if env_ids is None else np.ascontiguousarray(env_ids, dtype=np.int32).ravel()
-        n = self.num_envs if ids is None else int(ids.size)
-        hosts = np.zeros((n, L.NUM_BLUE, L.BLUE_VIEW_HOSTS, L.BLUE_VIEW_PER_HOST), np.uint8)
-        scal = np.zeros((n, L.NUM_BLUE, L.BLUE_VIEW_SCALARS), np.int32)
-        if n == 0:
-            return hosts, scal
-        hip, vp = _hip(), ctypes.c_void_p
-        b_ids = ((4 * n + 15) & ~15) if ids is not None else 0          # [ids | hosts | scalars]: every part 8-byte aligned
-        _hip_chk(hip.hipSetDevice(self._dev), 'hipSetDevice')
-        d = vp()
-        _hip_chk(hip.hipMalloc(ctypes.byref(d), b_ids + hosts.nbytes + scal.nbytes), 'hipMalloc')
-        try:
-            if ids is not None:
-                _hip_chk(hip.hipMemcpy(d, ids.ctypes.data_as(vp), ids.nbytes, 1), 'hipMemcpy')
-            d_hosts, d_scal = vp(d.value + b_ids), vp(d.value + b_ids + hosts.nbytes)
-            rc = self.lib.cc4_blue_view_device(self._h, None, 0, d if ids is not None else None, n, d_hosts, d_scal)
-            rc2 = self.lib.cc4_synchronize(self._h)
-            if rc or rc2:
-                self._chk(rc or rc2, 'cc4_blue_view_device')
-            _hip_chk(hip.hipMemcpy(hosts.ctypes.data_as(vp), d_hosts, hosts.nbytes, 2), 'hipMemcpy')
-            _hip_chk(hip.hipMemcpy(scal.ctypes.data_as(vp), d_scal, scal.nbytes, 2), 'hipMemcpy')
-        finally:
-            hip.hipFree(d)
-        if ids is not None and ((ids < 0) | (ids >= self.num_envs)).any():
-            faults = ctypes.c_uint32(0)
-            self._chk(self.lib.cc4_copy_faults(self._h, ctypes.byref(faults)), 'cc4_copy_faults')
-            raise_on_copy_faults(faults.value)
-        return hosts, scal
+        return self._view('cc4_blue_view_device', env_ids, (((L.NUM_BLUE, L.BLUE_VIEW_HOSTS, L.BLUE_VIEW_PER_HOST), np.uint8, 0),
+                                                           ((L.NUM_BLUE, L.BLUE_VIEW_SCALARS), np.int32, 0)))
 
     def blue_edges_device(self, d_edges, d_counts=None, n=None, d_ids=None, d_bank=None, capacity=0, max_edges=L.BLUE_EDGES_MAX):
         """cc4_blue_edges_device into device memory of the caller's (device addresses): edges [n, max_edges, 8] int32, 16-byte aligned, counts
         [n, 8] int32 or None, of episodes d_ids (int32 [n] on the device; None: 0 .. n-1) of the env or of the slots of a snapshot bank.
         Enqueued, no host wait."""
-        vp = ctypes.c_void_p
-        as_p = lambda x: x if x is None or isinstance(x, vp) else vp(int(x))      # noqa: E731
-        rc = self.lib.cc4_blue_edges_device(self._h, as_p(d_bank), int(capacity), as_p(d_ids), self.num_envs if n is None else int(n),
-                                            int(max_edges), as_p(d_edges), as_p(d_counts))
-        if rc:
-            self._chk(rc, 'cc4_blue_edges_device')
+        self._view_device('cc4_blue_edges_device', d_edges, d_counts, n, d_ids, d_bank, capacity, int(max_edges))
 
     def blue_edges(self, ids=None, max_edges=L.BLUE_EDGES_MAX):
         """The Monitor's connection entries of the step just taken as edge lists (cc4_blue_edges_device, include/cc4.h; columns and words:
@@ -594,34 +541,7 @@ class CC4VecEnv:
         max_edges = int(max_edges)
         if not 1 <= max_edges <= L.BLUE_EDGES_MAX:
             raise ValueError(f'max_edges must be 1 .. {L.BLUE_EDGES_MAX}, got {max_edges}')
-        ids = None if ids is None else np.ascontiguousarray(ids, dtype=np.int32).ravel()
-        n = self.num_envs if ids is None else int(ids.size)
-        edges = np.full((n, max_edges, L.BLUE_EDGES_COLUMNS), -1, np.int32)
-        counts = np.zeros((n, L.BLUE_EDGES_WORDS), np.int32)
-        if n == 0:
-            return edges, counts
-        hip, vp = _hip(), ctypes.c_void_p
-        b_ids = ((4 * n + 15) & ~15) if ids is not None else 0          # [ids | edges | counts]: every part 16-byte aligned
-        _hip_chk(hip.hipSetDevice(self._dev), 'hipSetDevice')
-        d = vp()
-        _hip_chk(hip.hipMalloc(ctypes.byref(d), b_ids + edges.nbytes + counts.nbytes), 'hipMalloc')
-        try:
-            if ids is not None:
-                _hip_chk(hip.hipMemcpy(d, ids.ctypes.data_as(vp), ids.nbytes, 1), 'hipMemcpy')
-            d_edges, d_counts = vp(d.value + b_ids), vp(d.value + b_ids + edges.nbytes)
-            rc = self.lib.cc4_blue_edges_device(self._h, None, 0, d if ids is not None else None, n, max_edges, d_edges, d_counts)
-            rc2 = self.lib.cc4_synchronize(self._h)
-            if rc or rc2:
-                self._chk(rc or rc2, 'cc4_blue_edges_device')
-            _hip_chk(hip.hipMemcpy(edges.ctypes.data_as(vp), d_edges, edges.nbytes, 2), 'hipMemcpy')
-            _hip_chk(hip.hipMemcpy(counts.ctypes.data_as(vp), d_counts, counts.nbytes, 2), 'hipMemcpy')
-        finally:
-            hip.hipFree(d)
-        if ids is not None and ((ids < 0) | (ids >= self.num_envs)).any():
-            faults = ctypes.c_uint32(0)
-            self._chk(self.lib.cc4_copy_faults(self._h, ctypes.byref(faults)), 'cc4_copy_faults')
-            raise_on_copy_faults(faults.value)
-        return edges, counts
+        return self._view('cc4_blue_edges_device', ids, (((max_edges, L.BLUE_EDGES_COLUMNS), np.int32, -1), ((L.BLUE_EDGES_WORDS,), np.int32, 0)), max_edges)
 
     def enable_reward_terms(self, on=True):
         """cc4_enable_reward_terms: record the pieces of every step's reward (reward_terms()).  The env then runs the full builds of its step
@@ -637,46 +557,14 @@ class CC4VecEnv:
         """cc4_reward_terms_device into device memory of the caller's (device addresses): terms [n, 9, 4] int32 and words [n, 16] int32 (or None),
         both 16-byte aligned, of episodes d_ids (int32 [n] on the device; None: 0 .. n-1) of the env or of the slots of a snapshot bank.
         Enqueued, no host wait."""
-        vp = ctypes.c_void_p
-        as_p = lambda x: x if x is None or isinstance(x, vp) else vp(int(x))      # noqa: E731
-        rc = self.lib.cc4_reward_terms_device(self._h, as_p(d_bank), int(capacity), as_p(d_ids), self.num_envs if n is None else int(n),
-                                              as_p(d_terms), as_p(d_words))
-        if rc:
-            self._chk(rc, 'cc4_reward_terms_device')
+        self._view_device('cc4_reward_terms_device', d_terms, d_words, n, d_ids, d_bank, capacity)
 
     def reward_terms(self, ids=None):
         """Why the last step's reward was what it was (cc4_reward_terms_device, include/cc4.h; columns and words: reward_terms.TERM_COLUMNS /
         WORDS): (terms [n, 9, 4] int32, words [n, 16] int32) of episodes ids (None: all), as NumPy arrays.  Synchronises, like the other
         getters.  words[:, 0] says whether the last step recorded (enable_reward_terms(), or an env that steps with red / green actions).  An
         index out of range gives all-zero rows and raises CC4EngineError after the call."""
-        ids = None if ids is None else np.ascontiguousarray(ids, dtype=np.int32).ravel()
-        n = self.num_envs if ids is None else int(ids.size)
-        terms = np.zeros((n, L.REWARD_SUBNETS, L.REWARD_COLS), np.int32)
-        words = np.zeros((n, L.REWARD_WORDS), np.int32)
-        if n == 0:
-            return terms, words
-        hip, vp = _hip(), ctypes.c_void_p
-        b_ids = ((4 * n + 15) & ~15) if ids is not None else 0          # [ids | terms | words]: every part 16-byte aligned (144 n, 64 n)
-        _hip_chk(hip.hipSetDevice(self._dev), 'hipSetDevice')
-        d = vp()
-        _hip_chk(hip.hipMalloc(ctypes.byref(d), b_ids + terms.nbytes + words.nbytes), 'hipMalloc')
-        try:
-            if ids is not None:
-                _hip_chk(hip.hipMemcpy(d, ids.ctypes.data_as(vp), ids.nbytes, 1), 'hipMemcpy')
-            d_terms, d_words = vp(d.value + b_ids), vp(d.value + b_ids + terms.nbytes)
-            rc = self.lib.cc4_reward_terms_device(self._h, None, 0, d if ids is not None else None, n, d_terms, d_words)
-            rc2 = self.lib.cc4_synchronize(self._h)
-            if rc or rc2:
-                self._chk(rc or rc2, 'cc4_reward_terms_device')
-            _hip_chk(hip.hipMemcpy(terms.ctypes.data_as(vp), d_terms, terms.nbytes, 2), 'hipMemcpy')
-            _hip_chk(hip.hipMemcpy(words.ctypes.data_as(vp), d_words, words.nbytes, 2), 'hipMemcpy')
-        finally:
-            hip.hipFree(d)
-        if ids is not None and ((ids < 0) | (ids >= self.num_envs)).any():
-            faults = ctypes.c_uint32(0)
-            self._chk(self.lib.cc4_copy_faults(self._h, ctypes.byref(faults)), 'cc4_copy_faults')
-            raise_on_copy_faults(faults.value)
-        return terms, words
+        return self._view('cc4_reward_terms_device', ids, (((L.REWARD_SUBNETS, L.REWARD_COLS), np.int32, 0), ((L.REWARD_WORDS,), np.int32, 0)))
 
     def plan_kernel_for(self, k):
         """cc4_plan_kernel_for: the kernel a run_plan / step_plan call of k steps launches ('k_run_philox1p' / 'k_run_pcgp': one launch for the

@@ -16,7 +16,7 @@ import capacity_util
 import golden_util
 from cage_challenge_4_amd import blue_edges as BE
 from oracle_binding import OracleVecEnv, random_actions
-from test_state_features import DevMem, _dev, _faults
+from view_util import DevMem, _dev, _faults, call_view
 
 pytestmark = pytest.mark.gpu
 
@@ -29,20 +29,9 @@ assert EVREC.itemsize == 12
 
 def _edges(dev, n, E=160, ids=None, bank=None, cap=0, fill=0, counts=True):
     """cc4_blue_edges_device into a fresh device buffer [edges | counts], then synchronise and copy down."""
-    buf = DevMem(n * (E * 32 + 32), fill)
-    assert buf.hip.hipDeviceSynchronize() == 0          # the fill runs on the null stream, the kernel on the handle's: the fill first
-    d_ids = None
-    if ids is not None:
-        d_ids = DevMem(4 * max(len(ids), 1))
-        d_ids.up(np.asarray(ids, np.int32))
-    dev.blue_edges_device(buf.p, buf.at(n * E * 32) if counts else None, n=n, d_ids=d_ids.p if d_ids else None,
-                          d_bank=bank.p if bank is not None else None, capacity=cap, max_edges=E)
-    dev.synchronize()
-    edges, cnt = buf.down(np.int32, (n, E, 8)), buf.down(np.int32, (n, 8), n * E * 32)
-    if d_ids:
-        d_ids.free()
-    buf.free()
-    return edges, cnt
+    def call(d_bank, cap, d_ids, n, p_edges, p_counts):
+        dev.blue_edges_device(p_edges, p_counts, n=n, d_ids=d_ids, d_bank=d_bank, capacity=cap, max_edges=E)
+    return call_view(dev, call, n, ((np.int32, (E, 8)), (np.int32, (8,))), ids, bank, cap, fill, second=counts)
 
 
 def _from_rows(env, episodes, steps, E=160):

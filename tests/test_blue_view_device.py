@@ -13,7 +13,7 @@ import blue_util as BU
 import golden_util
 from cage_challenge_4_amd import blue_view as BV
 from oracle_binding import random_actions
-from test_state_features import DevMem, _dev, _faults
+from view_util import DevMem, _dev, _faults, call_view
 
 pytestmark = pytest.mark.gpu
 
@@ -24,19 +24,9 @@ CF_RANGE, CF_SLOT_EMPTY = 1, 8
 
 def _view(dev, n, ids=None, bank=None, cap=0, fill=0, scalars=True):
     """cc4_blue_view_device into a fresh device buffer [hosts | scalars], then synchronise and copy down."""
-    buf = DevMem(n * (ROW_H + ROW_S), fill)
-    d_ids = None
-    if ids is not None:
-        d_ids = DevMem(4 * max(len(ids), 1))
-        d_ids.up(np.asarray(ids, np.int32))
-    dev.blue_view_device(buf.p, buf.at(n * ROW_H) if scalars else None, n=n, d_ids=d_ids.p if d_ids else None,
-                         d_bank=bank.p if bank is not None else None, capacity=cap)
-    dev.synchronize()
-    hosts, scal = buf.down(np.uint8, (n, 5, 137, 8)), buf.down(np.int32, (n, 5, 16), n * ROW_H)
-    if d_ids:
-        d_ids.free()
-    buf.free()
-    return hosts, scal
+    def call(d_bank, cap, d_ids, n, p_hosts, p_scal):
+        dev.blue_view_device(p_hosts, p_scal, n=n, d_ids=d_ids, d_bank=d_bank, capacity=cap)
+    return call_view(dev, call, n, ((np.uint8, (5, 137, 8)), (np.int32, (5, 16))), ids, bank, cap, fill, second=scalars)
 
 
 def _from_rows(dev, episodes, steps):

@@ -154,7 +154,7 @@ def test_copies_and_features_of_full_containers():
     """clone / save / load of every at-capacity episode: the destination's hot row and the live extents of its cold row are the source's -- to the
     last entry of a full list --, the episodes behind the destinations are untouched; k_state_features strides over a full pool."""
     from cage_challenge_4_amd import state_features as SF
-    from test_state_features import DevMem
+    from view_util import DevMem
     mode = 1
     caps_ = [sc for sc in U.SCENARIOS if sc.endswith(':cap')] + ['proc_pin:over', 'proc_pin:m1']
     m = len(caps_)

@@ -11,7 +11,7 @@ from cage_challenge_4_amd import reward_terms as RT
 from oracle_binding import OracleVecEnv
 import reward_terms_util as U
 import test_scripted as TS
-from test_state_features import DevMem, _dev, _faults
+from view_util import DevMem, _dev, _faults, call_view
 
 pytestmark = pytest.mark.gpu
 
@@ -30,19 +30,9 @@ def _make(kernel, mode, lean, monkeypatch, n, **kw):
 
 def _view(dev, n, ids=None, bank=None, cap=0, fill=0, words=True):
     """cc4_reward_terms_device into a fresh device buffer [terms | words], then synchronise and copy down."""
-    buf = DevMem(n * (ROW_T + ROW_W), fill)
-    d_ids = None
-    if ids is not None:
-        d_ids = DevMem(4 * max(len(ids), 1))
-        d_ids.up(np.asarray(ids, np.int32))
-    dev.reward_terms_device(buf.p, buf.at(n * ROW_T) if words else None, n=n, d_ids=d_ids.p if d_ids else None,
-                            d_bank=bank.p if bank is not None else None, capacity=cap)
-    dev.synchronize()
-    terms, wd = buf.down(np.int32, (n, 9, 4)), buf.down(np.int32, (n, 16), n * ROW_T)
-    if d_ids:
-        d_ids.free()
-    buf.free()
-    return terms, wd
+    def call(d_bank, cap, d_ids, n, p_terms, p_words):
+        dev.reward_terms_device(p_terms, p_words, n=n, d_ids=d_ids, d_bank=d_bank, capacity=cap)
+    return call_view(dev, call, n, ((np.int32, (9, 4)), (np.int32, (16,))), ids, bank, cap, fill, second=words)
 
 
 @pytest.mark.parametrize('kernel,mode,lean', KERNELS, ids=[k[0] for k in KERNELS])

@@ -9,8 +9,8 @@ import pytest
 
 from cage_challenge_4_amd import state_features as SF
 from cage_challenge_4_amd import true_state as T
-from cage_challenge_4_amd.vec_env import _hip
 from oracle_binding import OracleVecEnv, random_actions
+from view_util import DevMem, _dev, _faults, call_view
 
 pytestmark = pytest.mark.gpu
 
@@ -20,63 +20,11 @@ SE_ADD_RED_SESSION, SE_SET_RED_ACTIVE = 5, 9
 CF_RANGE, CF_SLOT_EMPTY, CF_SLOT_CONFIG = 1, 8, 16
 
 
-class DevMem:
-    """A device allocation through the HIP runtime libcc4.so is linked against (no torch in this file)."""
-
-    def __init__(self, nbytes, fill=0):
-        self.hip, self.nbytes, self.p = _hip(), int(nbytes), VP()
-        self.hip.hipMemset.argtypes, self.hip.hipMemset.restype = [VP, ctypes.c_int, ctypes.c_size_t], ctypes.c_int
-        assert self.hip.hipMalloc(ctypes.byref(self.p), max(self.nbytes, 16)) == 0
-        assert self.hip.hipMemset(self.p, fill, max(self.nbytes, 16)) == 0
-
-    def at(self, off):
-        assert 0 <= off <= self.nbytes
-        return VP(self.p.value + off)
-
-    def up(self, arr, off=0):
-        arr = np.ascontiguousarray(arr)
-        assert off + arr.nbytes <= self.nbytes
-        assert self.hip.hipMemcpy(self.at(off), arr.ctypes.data_as(VP), arr.nbytes, 1) == 0
-
-    def down(self, dtype, shape, off=0):
-        out = np.zeros(shape, dtype)
-        assert off + out.nbytes <= self.nbytes
-        assert self.hip.hipMemcpy(out.ctypes.data_as(VP), self.at(off), out.nbytes, 2) == 0
-        return out
-
-    def free(self):
-        if self.p:
-            self.hip.hipFree(self.p)
-            self.p = VP()
-
-
-def _dev(n, **kw):
-    from cage_challenge_4_amd import CC4VecEnv
-    return CC4VecEnv(n, **kw)
-
-
 def _features(dev, n, ids=None, bank=None, cap=0, out=None, fill=0):
     """cc4_state_features_device into a fresh (or the given) device buffer [hosts | glob], then synchronise and copy down."""
-    buf = out or DevMem(n * (ROW_H + ROW_G), fill)
-    d_ids = None
-    if ids is not None:
-        d_ids = DevMem(4 * max(len(ids), 1))
-        d_ids.up(np.asarray(ids, np.int32))
-    rc = dev.lib.cc4_state_features_device(dev._h, bank.p if bank is not None else None, cap, d_ids.p if d_ids else None, n, buf.p, buf.at(n * ROW_H))
-    assert rc == 0, dev.lib.cc4_last_error(dev._h)
-    dev.synchronize()
-    hosts, glob = buf.down(np.uint8, (n, 137, 16)), buf.down(np.int32, (n, 32), n * ROW_H)
-    if d_ids:
-        d_ids.free()
-    if out is None:
-        buf.free()
-    return hosts, glob
-
-
-def _faults(dev):
-    f = ctypes.c_uint32(0)
-    dev._chk(dev.lib.cc4_copy_faults(dev._h, ctypes.byref(f)), 'cc4_copy_faults')
-    return f.value
+    def call(d_bank, cap, d_ids, n, p_hosts, p_glob):
+        assert dev.lib.cc4_state_features_device(dev._h, d_bank, cap, d_ids, n, p_hosts, p_glob) == 0, dev.lib.cc4_last_error(dev._h)
+    return call_view(dev, call, n, ((np.uint8, (137, 16)), (np.int32, (32,))), ids, bank, cap, fill, out)
 
 
 def _from_rows(rows):
