@@ -1,7 +1,7 @@
 // cc4_api_views.hip -- the host side of libcc4.so: the derived views, which read tensors out of the batch without stepping it -- state features, the
-// red agents' view, blue's own knowledge, the Monitor's connections as edge lists, reward terms (include/cc4.h; the kernels: cc4_k_feat.hip,
-// cc4_k_red.hip, cc4_k_blue.hip, cc4_k_edges.hip, cc4_k_reward.hip; the definitions: cc4_features.h, cc4_red_view.h, cc4_blue_view.h, cc4_blue_edges.h,
-// cc4_reward_terms.h).  Every view has a device entry point and the same definition on the host from one row; the call shape of the device entry
+// red agents' view, blue's own knowledge, the Monitor's connections as edge lists, reward terms, blue actions sampled from policy logits (include/cc4.h;
+// the kernels: cc4_k_feat.hip, cc4_k_red.hip, cc4_k_blue.hip, cc4_k_edges.hip, cc4_k_reward.hip, cc4_k_sample.hip; the definitions: cc4_features.h,
+// cc4_red_view.h, cc4_blue_view.h, cc4_blue_edges.h, cc4_reward_terms.h, cc4_sample.h).  Every view has a device entry point and the same definition on the host from one row; the call shape of the device entry
 // points is stated at ViewSrc (cc4_args.h) and implemented once here: view_check, view_launch.
 #include "cc4_host.h"
 #include "cc4_features.h"
@@ -9,6 +9,7 @@
 #include "cc4_blue_view.h"
 #include "cc4_blue_edges.h"
 #include "cc4_reward_terms.h"
+#include "cc4_sample.h"
 
 // ---- the device entry points.  One launch on the main stream behind the group streams, no host synchronisation; a view only reads rows -- as the
 // last step left them -- so the next step launches need no ordering behind it beyond the main stream's own.
@@ -67,6 +68,21 @@ int cc4_reward_terms_device(cc4_handle* h, const void* d_bank, int32_t capacity,
   const int rc = view_check(h, "cc4_reward_terms_device", nullptr, n, d_terms, 16, d_words, 16,
                             "the terms buffer is required and must be 16-byte aligned (the words: 16-byte aligned or NULL)", d_bank, capacity);
   return rc == VIEW_GO ? view_launch(h, k_reward_terms, d_bank, capacity, d_ids, n, d_terms, d_words) : rc;
+}
+// of the hot rows exists and the agents' busy bytes; beside the rows one input, the logits.  The refusals of its own, in their order:
+static const char* sample_bad(int32_t dtype, const void* logits, float temperature, int32_t flags) {
+  if (dtype < 1 || dtype > 3) return "logits_dtype must be 1 (float16), 2 (bfloat16) or 3 (float32)";
+  if (!(temperature > 0.0f) || !std::isfinite(temperature)) return "the temperature must be finite and positive";
+  if (flags & ~(int32_t)SA_FLAGS) return "unknown flag bits (CC4_SAMPLE_GREEDY | CC4_SAMPLE_BUSY)";
+  if (reinterpret_cast<uintptr_t>(logits) % 4) return "the logits must be 4-byte aligned";
+  return nullptr;
+}
+int cc4_sample_actions_device(cc4_handle* h, const void* d_bank, int32_t capacity, const int32_t* d_ids, int32_t n, int32_t logits_dtype, const void* d_logits,
+                              uint64_t seed0, uint32_t t, float temperature, int32_t flags, int32_t* d_actions, float* d_stats) {
+  const int rc = view_check(h, "cc4_sample_actions_device", sample_bad(logits_dtype, d_logits, temperature, flags), n, d_actions, 4, d_stats, 4,
+                            "the action buffer is required and must be 4-byte aligned (the stats: 4-byte aligned or NULL)", d_bank, capacity);
+  return rc == VIEW_GO ? view_launch(h, k_sample_actions, d_bank, capacity, d_ids, n, d_logits, (int)logits_dtype, seed0, t, 1.0f / temperature, (int)flags,
+                                     d_actions, d_stats) : rc;
 }
 
 // The switch of the reward record: the handle behaves as after a cc4_step_red_device whose records were all "the scripted class acts" -- d_ext filled with
@@ -164,4 +180,16 @@ int cc4_reward_terms_from_row(const void* hot_row, const void* cold_row, int32_t
   if (int rc = row_copies(r, hot_row, cold_row, &steps, RC_RWD)) return rc;
   reward_terms_from_row(r.s, r.rwd, terms, words);
   return 0;
+}
+// 0, 1 (the logits refused some agent: cc4_sample.h), -2
+int cc4_sample_actions_from_row(const void* hot_row, const float* logits, uint64_t seed0, uint32_t t, int32_t e, float temperature, int32_t flags,
+                                int32_t* actions, float* stats) {
+  if (!hot_row || !actions || sample_bad(3, nullptr, temperature, flags)) return -2;
+  RowCopy r;
+  if (int rc = row_copies(r, hot_row, nullptr, nullptr, 0)) return rc;
+  float* l = nullptr;                                                      // (the caller's logits may sit at any address)
+  if (logits && !(l = static_cast<float*>(row_copy(logits, sizeof(float) * SA_SLOTS, 16)))) return -1;
+  const int refused = sample_from_row(r.s, l, seed0, t, e, 1.0f / temperature, flags, actions, stats);
+  free(l);
+  return refused ? 1 : 0;
 }

@@ -1,5 +1,5 @@
 // cc4_args.h -- what the host side and the kernels of libcc4.so share: the constants, the argument blocks of the kernels (StepArgs, XchgArgs, RunArgs,
-// PlanArgs, ResetArgs, CopyArgs, RedSubmitArgs, and ViewSrc with the five view blocks FeatArgs, RedViewArgs, BlueViewArgs, BlueEdgesArgs, RewardArgs), the snapshot-slot layout, and the register budgets of the kernels.  No device helper (cc4_kernels.h) and nothing of
+// PlanArgs, ResetArgs, CopyArgs, RedSubmitArgs, and ViewSrc with the six view blocks FeatArgs, RedViewArgs, BlueViewArgs, BlueEdgesArgs, RewardArgs, SampleArgs), the snapshot-slot layout, and the register budgets of the kernels.  No device helper (cc4_kernels.h) and nothing of
 // the C++ host library (cc4_host.h).  The index arithmetic of the persistent schedule -- partitions, tickets, runs, the progress word -- is in cc4_sched.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -194,7 +194,8 @@ struct CopyArgs {
   uint32_t* fault;
 };
 
-// ---- the derived views (cc4_state_features_device, cc4_red_view_device, cc4_blue_view_device, cc4_blue_edges_device, cc4_reward_terms_device): kernels
+// ---- the derived views (cc4_state_features_device, cc4_red_view_device, cc4_blue_view_device, cc4_blue_edges_device, cc4_reward_terms_device,
+// cc4_sample_actions_device): kernels
 // that read tensors out of the batch without stepping it, one wavefront per entry.  Their common call shape, stated once: entry i reads episode
 // ids[i] (null: i) of the handle -- its hot row and, at cold_at(cold, e, cold_row), its cold row -- or the two rows inside slot ids[i] of a snapshot
 // bank; an index out of range, a slot that was never written or one of another configuration gives the view's empty output and raises its CF_* bit in
@@ -246,4 +247,16 @@ struct RewardArgs {
   ViewSrc src;
   int32_t* terms;                                        // [count][9][4], 16-byte aligned
   int32_t* words;                                        // [count][16], 16-byte aligned, or null
+};
+// masked sampling of the blue actions from policy logits (cc4_k_sample.hip; the definition: cc4_sample.h): of the hot row the exists bits and the agents'
+// busy bytes; beside the rows one input, the logits
+struct SampleArgs {
+  ViewSrc src;
+  const void* logits;                                    // [count][570] in dtype, row i belongs to entry i, 4-byte aligned; or null: all zero
+  int dtype;                                             // 1 float16, 2 bfloat16, 3 float32 (the codes of cc4_policy_outputs)
+  uint64_t seed0; uint32_t t;                            // the noise: Philox key seed0 + the entry's id, counter word t
+  float inv_t;                                           // 1 / temperature
+  int flags;                                             // CC4_SAMPLE_*
+  int32_t* actions;                                      // [count][5], 4-byte aligned
+  float* stats;                                          // [count][5][2] (logp, entropy) or null
 };

@@ -62,6 +62,8 @@ __global__ void k_blue_view(BlueViewArgs a);
 __global__ void k_blue_edges(BlueEdgesArgs a);
 // reward terms (cc4_k_reward.hip): one wavefront per requested episode or bank slot
 __global__ void k_reward_terms(RewardArgs a);
+// masked sampling of the blue actions from policy logits (cc4_k_sample.hip): one wavefront per requested episode or bank slot
+__global__ void k_sample_actions(SampleArgs a);
 // per-episode opponent classes (cc4_k_misc.hip): one lane per episode
 __global__ void k_set_policies(EnvState* st, const int8_t* __restrict__ red, const int8_t* __restrict__ green, const int8_t* __restrict__ blue, int n, uint32_t* fault);
 __global__ void k_get_policies(const EnvState* __restrict__ st, int8_t* __restrict__ live, int8_t* __restrict__ assigned, int n);

@@ -1,4 +1,4 @@
-// cc4_view_src.h -- the one resolver of the derived-view kernels (k_state_features, k_red_view, k_blue_view, k_blue_edges, k_reward_terms): which rows
+// cc4_view_src.h -- the one resolver of the derived-view kernels (k_state_features, k_red_view, k_blue_view, k_blue_edges, k_reward_terms, k_sample_actions): which rows
 // entry i of a call reads, or why it reads none.  The contract is stated at ViewSrc (cc4_args.h); this is its only implementation on the device.
 #pragma once
 #include "cc4_args.h"

@@ -12,6 +12,7 @@ from . import _lib as L
 from .vec_env import CC4VecEnv, raise_on_copy_faults, split_obs, split_mask  # noqa: F401  (split_obs / split_mask slice tensors too)
 
 _OBS_DTYPES = {torch.uint8: 0, torch.float16: 1, torch.bfloat16: 2, torch.float32: 3}
+_LOGIT_DTYPES = {torch.float16: 1, torch.bfloat16: 2, torch.float32: 3}      # the same codes: what sample_actions() takes
 
 
 class CC4TorchVecEnv:
@@ -70,6 +71,11 @@ class CC4TorchVecEnv:
     reward_terms(ids=None, bank=None, out=None) -> (terms [n, 9, 4] int32, words [n, 16] int32)   per subnet the LocalWork / AccessService /
                                                   Impact penalties and the number of events; brm, action cost, each blue agent's share
 
+    From policy logits to valid actions (include/cc4.h cc4_sample_actions_device; cage_challenge_4_amd.action_sampling):
+    sample_actions(logits=None, *, seed=0, t=None, temperature=1.0, greedy=False, busy_aware=True, ids=None, bank=None, out=None)
+                                                  -> (actions [n, 5] int32, stats [n, 5, 2] float32)   a policy's [n, 570] logits to the indices
+                                                  step() takes in one launch: masked, busy agents -1, logp and entropy of the draw
+
     Mixed opponents in one batch (include/cc4.h cc4_set_policies_device, cc4_reset_device):
     set_opponents(red=None, green=None, blue=None)   integer tensors [N] on the device: the classes each episode regenerates into from its next
                                                      regeneration on (never mid-episode); None keeps
@@ -100,6 +106,7 @@ class CC4TorchVecEnv:
             self._fresh = torch.zeros(n, dtype=torch.uint8, **z)     # episodes a copy overwrote since the last check_errors (strict mode: new episodes)
             self._messages = torch.zeros((n, L.NUM_BLUE, L.MSG_LEN), dtype=torch.uint8, **z)
             self._red = None         # [N, 6, 4] int32 staging of step(red_actions=...), allocated on first use
+        self._sample_t = 0           # the counter word of sample_actions(t=None)
         vp = ctypes.c_void_p
         self._p_out = (vp(self.obs.data_ptr()), vp(self.action_mask.data_ptr()), vp(self.reward.data_ptr()), vp(self.done.data_ptr()),
                        vp(self.err.data_ptr()))
@@ -360,6 +367,30 @@ class CC4TorchVecEnv:
             raise ValueError(f'max_edges must be 1 .. {L.BLUE_EDGES_MAX}, got {max_edges}')
         return self._view('cc4_blue_edges_device', ids, bank, out, (((max_edges, L.BLUE_EDGES_COLUMNS), torch.int32, 16), ((L.BLUE_EDGES_WORDS,), torch.int32, 1)),
                           max_edges)
+
+    def sample_actions(self, logits=None, *, seed=0, t=None, temperature=1.0, greedy=False, busy_aware=True, ids=None, bank=None, out=None):
+        """Valid blue actions drawn from policy logits in one launch (cc4_sample_actions_device, include/cc4.h; the definition:
+        action_sampling) as tensors on the env's device: (actions [n, 5] int32, stats [n, 5, 2] float32 -- logp, entropy).  Per agent the slots
+        this episode's topology does not have are masked out and one slot is drawn from softmax(logits / temperature) over the rest (greedy: the
+        arg-max); a busy agent (busy_aware) gets -1, "submits nothing", and zero stats -- step() takes the actions as they are.  logits: a
+        contiguous float16, bfloat16 or float32 tensor [n, 570] on the env's device, row j for entry j; None: uniform over the valid slots.
+        The noise is a fixed function of (seed, t, the entry's id, agent, slot); t=None: a counter of the env that advances by one per call.
+        ids, bank, out and the ordering on the current stream as state_features(); no host copy, no host wait.  A faulty entry gives -1 actions
+        and zero stats, an agent whose valid logits hold a NaN or +inf or are all -inf gets -1 alone; check_errors() raises CC4EngineError for
+        either."""
+        from .action_sampling import check_temperature, flags_of
+        temperature = check_temperature(temperature)
+        n = int(ids.numel()) if torch.is_tensor(ids) else (int(bank.shape[0]) if torch.is_tensor(bank) else self.num_envs)
+        code, lp = 3, None
+        if logits is not None:
+            if (not torch.is_tensor(logits) or tuple(logits.shape) != (n, L.MASK_PER_ENV) or logits.dtype not in _LOGIT_DTYPES
+                    or logits.device != self.device or not logits.is_contiguous()):
+                raise ValueError(f'logits must be a contiguous float16, bfloat16 or float32 tensor [{n}, {L.MASK_PER_ENV}] on {self.device}')
+            code, lp = _LOGIT_DTYPES[logits.dtype], ctypes.c_void_p(logits.data_ptr())
+        if t is None:
+            t, self._sample_t = self._sample_t, self._sample_t + 1
+        return self._view('cc4_sample_actions_device', ids, bank, out, (((L.NUM_BLUE,), torch.int32, 4), ((L.NUM_BLUE, 2), torch.float32, 4)),
+                          code, lp, int(seed) & (2 ** 64 - 1), int(t) & 0xFFFFFFFF, temperature, flags_of(greedy, busy_aware))
 
     def enable_event_log(self, on=True):
         """CC4VecEnv.enable_event_log (cc4_enable_event_log): record the HostEvents entries of every step, which fills the event columns of

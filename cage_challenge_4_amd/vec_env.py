@@ -543,6 +543,56 @@ class CC4VecEnv:
             raise ValueError(f'max_edges must be 1 .. {L.BLUE_EDGES_MAX}, got {max_edges}')
         return self._view('cc4_blue_edges_device', ids, (((max_edges, L.BLUE_EDGES_COLUMNS), np.int32, -1), ((L.BLUE_EDGES_WORDS,), np.int32, 0)), max_edges)
 
+    def sample_actions_device(self, d_actions, d_stats=None, d_logits=None, logits_dtype=3, seed=0, t=0, temperature=1.0, flags=L.SAMPLE_BUSY,
+                              n=None, d_ids=None, d_bank=None, capacity=0):
+        """cc4_sample_actions_device on device memory of the caller's (device addresses): logits [n, 570] in logits_dtype (1 float16, 2 bfloat16,
+        3 float32; None: uniform over the valid slots) -> actions [n, 5] int32 and stats [n, 5, 2] float32 (or None), of episodes d_ids (int32
+        [n] on the device; None: 0 .. n-1) of the env or of the slots of a snapshot bank.  Enqueued, no host wait."""
+        vp = ctypes.c_void_p
+        as_p = lambda x: x if x is None or isinstance(x, vp) else vp(int(x))      # noqa: E731
+        self._view_device('cc4_sample_actions_device', d_actions, d_stats, n, d_ids, d_bank, capacity, int(logits_dtype), as_p(d_logits),
+                          int(seed) & (2 ** 64 - 1), int(t) & 0xFFFFFFFF, float(temperature), int(flags))
+
+    def sample_actions(self, logits=None, ids=None, seed=0, t=0, temperature=1.0, greedy=False, busy_aware=True):
+        """Valid blue actions drawn from policy logits (cc4_sample_actions_device, include/cc4.h; the definition: action_sampling):
+        (actions [n, 5] int32, stats [n, 5, 2] float32 -- logp, entropy) of episodes ids (None: all), as NumPy arrays.  logits: [n, 570]
+        float16 or float32 (float64 is cast to float32; uint16 is taken as bfloat16 bit patterns), row j for entry j; None: uniform over the valid
+        slots.  The noise is a fixed function of (seed, t, episode, agent, slot).  A busy agent (busy_aware) gets -1: "submits nothing".
+        Synchronises, like the other getters.  An index out of range gives -1 actions and zero stats and raises CC4EngineError after the call,
+        as does an agent whose valid logits hold a NaN or +inf or are all -inf (only that agent is -1)."""
+        from . import action_sampling as AS
+        temperature = AS.check_temperature(temperature)
+        n = self.num_envs if ids is None else int(np.asarray(ids).size)
+        extra = lambda dt, p: (dt, p, int(seed) & (2 ** 64 - 1), int(t) & 0xFFFFFFFF, temperature, AS.flags_of(greedy, busy_aware))      # noqa: E731
+        outs = (((L.NUM_BLUE,), np.int32, -1), ((L.NUM_BLUE, 2), np.float32, 0))
+        if logits is None:
+            a, st = self._view('cc4_sample_actions_device', ids, outs, *extra(3, None))
+        else:
+            lg = np.asarray(logits)
+            if lg.shape != (n, L.MASK_PER_ENV):
+                raise ValueError(f'logits must have shape ({n}, {L.MASK_PER_ENV}), got {lg.shape}')
+            if lg.dtype == np.float64:
+                lg = lg.astype(np.float32)
+            code = {np.dtype(np.float16): 1, np.dtype(np.uint16): 2, np.dtype(np.float32): 3}.get(lg.dtype)
+            if code is None:
+                raise ValueError(f'logits must be float16, float32 (or uint16: bfloat16 bit patterns), got {lg.dtype}')
+            lg = np.ascontiguousarray(lg)
+            if n == 0:
+                return self._view('cc4_sample_actions_device', ids, outs, *extra(code, None))
+            hip, vp = _hip(), ctypes.c_void_p
+            _hip_chk(hip.hipSetDevice(self._dev), 'hipSetDevice')
+            d = vp()
+            _hip_chk(hip.hipMalloc(ctypes.byref(d), lg.nbytes), 'hipMalloc')
+            try:
+                _hip_chk(hip.hipMemcpy(d, lg.ctypes.data_as(vp), lg.nbytes, 1), 'hipMemcpy')
+                a, st = self._view('cc4_sample_actions_device', ids, outs, *extra(code, d))
+            finally:
+                hip.hipFree(d)
+        faults = ctypes.c_uint32(0)
+        self._chk(self.lib.cc4_copy_faults(self._h, ctypes.byref(faults)), 'cc4_copy_faults')
+        raise_on_copy_faults(faults.value)
+        return a, st
+
     def enable_reward_terms(self, on=True):
         """cc4_enable_reward_terms: record the pieces of every step's reward (reward_terms()).  The env then runs the full builds of its step
         kernel, one launch per step, and leaves the one-launch forms of run / plan calls and rollouts, as with submitted red / green actions;
