@@ -165,6 +165,7 @@ SIGNATURES = {
     'cc4_debug_digest_rows': (ctypes.c_int, [_P, _P, ctypes.c_size_t, _P, ctypes.c_float, ctypes.c_uint8, ctypes.c_uint32, _P, _P]),
     'cc4_debug_digest': (ctypes.c_int, [_P, _P]),
     'cc4_debug_verify_plant': (ctypes.c_int, [_P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32]),
+    'cc4_debug_live_resources': (ctypes.c_int, [ctypes.POINTER(ctypes.c_int64)]),
     'cc4_get_gather_log': (ctypes.c_int, [_P, _P, ctypes.c_int32, ctypes.c_int32]),
     'cc4_get_allgathered_obs': (ctypes.c_int, [_P, _P]),
     'cc4_unpack_obs_device': (ctypes.c_int, [_P, ctypes.POINTER(_P)]),

@@ -1,11 +1,17 @@
-// cc4_api.hip -- the host side of libcc4.so, its core: create / destroy, the episode groups and their streams, the launches of one step (launch_step),
-// reset, the step entry points and the getters, episode copies, state get / set, the event log and the replay.  The handle itself: cc4_host.h; k steps
+// cc4_api.hip -- the host side of libcc4.so, its core: create / destroy (what a handle allocates, here or in any other unit, is registered with its
+// owner -- cc4_host.h dev_alloc .. release -- and cc4_destroy releases the list), the prologue of every entry point (enter), the episode groups and
+// their streams (join_groups, fork_groups), the launches of one step (launch_step), reset, the step entry points and the getters (copy_to_host),
+// episode copies, state get / set, the event log and the replay.  The handle itself: cc4_host.h; k steps
 // per call: cc4_api_run.hip; rollouts: cc4_api_rollout.hip; the communicator and the exchange: cc4_api_comm.hip; the derived views: cc4_api_views.hip;
 // debug hooks: cc4_api_debug.hip.
 #include "cc4_host.h"
 #include "cc4_export.h"
 
 static thread_local std::string g_create_err;
+// the handles that exist (shadow handles among them) and the call-local device blocks (DevTemp): what cc4_debug_live_resources counts
+static std::mutex g_handles_mu;
+static std::vector<cc4_handle*> g_handles;
+std::atomic<int64_t> g_scoped_blocks{0};
 
 // The ROCm runtime multiplexes HIP streams onto GPU_MAX_HW_QUEUES hardware queues (default 4), and two streams that share a
 // queue run their kernels one after the other.  Three launches per step fit the default; a fourth stream needs more queues
@@ -118,6 +124,34 @@ int join_groups(cc4_handle* h) {
   }
   return 0;
 }
+// ... and the other direction, in front of launches on the group streams: they start behind what the main stream holds (an upload, a reset, a launch
+// of the whole batch).  The one place that records mev.
+int fork_groups(cc4_handle* h) {
+  if (h->ngroups > 1 && h->main_ahead) {
+    HIPCHK(h, hipEventRecord(h->mev, h->stream));
+    for (int g = 1; g < h->ngroups; ++g) HIPCHK(h, hipStreamWaitEvent(h->gstream[g], h->mev, 0));
+    h->main_ahead = false;
+  }
+  return 0;
+}
+// (a handle with a communicator never has a rollout in flight -- cc4_rollout_begin refuses it -- so the order of the two refusals cannot be observed)
+int enter_refused(cc4_handle* h, const char* who, unsigned refuse) {
+  if ((refuse & EN_NO_ROLLOUT) && h->rollout_k > 0) { h->err = std::string(who) + ": a rollout is in flight on this handle: cc4_rollout_end first"; return -2; }
+  if ((refuse & EN_NO_COMM) && h->comm) { h->err = std::string(who) + ": not on a handle with a communicator"; return -2; }
+  return 0;
+}
+int enter(cc4_handle* h, const char* who, unsigned refuse) {
+  if (int rc = enter_refused(h, who, refuse)) return rc;
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  return join_groups(h) ? -1 : 0;
+}
+// `bytes` from the device to the caller's memory behind everything the handle holds, and the wait for it (0 bytes: the wait alone)
+int copy_to_host(cc4_handle* h, const char* who, void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
+  if (int rc = enter(h, who)) return rc;
+  if (bytes) HIPCHK(h, hipMemcpyAsync(dst, src, bytes, kind, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return 0;
+}
 int sync_all(cc4_handle* h) {
   // (!groups_busy: whatever the group streams were given, the main stream already waits for -- join_groups, or the joined end of
   // cc4_run_random_steps -- and a host wait on an idle stream is not free: ~8 us each inside a short timed region)
@@ -137,7 +171,7 @@ int wall_khz(cc4_handle* h) {
 // the pinned host word a kernel raises when one of its waits gives up (XchgArgs.timeout_host), and its device address
 int ensure_watchdog_word(cc4_handle* h) {
   if (!h->h_xtimeout) {
-    HIPCHK(h, hipHostMalloc(reinterpret_cast<void**>(&h->h_xtimeout), sizeof(uint32_t), hipHostMallocDefault));
+    if (pin_alloc(h, &h->h_xtimeout, sizeof(uint32_t))) return -1;
     HIPCHK(h, hipHostGetDevicePointer(reinterpret_cast<void**>(&h->d_xtimeout), h->h_xtimeout, 0));
   }
   return 0;
@@ -200,11 +234,7 @@ int launch_step(cc4_handle* h, const int32_t* d_actions, const uint8_t* d_msgs, 
   }
   const bool whole = api_step && h->whole_batch_steps && h->ngroups > 1 && h->joined_between && !h->groups_busy && !h->comm;
   h->joined_between = false;
-  if (!whole && h->ngroups > 1 && h->main_ahead) {   // e.g. an action upload or a reset on the main stream: the group streams start behind it
-    HIPCHK(h, hipEventRecord(h->mev, h->stream));
-    for (int g = 1; g < h->ngroups; ++g) HIPCHK(h, hipStreamWaitEvent(h->gstream[g], h->mev, 0));
-    h->main_ahead = false;
-  }
+  if (!whole && fork_groups(h)) return -1;   // e.g. an action upload or a reset on the main stream: the group streams start behind it
   if (h->keep_prev) {      // the rows as they stand before this step (cc4_replay_logged); a small handle: one launch per step, main stream
     const size_t n = (size_t)h->cfg.num_envs;
     HIPCHK(h, hipMemcpyAsync(h->d_prev_state, h->d_state, n * sizeof(EnvState), hipMemcpyDeviceToDevice, h->stream));
@@ -299,6 +329,7 @@ int cc4_create(const cc4_config* cfg, cc4_handle** out) {
   cc4_handle* h = new cc4_handle();
   h->cfg = *cfg;
   *out = h;
+  { std::lock_guard<std::mutex> lk(g_handles_mu); g_handles.push_back(h); }
   // how a host thread waits for the device is the runtime's default unless CC4_HOST_WAIT=spin|yield|block says otherwise (spinning by default was
   // tried in r06: no measurable gain on a 20-step call, and the exchange's soak test failed once under it); ignored (hipErrorSetOnActiveProcess) when
   // the process has initialised the device some other way already
@@ -329,59 +360,47 @@ int cc4_create(const cc4_config* cfg, cc4_handle** out) {
     if (const char* v = getenv("CC4_GROUPS")) ng = atoi(v);
     configure_groups(h, ng);
   }
-  HIPCHK(h, hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+  if (new_stream(h, &h->stream)) return -1;
   h->gstream[0] = h->stream;
   for (int g = 1; g < h->ngroups; ++g) {   // only the streams that are used: the runtime spreads streams over few hardware queues
-    HIPCHK(h, hipStreamCreateWithFlags(&h->gstream[g], hipStreamNonBlocking));
-    HIPCHK(h, hipEventCreateWithFlags(&h->gev[g], hipEventDisableTiming));
+    if (new_stream(h, &h->gstream[g]) || new_event(h, &h->gev[g], hipEventDisableTiming)) return -1;
   }
-  HIPCHK(h, hipEventCreateWithFlags(&h->mev, hipEventDisableTiming));
-  HIPCHK(h, hipEventCreateWithFlags(&h->ev_wait, hipEventDisableTiming));
-  HIPCHK(h, hipEventCreateWithFlags(&h->ev_signal, hipEventDisableTiming));
+  if (new_event(h, &h->mev, hipEventDisableTiming) || new_event(h, &h->ev_wait, hipEventDisableTiming) || new_event(h, &h->ev_signal, hipEventDisableTiming)) return -1;
   if (h->auto_groups && h->ngroups == 3) {
     // a fourth launch per step where this handle's four streams really run side by side (8192 episodes 717 -> 742 M, 2048: 310 ->
     // 314 M, 1024: 179 -> 183 M; with two of them on one hardware queue: 445 M)
-    HIPCHK(h, hipStreamCreateWithFlags(&h->gstream[3], hipStreamNonBlocking));
+    if (new_stream(h, &h->gstream[3])) return -1;
     if (streams_run_concurrently(h->gstream, 4)) {
-      HIPCHK(h, hipEventCreateWithFlags(&h->gev[3], hipEventDisableTiming));
+      if (new_event(h, &h->gev[3], hipEventDisableTiming)) return -1;
       configure_groups(h, 4);
-    } else {
-      (void)hipStreamDestroy(h->gstream[3]);
-      h->gstream[3] = nullptr;
-    }
+    } else release(h, &h->gstream[3]);
   }
   size_t n = (size_t)cfg->num_envs;
-  HIPCHK(h, hipMalloc(&h->d_state, n * sizeof(EnvState)));
   h->cold_row = cold_row_bytes(cfg->steps);
-  HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&h->d_cold), n * h->cold_row));
-  if (cfg->rng_mode == 1) HIPCHK(h, hipMalloc(&h->d_reset_ws, n * RESET_WS_WORDS * sizeof(uint32_t)));   // the one-wave kernel's generation work area
-  else HIPCHK(h, hipMalloc(&h->d_reset_ws, n * 128 * sizeof(uint64_t)));                                 // numpy stream: the LCG window of the green actions (wave_green_exec), 1 KB per episode
+  if (dev_alloc(h, &h->d_state, n * sizeof(EnvState)) || dev_alloc(h, &h->d_cold, n * h->cold_row)) return -1;
+  // counter mode: the one-wave kernel's generation work area; numpy stream: the LCG window of the green actions (wave_green_exec), 1 KB per episode
+  if (dev_alloc(h, &h->d_reset_ws, cfg->rng_mode == 1 ? n * RESET_WS_WORDS * sizeof(uint32_t) : n * 128 * sizeof(uint64_t))) return -1;
   h->in_bytes = n * NBLUE * sizeof(int32_t) + n * NBLUE * MSG_LEN;
   h->small_io = cfg->num_envs <= cc4_handle::SMALL_IO_ENVS;
   if (const char* v = getenv("CC4_SMALL_IO")) h->small_io = h->small_io && atoi(v) != 0;
-  if (h->small_io) {
-    HIPCHK(h, hipHostMalloc(reinterpret_cast<void**>(&h->pin_in), h->in_bytes, hipHostMallocDefault));
+  if (h->small_io) {      // (d_actions: the device's name for pin_in -- the owner knows pin_in only; d_obs / pin_out below alike)
+    if (pin_alloc(h, &h->pin_in, h->in_bytes)) return -1;
     HIPCHK(h, hipHostGetDevicePointer(reinterpret_cast<void**>(&h->d_actions), h->pin_in, 0));
     memset(h->pin_in, 0, h->in_bytes);
-  } else
-  HIPCHK(h, hipMalloc(&h->d_actions, h->in_bytes));
+  } else if (dev_alloc(h, &h->d_actions, h->in_bytes)) return -1;
   h->d_msgs = reinterpret_cast<uint8_t*>(h->d_actions) + n * NBLUE * sizeof(int32_t);
-  HIPCHK(h, hipMalloc(&h->d_seeds, n * sizeof(uint64_t)));
-  HIPCHK(h, hipMalloc(&h->d_envmask, n));
+  if (dev_alloc(h, &h->d_seeds, n * sizeof(uint64_t)) || dev_alloc(h, &h->d_envmask, n)) return -1;
   h->out_bytes = n * OBS_TOTAL * sizeof(int32_t) + n * sizeof(float) + n * sizeof(uint32_t) + n;
   if (h->small_io) {
-    HIPCHK(h, hipHostMalloc(reinterpret_cast<void**>(&h->pin_out), h->out_bytes, hipHostMallocDefault));
+    if (pin_alloc(h, &h->pin_out, h->out_bytes)) return -1;
     HIPCHK(h, hipHostGetDevicePointer(reinterpret_cast<void**>(&h->d_obs), h->pin_out, 0));
-  } else
-  HIPCHK(h, hipMalloc(&h->d_obs, h->out_bytes));
+  } else if (dev_alloc(h, &h->d_obs, h->out_bytes)) return -1;
   h->d_reward = reinterpret_cast<float*>(h->d_obs + n * OBS_TOTAL);
   h->d_err = reinterpret_cast<uint32_t*>(h->d_reward + n);
   h->d_done = reinterpret_cast<uint8_t*>(h->d_err + n);
-  HIPCHK(h, hipMalloc(&h->d_mask, n * MASK_TOTAL));
-  HIPCHK(h, hipMalloc(&h->d_rng, n * 7 * sizeof(uint64_t)));
-  HIPCHK(h, hipMalloc(&h->d_claim, n * sizeof(uint32_t) + sizeof(uint32_t)));     // [n] claim words + the fault word
+  if (dev_alloc(h, &h->d_mask, n * MASK_TOTAL) || dev_alloc(h, &h->d_rng, n * 7 * sizeof(uint64_t))) return -1;
+  if (dev_alloc(h, &h->d_claim, n * sizeof(uint32_t) + sizeof(uint32_t)) || dev_alloc(h, &h->d_mask_stale, n)) return -1;     // [n] claim words + the fault word
   h->d_copy_fault = h->d_claim + n;
-  HIPCHK(h, hipMalloc(&h->d_mask_stale, n));
   HIPCHK(h, hipMemsetAsync(h->d_claim, 0, n * sizeof(uint32_t) + sizeof(uint32_t), h->stream));
   HIPCHK(h, hipMemsetAsync(h->d_mask_stale, 0, n, h->stream));
   HIPCHK(h, hipMemsetAsync(h->d_state, 0, n * sizeof(EnvState), h->stream));
@@ -389,8 +408,6 @@ int cc4_create(const cc4_config* cfg, cc4_handle** out) {
   HIPCHK(h, hipMemsetAsync(h->d_obs, 0, n * OBS_TOTAL * sizeof(int32_t), h->stream));
   HIPCHK(h, hipMemsetAsync(h->d_done, 0, n, h->stream));
   HIPCHK(h, hipMemsetAsync(h->d_err, 0, n * sizeof(uint32_t), h->stream));
-  HIPCHK(h, hipEventCreate(&h->ev0));
-  HIPCHK(h, hipEventCreate(&h->ev1));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   if (choose_run_form(h, 0)) return -1;
   if (const char* v = getenv("CC4_PERSIST_MIN_K")) h->persist_min_k = atoi(v);
@@ -404,37 +421,20 @@ void cc4_destroy(cc4_handle* h) {
   if (!h) return;
   enq_pool_stop(h);
   (void)hipSetDevice(h->cfg.device_id);
-  for (int g = cc4_handle::MAX_GROUPS - 1; g >= 0; --g) if (h->gstream[g]) (void)hipStreamSynchronize(h->gstream[g]);
-  if (h->comm_stream) (void)hipStreamSynchronize(h->comm_stream);
+  for (const OwnedList::Entry& e : h->own.entries) if (e.kind == OWN_STREAM && *e.field) (void)hipStreamSynchronize(static_cast<hipStream_t>(*e.field));
   if (h->comm) ncclCommDestroy(h->comm);
-  for (int b = 0; b < cc4_handle::OBS_RING; ++b) { for (int g = 0; g < cc4_handle::MAX_GROUPS; ++g) if (h->ev_step[b][g]) (void)hipEventDestroy(h->ev_step[b][g]); if (h->ev_comm[b]) (void)hipEventDestroy(h->ev_comm[b]); }
-  if (h->comm_stream) (void)hipStreamDestroy(h->comm_stream);
-  for (int g = 0; g < 4; ++g) if (h->gpolicy[g]) (void)hipStreamDestroy(h->gpolicy[g]);
-  if (h->rev) (void)hipEventDestroy(h->rev);
-  for (void* p : {(void*)h->d_ract, (void*)h->d_rready, (void*)h->d_rcnt, (void*)h->d_rfail}) if (p) (void)hipFree(p);
-  void* ptrs[] = {h->d_state, h->d_cold, h->small_io ? nullptr : (void*)h->d_actions, h->d_seeds, h->d_envmask, h->small_io ? nullptr : (void*)h->d_obs,
-                  h->d_mask, h->d_rng, h->d_reset_ws, h->d_ext, h->d_run, h->d_slot_part, h->d_pool, h->d_claim, h->d_mask_stale, h->d_copy_idx, h->d_copy_seeds, h->d_pol};     // (d_msgs, d_reward, d_err, d_done live inside d_actions / d_obs; small handles: pinned host memory, freed below)
-  for (void* p : ptrs) if (p) (void)hipFree(p);
   if (h->shadow) { cc4_destroy(h->shadow); h->shadow = nullptr; (void)hipSetDevice(h->cfg.device_id); }
-  for (void* p : {(void*)h->d_prev_state, (void*)h->d_prev_cold, (void*)h->d_prev_out}) if (p) (void)hipFree(p);
-  if (h->d_digest) (void)hipFree(h->d_digest);
-  if (h->d_plan_err) (void)hipFree(h->d_plan_err);
-  if (h->pin_in) (void)hipHostFree(h->pin_in);
-  if (h->pin_out) (void)hipHostFree(h->pin_out);
-  for (int b = 0; b < cc4_handle::OBS_RING; ++b) { if (h->d_obs8[b]) (void)hipFree(h->d_obs8[b]); if (h->d_all_obs8[b]) (void)hipFree(h->d_all_obs8[b]); }
-  if (h->d_unpacked) (void)hipFree(h->d_unpacked);
-  for (void* p : {(void*)h->d_xslab, (void*)h->d_xall, (void*)h->d_xflags, (void*)h->d_xlog, (void*)h->d_xgcnt}) if (p) (void)hipFree(p);
-  if (h->h_xtimeout) (void)hipHostFree(h->h_xtimeout);
-  if (h->xev) (void)hipEventDestroy(h->xev);
-  for (hipEvent_t e : h->evs) if (e) (void)hipEventDestroy(e);
-  if (h->ev0) (void)hipEventDestroy(h->ev0);
-  if (h->ev1) (void)hipEventDestroy(h->ev1);
-  for (int g = 1; g < cc4_handle::MAX_GROUPS; ++g) { if (h->gev[g]) (void)hipEventDestroy(h->gev[g]); if (h->gstream[g]) (void)hipStreamDestroy(h->gstream[g]); }
-  if (h->mev) (void)hipEventDestroy(h->mev);
-  if (h->ev_wait) (void)hipEventDestroy(h->ev_wait);
-  if (h->ev_signal) (void)hipEventDestroy(h->ev_signal);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
+  h->own.release_all();
+  { std::lock_guard<std::mutex> lk(g_handles_mu); g_handles.erase(std::remove(g_handles.begin(), g_handles.end(), h), g_handles.end()); }
   delete h;
+}
+// debug: what the handles of this process (and the call-local blocks of calls in flight) hold -- out[0] device blocks, [1] pinned blocks, [2] events, [3] streams
+int cc4_debug_live_resources(int64_t out[4]) {
+  if (!out) return -2;
+  out[OWN_DEVICE] = g_scoped_blocks.load(); out[OWN_PINNED] = out[OWN_EVENT] = out[OWN_STREAM] = 0;
+  std::lock_guard<std::mutex> lk(g_handles_mu);
+  for (const cc4_handle* h : g_handles) h->own.count_live(out);
+  return 0;
 }
 
 // the launch of a reset on the main stream (joined by the caller), from seeds and a mask on the device (either may be null), and its bookkeeping: what
@@ -459,8 +459,7 @@ static int reset_launch(cc4_handle* h, const uint64_t* d_seeds, const uint8_t* d
   return 0;
 }
 int cc4_reset(cc4_handle* h, const uint64_t* seeds, const uint8_t* env_mask) {
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  if (join_groups(h)) return -1;
+  if (int rc = enter(h, "cc4_reset")) return rc;
   size_t n = (size_t)h->cfg.num_envs;
   if (seeds) HIPCHK(h, hipMemcpyAsync(h->d_seeds, seeds, n * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
   if (env_mask) HIPCHK(h, hipMemcpyAsync(h->d_envmask, env_mask, n, hipMemcpyHostToDevice, h->stream));
@@ -470,25 +469,19 @@ int cc4_reset(cc4_handle* h, const uint64_t* seeds, const uint8_t* env_mask) {
 }
 // cc4_reset on seeds and a mask that are on the device already (a criterion a kernel of the caller's evaluated: env_mask = done): no upload, no host wait
 int cc4_reset_device(cc4_handle* h, const uint64_t* d_seeds, const uint8_t* d_env_mask) {
-  if (h->rollout_k > 0) { h->err = "cc4_reset_device: a rollout is in flight on this handle: cc4_rollout_end first"; return -2; }
+  if (int rc = enter_refused(h, "cc4_reset_device", EN_NO_ROLLOUT)) return rc;
   if (h->comm) { h->err = "cc4_reset_device: not on a handle with a communicator (cc4_reset orders the exchange's buffers through the host)"; return -2; }
   if (reinterpret_cast<uintptr_t>(d_seeds) % 8) { h->err = "cc4_reset_device: the seeds must be 8-byte aligned"; return -2; }
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  if (join_groups(h)) return -1;
+  if (int rc = enter(h, "cc4_reset_device")) return rc;
   return reset_launch(h, d_seeds, d_env_mask);
 }
 
 // ---- per-episode opponent classes (include/cc4.h "Mixed opponents in one batch"; the rule: row_assign / row_policies, cc4_state.h).  An assignment
 // is a byte of the hot row that only the regenerations read: no step launch needs ordering behind these beyond the main stream's own.
-static int policy_call_refused(cc4_handle* h, const char* who) {
-  if (h->rollout_k > 0) { h->err = std::string(who) + ": a rollout is in flight on this handle: cc4_rollout_end first"; return -2; }
-  return 0;
-}
 int cc4_set_policies_device(cc4_handle* h, const int8_t* d_red, const int8_t* d_green, const int8_t* d_blue) {
-  if (int rc = policy_call_refused(h, "cc4_set_policies_device")) return rc;
+  if (int rc = enter_refused(h, "cc4_set_policies_device", EN_NO_ROLLOUT)) return rc;
   if (!d_red && !d_green && !d_blue) return 0;
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  if (join_groups(h)) return -1;
+  if (int rc = enter(h, "cc4_set_policies_device")) return rc;
   const int n = h->cfg.num_envs;
   hipLaunchKernelGGL(k_set_policies, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->d_state, d_red, d_green, d_blue, n, h->d_copy_fault);
   HIPCHK(h, hipGetLastError());
@@ -496,12 +489,11 @@ int cc4_set_policies_device(cc4_handle* h, const int8_t* d_red, const int8_t* d_
   return 0;
 }
 int cc4_set_policies(cc4_handle* h, const int8_t* red, const int8_t* green, const int8_t* blue) {
-  if (int rc = policy_call_refused(h, "cc4_set_policies")) return rc;
+  if (int rc = enter_refused(h, "cc4_set_policies", EN_NO_ROLLOUT)) return rc;
   if (!red && !green && !blue) return 0;
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  if (join_groups(h)) return -1;
+  if (int rc = enter(h, "cc4_set_policies")) return rc;
   const size_t n = (size_t)h->cfg.num_envs;
-  if (!h->d_pol) HIPCHK(h, hipMalloc(&h->d_pol, 6 * n));
+  if (!h->d_pol && dev_alloc(h, &h->d_pol, 6 * n)) return -1;
   const int8_t* src[3] = {red, green, blue};
   const int8_t* dev[3] = {nullptr, nullptr, nullptr};
   for (int c = 0; c < 3; ++c) if (src[c]) { HIPCHK(h, hipMemcpyAsync(h->d_pol + c * n, src[c], n, hipMemcpyHostToDevice, h->stream)); dev[c] = h->d_pol + c * n; }
@@ -510,22 +502,20 @@ int cc4_set_policies(cc4_handle* h, const int8_t* red, const int8_t* green, cons
   return 0;
 }
 int cc4_policies_device(cc4_handle* h, int8_t* d_live, int8_t* d_assigned) {
-  if (int rc = policy_call_refused(h, "cc4_policies_device")) return rc;
+  if (int rc = enter_refused(h, "cc4_policies_device", EN_NO_ROLLOUT)) return rc;
   if (!d_live && !d_assigned) return 0;
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  if (join_groups(h)) return -1;
+  if (int rc = enter(h, "cc4_policies_device")) return rc;
   const int n = h->cfg.num_envs;
   hipLaunchKernelGGL(k_get_policies, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->d_state, d_live, d_assigned, n);
   HIPCHK(h, hipGetLastError());
   return 0;
 }
 int cc4_get_policies(cc4_handle* h, int8_t* live, int8_t* assigned) {
-  if (int rc = policy_call_refused(h, "cc4_get_policies")) return rc;
+  if (int rc = enter_refused(h, "cc4_get_policies", EN_NO_ROLLOUT)) return rc;
   if (!live && !assigned) return 0;
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  if (join_groups(h)) return -1;
+  if (int rc = enter(h, "cc4_get_policies")) return rc;
   const size_t n = (size_t)h->cfg.num_envs;
-  if (!h->d_pol) HIPCHK(h, hipMalloc(&h->d_pol, 6 * n));
+  if (!h->d_pol && dev_alloc(h, &h->d_pol, 6 * n)) return -1;
   if (int rc = cc4_policies_device(h, live ? h->d_pol : nullptr, assigned ? h->d_pol + 3 * n : nullptr)) return rc;
   if (live) HIPCHK(h, hipMemcpyAsync(live, h->d_pol, 3 * n, hipMemcpyDeviceToHost, h->stream));
   if (assigned) HIPCHK(h, hipMemcpyAsync(assigned, h->d_pol + 3 * n, 3 * n, hipMemcpyDeviceToHost, h->stream));
@@ -535,30 +525,30 @@ int cc4_get_policies(cc4_handle* h, int8_t* live, int8_t* assigned) {
 // The same definition on one hot row (cc4_get_state, a checkpoint): no device, no handle.
 int cc4_row_set_policies(void* hot_row, int red, int green, int blue) {
   if (!hot_row) return -2;
-  EnvState* s = static_cast<EnvState*>(aligned_alloc(alignof(EnvState), sizeof(EnvState)));   // (the caller's bytes may sit at any address)
-  if (!s) return -1;
-  memcpy(s, hot_row, offsetof(EnvState, hd));
-  const bool ok = row_assign(s, red, green, blue);
-  if (ok) static_cast<uint8_t*>(hot_row)[offsetof(EnvState, assign)] = s->assign;
-  free(s);
+  RowCopy r;      // (the agent part of the row is all the rule reads: no more of the caller's bytes is touched)
+  if (!(r.s = static_cast<EnvState*>(row_copy(hot_row, offsetof(EnvState, hd), alignof(EnvState), sizeof(EnvState))))) return -1;
+  const bool ok = row_assign(r.s, red, green, blue);
+  if (ok) static_cast<uint8_t*>(hot_row)[offsetof(EnvState, assign)] = r.s->assign;
   return ok ? 0 : -2;
 }
 int cc4_row_get_policies(const void* hot_row, int8_t live[3], int8_t assigned[3]) {
   if (!hot_row) return -2;
-  EnvState* s = static_cast<EnvState*>(aligned_alloc(alignof(EnvState), sizeof(EnvState)));
-  if (!s) return -1;
-  memcpy(s, hot_row, offsetof(EnvState, hd));
-  row_policies(s, live, assigned);
-  free(s);
+  RowCopy r;
+  if (!(r.s = static_cast<EnvState*>(row_copy(hot_row, offsetof(EnvState, hd), alignof(EnvState), sizeof(EnvState))))) return -1;
+  row_policies(r.s, live, assigned);
   return 0;
 }
 
-int cc4_step(cc4_handle* h, const int32_t* actions, const uint8_t* messages) {
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  if (join_groups(h)) return -1;
-  size_t n = (size_t)h->cfg.num_envs;
+// the blue actions and messages of a step from the caller's memory into the handle's buffers, on the main stream (either may be null: none given)
+static int upload_inputs(cc4_handle* h, const int32_t* actions, const uint8_t* messages) {
+  const size_t n = (size_t)h->cfg.num_envs;
   if (actions) HIPCHK(h, hipMemcpyAsync(h->d_actions, actions, n * NBLUE * sizeof(int32_t), hipMemcpyDefault, h->stream));
   if (messages) HIPCHK(h, hipMemcpyAsync(h->d_msgs, messages, n * NBLUE * MSG_LEN, hipMemcpyDefault, h->stream));
+  return 0;
+}
+int cc4_step(cc4_handle* h, const int32_t* actions, const uint8_t* messages) {
+  if (int rc = enter(h, "cc4_step")) return rc;
+  if (upload_inputs(h, actions, messages)) return -1;
   if (launch_step(h, actions ? h->d_actions : nullptr, messages ? h->d_msgs : nullptr, false, 0, 0, false, true)) return -1;
   return sync_all(h);
 }
@@ -585,7 +575,7 @@ static int fetch_outputs(cc4_handle* h, int32_t* obs, float* reward, uint8_t* do
     return 0;
   }
   if (h->cfg.num_envs <= PIN_MAX_ENVS) {
-    if (!h->pin_out) HIPCHK(h, hipHostMalloc(reinterpret_cast<void**>(&h->pin_out), h->out_bytes, hipHostMallocDefault));
+    if (!h->pin_out && pin_alloc(h, &h->pin_out, h->out_bytes)) return -1;
     const size_t lo = obs ? 0 : b_obs;                         // (a caller that wants no observations does not pay for them)
     HIPCHK(h, hipMemcpyAsync(h->pin_out + lo, reinterpret_cast<const uint8_t*>(h->d_obs) + lo, h->out_bytes - lo, hipMemcpyDefault, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -605,8 +595,7 @@ int cc4_fetch(cc4_handle* h, int32_t* obs, float* reward, uint8_t* done, uint32_
 }
 // cc4_step + cc4_fetch with one host synchronisation in all: inputs up in one copy, the step's launches, outputs down in one copy
 int cc4_step_fetch(cc4_handle* h, const int32_t* actions, const uint8_t* messages, int32_t* obs, float* reward, uint8_t* done, uint32_t* err) {
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  if (join_groups(h)) return -1;
+  if (int rc = enter(h, "cc4_step_fetch")) return rc;
   const size_t n = (size_t)h->cfg.num_envs;
   const size_t b_act = n * NBLUE * sizeof(int32_t), b_msg = n * NBLUE * MSG_LEN;
   if (h->small_io) {                                          // (every earlier launch has completed: each call of this surface ends with a host wait)
@@ -614,15 +603,12 @@ int cc4_step_fetch(cc4_handle* h, const int32_t* actions, const uint8_t* message
     if (actions) memcpy(h->pin_in, actions, b_act);
     if (messages) memcpy(h->pin_in + b_act, messages, b_msg);
   } else if (h->cfg.num_envs <= PIN_MAX_ENVS && (actions || messages)) {
-    if (!h->pin_in) HIPCHK(h, hipHostMalloc(reinterpret_cast<void**>(&h->pin_in), h->in_bytes, hipHostMallocDefault));
+    if (!h->pin_in && pin_alloc(h, &h->pin_in, h->in_bytes)) return -1;
     if (actions) memcpy(h->pin_in, actions, b_act);
     if (messages) memcpy(h->pin_in + b_act, messages, b_msg);
     const size_t lo = actions ? 0 : b_act, hi = messages ? b_act + b_msg : b_act;
     HIPCHK(h, hipMemcpyAsync(reinterpret_cast<uint8_t*>(h->d_actions) + lo, h->pin_in + lo, hi - lo, hipMemcpyDefault, h->stream));
-  } else {
-    if (actions) HIPCHK(h, hipMemcpyAsync(h->d_actions, actions, b_act, hipMemcpyDefault, h->stream));
-    if (messages) HIPCHK(h, hipMemcpyAsync(h->d_msgs, messages, b_msg, hipMemcpyDefault, h->stream));
-  }
+  } else if (upload_inputs(h, actions, messages)) return -1;
   if (launch_step(h, actions ? h->d_actions : nullptr, messages ? h->d_msgs : nullptr, false, 0, 0, false, true)) return -1;
   return fetch_outputs(h, obs, reward, done, err);
 }
@@ -633,10 +619,9 @@ int cc4_step_ex(cc4_handle* h, const int32_t* actions, const uint8_t* messages, 
                 offsetof(cc4_agent_action, rate0) == offsetof(ExtAct, rate0) && offsetof(cc4_agent_action, flags) == offsetof(ExtAct, flags),
                 "cc4_agent_action (include/cc4.h) is ExtAct (csrc/cc4_state.h)");
   if (!red && !green) return cc4_step(h, actions, messages);
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  if (join_groups(h)) return -1;
+  if (int rc = enter(h, "cc4_step_ex")) return rc;
   const size_t n = (size_t)h->cfg.num_envs;
-  if (!h->d_ext) HIPCHK(h, hipMalloc(&h->d_ext, n * EXT_PER_ENV * sizeof(ExtAct)));
+  if (!h->d_ext && dev_alloc(h, &h->d_ext, n * EXT_PER_ENV * sizeof(ExtAct))) return -1;
   h->h_ext.resize(n * EXT_PER_ENV);
   memset(h->h_ext.data(), 0xFF, h->h_ext.size() * sizeof(ExtAct));      // type -1 everywhere: nothing submitted
   for (size_t e = 0; e < n; ++e) {
@@ -655,8 +640,7 @@ int cc4_step_ex(cc4_handle* h, const int32_t* actions, const uint8_t* messages, 
   }
   HIPCHK(h, hipMemcpyAsync(h->d_ext, h->h_ext.data(), h->h_ext.size() * sizeof(ExtAct), hipMemcpyHostToDevice, h->stream));
   h->ext_seen = true; h->ext_submitted = true; h->ext_dirty = true; h->ext_green_dirty = green != nullptr;
-  if (actions) HIPCHK(h, hipMemcpyAsync(h->d_actions, actions, n * NBLUE * sizeof(int32_t), hipMemcpyDefault, h->stream));
-  if (messages) HIPCHK(h, hipMemcpyAsync(h->d_msgs, messages, n * NBLUE * MSG_LEN, hipMemcpyDefault, h->stream));
+  if (upload_inputs(h, actions, messages)) return -1;
   if (launch_step(h, actions ? h->d_actions : nullptr, messages ? h->d_msgs : nullptr, false, 0, 0, true, true)) return -1;
   return sync_all(h);
 }
@@ -665,11 +649,10 @@ int cc4_step_ex(cc4_handle* h, const int32_t* actions, const uint8_t* messages, 
 // engine's own host build edits them, they go back
 int cc4_edit_state(cc4_handle* h, int32_t env, int32_t op, int32_t a0, int32_t a1, int32_t a2) {
   if (env < 0 || env >= h->cfg.num_envs) { h->err = "cc4_edit_state: env out of range"; return -2; }
-  EnvState* st = (EnvState*)malloc(sizeof(EnvState));
-  EnvCold* cold = (EnvCold*)malloc(h->cold_row);
-  int rc = cc4_get_state(h, env, st);
-  if (rc == 0) rc = cc4_get_cold(h, env, cold);
+  FetchedRow r;
+  int rc = r.fetch(h, env);
   if (rc == 0) {
+    EnvState* const st = r.st; EnvCold* const cold = r.cold;
     StepWork w; memset(&w, 0, sizeof(w));
     Ctx x{st, cold, &st->rng, st->hd, &w};
     rc = state_edit(x, op, a0, a1, a2);
@@ -678,7 +661,6 @@ int cc4_edit_state(cc4_handle* h, int32_t env, int32_t op, int32_t a0, int32_t a
     if (rc < 0) h->err = "cc4_edit_state: unknown op, bad argument, or refused by a full container (see the episode's error flags)";
     int r2 = cc4_set_state(h, env, st); if (r2 == 0) r2 = cc4_set_cold(h, env, cold); if (r2) rc = r2;
   }
-  free(st); free(cold);
   return rc;
 }
 
@@ -694,13 +676,11 @@ int cc4_step_device(cc4_handle* h, const int32_t* d_actions, const uint8_t* d_me
 int cc4_step_red_device(cc4_handle* h, const int32_t* d_actions, const uint8_t* d_messages, const int32_t* d_red) {
   const char* who = "cc4_step_red_device";
   if (!d_red) { h->err = std::string(who) + ": no red actions (cc4_step_device steps without them)"; return -2; }
-  if (h->rollout_k > 0) { h->err = std::string(who) + ": a rollout is in flight on this handle: cc4_rollout_end first"; return -2; }
-  if (h->comm) { h->err = std::string(who) + ": not on a handle with a communicator"; return -2; }
+  if (int rc = enter_refused(h, who, EN_NO_ROLLOUT | EN_NO_COMM)) return rc;
   if (reinterpret_cast<uintptr_t>(d_red) % 16) { h->err = std::string(who) + ": the red actions must be 16-byte aligned"; return -2; }
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  if (join_groups(h)) return -1;
+  if (int rc = enter(h, who)) return rc;
   const int n = h->cfg.num_envs;
-  if (!h->d_ext) HIPCHK(h, hipMalloc(&h->d_ext, (size_t)n * EXT_PER_ENV * sizeof(ExtAct)));     // (ext_green_dirty is still true: the kernel writes every record)
+  if (!h->d_ext && dev_alloc(h, &h->d_ext, (size_t)n * EXT_PER_ENV * sizeof(ExtAct))) return -1;     // (ext_green_dirty is still true: the kernel writes every record)
   RedSubmitArgs a{h->d_state, d_red, h->d_ext, n, h->ext_green_dirty ? 1 : 0, h->d_copy_fault};
   hipLaunchKernelGGL(k_red_submit, dim3((n * NRED + 255) / 256), dim3(256), 0, h->stream, a);
   HIPCHK(h, hipGetLastError());
@@ -725,12 +705,7 @@ static int group_prologue(cc4_handle* h, int32_t g, const char* who) {
   if (g < 0 || g >= h->ngroups) { h->err = std::string(who) + ": no such group"; return -2; }
   if (h->comm || h->evlog_on || h->ext_seen) { h->err = std::string(who) + ": group-wise stepping serves handles without a communicator, event log, submitted red / green actions or recorded reward terms (cc4_enable_reward_terms)"; return -2; }
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  if (h->ngroups > 1 && h->main_ahead) {     // e.g. a reset or an upload on the main stream: the group streams start behind it
-    HIPCHK(h, hipEventRecord(h->mev, h->stream));
-    for (int q = 1; q < h->ngroups; ++q) HIPCHK(h, hipStreamWaitEvent(h->gstream[q], h->mev, 0));
-    h->main_ahead = false;
-  }
-  return 0;
+  return fork_groups(h) ? -1 : 0;     // e.g. a reset or an upload on the main stream: the group streams start behind it (no join: the groups stay apart)
 }
 int cc4_step_group_device(cc4_handle* h, int32_t g, const int32_t* d_actions, const uint8_t* d_messages) {
   if (int rc = group_prologue(h, g, "cc4_step_group_device")) return rc;
@@ -758,38 +733,24 @@ int cc4_random_actions_group_device(cc4_handle* h, int32_t g, uint64_t seed0, ui
 }
 
 int cc4_get_obs(cc4_handle* h, int32_t* obs) {
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  if (join_groups(h)) return -1;
-  HIPCHK(h, hipMemcpyAsync(obs, h->d_obs, (size_t)h->cfg.num_envs * OBS_TOTAL * sizeof(int32_t), hipMemcpyDefault, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return 0;
+  return copy_to_host(h, "cc4_get_obs", obs, h->d_obs, (size_t)h->cfg.num_envs * OBS_TOTAL * sizeof(int32_t), hipMemcpyDefault);
 }
 int cc4_get_reward_done(cc4_handle* h, float* reward, uint8_t* done) {
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  if (join_groups(h)) return -1;
-  size_t n = (size_t)h->cfg.num_envs;
+  if (int rc = enter(h, "cc4_get_reward_done")) return rc;      // (two pieces behind one prologue and in front of one wait: not two copy_to_host)
+  const size_t n = (size_t)h->cfg.num_envs;
   if (reward) HIPCHK(h, hipMemcpyAsync(reward, h->d_reward, n * sizeof(float), hipMemcpyDefault, h->stream));
   if (done) HIPCHK(h, hipMemcpyAsync(done, h->d_done, n, hipMemcpyDefault, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return 0;
 }
 int cc4_get_action_mask(cc4_handle* h, uint8_t* mask) {
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  if (join_groups(h)) return -1;
-  HIPCHK(h, hipMemcpyAsync(mask, h->d_mask, (size_t)h->cfg.num_envs * MASK_TOTAL, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return 0;
+  return copy_to_host(h, "cc4_get_action_mask", mask, h->d_mask, (size_t)h->cfg.num_envs * MASK_TOTAL, hipMemcpyDeviceToHost);
 }
 int cc4_get_err(cc4_handle* h, uint32_t* err) {
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  if (join_groups(h)) return -1;
-  HIPCHK(h, hipMemcpyAsync(err, h->d_err, (size_t)h->cfg.num_envs * sizeof(uint32_t), hipMemcpyDefault, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return 0;
+  return copy_to_host(h, "cc4_get_err", err, h->d_err, (size_t)h->cfg.num_envs * sizeof(uint32_t), hipMemcpyDefault);
 }
 int cc4_get_rng_state(cc4_handle* h, uint64_t* out) {
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  if (join_groups(h)) return -1;
+  if (int rc = enter(h, "cc4_get_rng_state")) return rc;
   int n = h->cfg.num_envs;
   hipLaunchKernelGGL(k_rng_state, dim3((n + 127) / 128), dim3(128), 0, h->stream, h->d_state, h->d_rng, n);
   HIPCHK(h, hipGetLastError());
@@ -799,8 +760,7 @@ int cc4_get_rng_state(cc4_handle* h, uint64_t* out) {
 }
 int cc4_set_seed(cc4_handle* h, const uint64_t* seeds) {
   h->prev_valid = false;        // (cc4_replay_logged would repeat a step from rows that have moved on)
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  if (join_groups(h)) return -1;
+  if (int rc = enter(h, "cc4_set_seed")) return rc;
   int n = h->cfg.num_envs;
   HIPCHK(h, hipMemcpyAsync(h->d_seeds, seeds, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
   hipLaunchKernelGGL(k_set_seed, dim3((n + 127) / 128), dim3(128), 0, h->stream, h->d_state, h->d_cold, h->cold_row, h->d_seeds, n, h->cfg.rng_mode);
@@ -811,8 +771,7 @@ int cc4_set_seed(cc4_handle* h, const uint64_t* seeds) {
 int cc4_set_rng_state(cc4_handle* h, const uint64_t* words) {
   h->prev_valid = false;
   if (h->cfg.rng_mode != 0) { h->err = "cc4_set_rng_state: a numpy PCG64 state needs rng_mode 0"; return -2; }
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  if (join_groups(h)) return -1;
+  if (int rc = enter(h, "cc4_set_rng_state")) return rc;
   int n = h->cfg.num_envs;
   HIPCHK(h, hipMemcpyAsync(h->d_rng, words, (size_t)n * 6 * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));   // d_rng holds 7 words per episode
   hipLaunchKernelGGL(k_set_rng_state, dim3((n + 127) / 128), dim3(128), 0, h->stream, h->d_state, h->d_rng, n);
@@ -827,16 +786,11 @@ int cc4_actions_device(cc4_handle* h, int32_t** p) { *p = h->d_actions; return 0
 // host copy of the handle's device action buffer: the indices cc4_step uploaded, or the ones the last step of
 // cc4_run_random_steps / cc4_random_actions_device drew on the device
 int cc4_get_actions(cc4_handle* h, int32_t* out) {
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  if (join_groups(h)) return -1;
-  HIPCHK(h, hipMemcpyAsync(out, h->d_actions, (size_t)h->cfg.num_envs * NBLUE * sizeof(int32_t), hipMemcpyDefault, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return 0;
+  return copy_to_host(h, "cc4_get_actions", out, h->d_actions, (size_t)h->cfg.num_envs * NBLUE * sizeof(int32_t), hipMemcpyDefault);
 }
 
 int cc4_random_actions_device(cc4_handle* h, uint64_t seed0, uint32_t t) {
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  if (join_groups(h)) return -1;
+  if (int rc = enter(h, "cc4_random_actions_device")) return rc;
   int tot = h->cfg.num_envs * NBLUE;
   hipLaunchKernelGGL(k_random_actions, dim3((tot + 255) / 256), dim3(256), 0, h->stream, h->d_actions, h->cfg.num_envs, seed0, t, 0);
   HIPCHK(h, hipGetLastError());
@@ -853,8 +807,7 @@ int cc4_stream_wait(cc4_handle* h, void* hip_stream) {
   return 0;
 }
 int cc4_stream_signal(cc4_handle* h, void* hip_stream) {
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  if (join_groups(h)) return -1;
+  if (int rc = enter(h, "cc4_stream_signal")) return rc;
   HIPCHK(h, hipEventRecord(h->ev_signal, h->stream));
   HIPCHK(h, hipStreamWaitEvent(reinterpret_cast<hipStream_t>(hip_stream), h->ev_signal, 0));
   return 0;
@@ -866,8 +819,7 @@ int cc4_policy_outputs(cc4_handle* h, int32_t obs_dtype, void* d_obs, uint8_t* d
   if (reinterpret_cast<uintptr_t>(d_obs) % align[obs_dtype] || reinterpret_cast<uintptr_t>(d_reward) % 4 || reinterpret_cast<uintptr_t>(d_err) % 4) {
     h->err = "cc4_policy_outputs: the observation buffer must be aligned to four values, reward and error buffers to 4 bytes"; return -2;
   }
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  if (join_groups(h)) return -1;
+  if (int rc = enter(h, "cc4_policy_outputs")) return rc;
   const int n = h->cfg.num_envs, tpb = 256;
   const int ep_blocks = (n + tpb - 1) / tpb;
   const long long vecs = (long long)n * OBS_TOTAL / 4;
@@ -886,15 +838,13 @@ int cc4_copy_episodes_device(cc4_handle* h, int32_t n, const void* d_src_bank, i
                              void* d_dst_bank, int32_t dst_capacity, const int32_t* d_dst, const uint64_t* d_seeds) {
   const char* who = "cc4_copy_episodes_device";
   if (n < 0 || (n > 0 && (!d_src || !d_dst))) { h->err = std::string(who) + ": n < 0, or no index arrays"; return -2; }
-  if (h->comm) { h->err = std::string(who) + ": not on a handle with a communicator"; return -2; }
-  if (h->rollout_k > 0) { h->err = std::string(who) + ": a rollout is in flight on this handle: cc4_rollout_end first"; return -2; }
+  if (int rc = enter_refused(h, who, EN_NO_ROLLOUT | EN_NO_COMM)) return rc;
   if (d_src_bank && d_dst_bank) { h->err = std::string(who) + ": bank -> bank copies are not supported (one side must be the handle's episodes)"; return -2; }
   if (d_seeds && d_dst_bank) { h->err = std::string(who) + ": seeds apply to copies into the handle's episodes only"; return -2; }
   if ((d_src_bank && src_capacity < 0) || (d_dst_bank && dst_capacity < 0)) { h->err = std::string(who) + ": negative bank capacity"; return -2; }
   if (reinterpret_cast<uintptr_t>(d_src_bank) % 64 || reinterpret_cast<uintptr_t>(d_dst_bank) % 64) { h->err = std::string(who) + ": a bank must be 64-byte aligned"; return -2; }
   if (n == 0) return 0;
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  if (join_groups(h)) return -1;
+  if (int rc = enter(h, "cc4_copy_episodes_device")) return rc;
   h->prev_valid = false;        // (cc4_replay_logged would repeat a step from rows that have moved on)
   uint32_t stamp = g_copy_stamp.fetch_add(1) % 0x7FFFFFFFu + 1u;     // 1 .. 2^31 - 1: claim words 2 * stamp and 2 * stamp + 1, never 0
   CopyArgs a{h->d_state, h->d_cold, h->cold_row, h->d_obs, h->d_reward, h->d_done, h->d_err, h->d_mask, h->d_mask_stale, h->d_claim,
@@ -909,8 +859,7 @@ int cc4_copy_episodes_device(cc4_handle* h, int32_t n, const void* d_src_bank, i
   return 0;
 }
 int cc4_copy_faults(cc4_handle* h, uint32_t* out) {
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  if (join_groups(h)) return -1;
+  if (int rc = enter(h, "cc4_copy_faults")) return rc;
   HIPCHK(h, hipMemcpyAsync(out, h->d_copy_fault, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipMemsetAsync(h->d_copy_fault, 0, sizeof(uint32_t), h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -919,12 +868,10 @@ int cc4_copy_faults(cc4_handle* h, uint32_t* out) {
 int cc4_clone_episodes(cc4_handle* h, int32_t n, const int32_t* src, const int32_t* dst, const uint64_t* seeds) {
   if (n < 0 || n > h->cfg.num_envs) { h->err = "cc4_clone_episodes: n must be 0 .. num_envs"; return -2; }
   if (n == 0) return 0;
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  if (h->rollout_k > 0) { h->err = "cc4_clone_episodes: a rollout is in flight on this handle: cc4_rollout_end first"; return -2; }
-  if (join_groups(h)) return -1;
+  if (int rc = enter(h, "cc4_clone_episodes", EN_NO_ROLLOUT)) return rc;
   const size_t N = (size_t)h->cfg.num_envs;
-  if (!h->d_copy_idx) HIPCHK(h, hipMalloc(&h->d_copy_idx, 2 * N * sizeof(int32_t)));
-  if (seeds && !h->d_copy_seeds) HIPCHK(h, hipMalloc(&h->d_copy_seeds, N * sizeof(uint64_t)));
+  if (!h->d_copy_idx && dev_alloc(h, &h->d_copy_idx, 2 * N * sizeof(int32_t))) return -1;
+  if (seeds && !h->d_copy_seeds && dev_alloc(h, &h->d_copy_seeds, N * sizeof(uint64_t))) return -1;
   HIPCHK(h, hipMemcpyAsync(h->d_copy_idx, src, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipMemcpyAsync(h->d_copy_idx + N, dst, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
   if (seeds) HIPCHK(h, hipMemcpyAsync(h->d_copy_seeds, seeds, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
@@ -948,19 +895,11 @@ int cc4_host_stats(cc4_handle* h, double* out /* [5] */) {
 
 int cc4_get_state(cc4_handle* h, int32_t env, void* buf) {
   if (env < 0 || env >= h->cfg.num_envs) { h->err = "cc4_get_state: env out of range"; return -2; }
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  if (join_groups(h)) return -1;
-  HIPCHK(h, hipMemcpyAsync(buf, h->d_state + env, sizeof(EnvState), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return 0;
+  return copy_to_host(h, "cc4_get_state", buf, h->d_state + env, sizeof(EnvState), hipMemcpyDeviceToHost);
 }
 int cc4_get_states(cc4_handle* h, int32_t first, int32_t count, void* buf) {
   if (first < 0 || count < 0 || first + count > h->cfg.num_envs) { h->err = "cc4_get_states: range out of the batch"; return -2; }
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  if (join_groups(h)) return -1;
-  if (count) HIPCHK(h, hipMemcpyAsync(buf, h->d_state + first, (size_t)count * sizeof(EnvState), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return 0;
+  return copy_to_host(h, "cc4_get_states", buf, h->d_state + first, (size_t)count * sizeof(EnvState), hipMemcpyDeviceToHost);
 }
 int cc4_set_state(cc4_handle* h, int32_t env, const void* buf) {
   h->prev_valid = false;        // (also every cc4_edit_state, which writes the rows back through here)
@@ -973,8 +912,7 @@ int cc4_set_state(cc4_handle* h, int32_t env, const void* buf) {
       return -2;
     }
   }
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  if (join_groups(h)) return -1;
+  if (int rc = enter(h, "cc4_set_state")) return rc;
   HIPCHK(h, hipMemcpyAsync(h->d_state + env, buf, sizeof(EnvState), hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->full_obs_next = true;      // the observation buffer still holds the previous occupant's slowly varying values
@@ -982,19 +920,21 @@ int cc4_set_state(cc4_handle* h, int32_t env, const void* buf) {
 }
 
 size_t cc4_cold_bytes(cc4_handle* h) { return h ? h->cold_row : 0; }
+int FetchedRow::fetch(cc4_handle* h, int32_t env) {
+  st = static_cast<EnvState*>(malloc(sizeof(EnvState)));
+  cold = static_cast<EnvCold*>(malloc(h->cold_row));
+  if (!st || !cold) { h->err = "no host memory for an episode's rows"; return -1; }
+  if (int rc = cc4_get_state(h, env, st)) return rc;
+  return cc4_get_cold(h, env, cold);
+}
 int cc4_get_cold(cc4_handle* h, int32_t env, void* buf) {
   if (env < 0 || env >= h->cfg.num_envs) { h->err = "cc4_get_cold: env out of range"; return -2; }
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  if (join_groups(h)) return -1;
-  HIPCHK(h, hipMemcpyAsync(buf, cold_at(h->d_cold, (size_t)env, h->cold_row), h->cold_row, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return 0;
+  return copy_to_host(h, "cc4_get_cold", buf, cold_at(h->d_cold, (size_t)env, h->cold_row), h->cold_row, hipMemcpyDeviceToHost);
 }
 int cc4_set_cold(cc4_handle* h, int32_t env, const void* buf) {
   h->prev_valid = false;
   if (env < 0 || env >= h->cfg.num_envs) { h->err = "cc4_set_cold: env out of range"; return -2; }
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  if (join_groups(h)) return -1;
+  if (int rc = enter(h, "cc4_set_cold")) return rc;
   HIPCHK(h, hipMemcpyAsync(cold_at(h->d_cold, (size_t)env, h->cold_row), buf, h->cold_row, hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return 0;
@@ -1002,24 +942,15 @@ int cc4_set_cold(cc4_handle* h, int32_t env, const void* buf) {
 
 int cc4_get_topology(cc4_handle* h, int32_t env, uint8_t* out) {
   if (env < 0 || env >= h->cfg.num_envs) { h->err = "cc4_get_topology: env out of range"; return -2; }
-  EnvState* tmp = (EnvState*)malloc(sizeof(EnvState));
-  HostStatic* hs = (HostStatic*)malloc(sizeof(HostStatic) * MAXH);
-  int rc = cc4_get_state(h, env, tmp);
-  if (rc == 0) {
-    hipError_t e = hipMemcpy(hs, cold_at(h->d_cold, (size_t)env, h->cold_row)->hs, sizeof(HostStatic) * MAXH, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) { h->err = std::string("cc4_get_topology: ") + hipGetErrorString(e); rc = -1; }
-  }
-  if (rc == 0) {
-    for (int i = 0; i < NSUB; ++i) { out[i] = tmp->cidr_octet[i]; out[9 + i] = tmp->n_users[i]; out[18 + i] = tmp->n_servers[i]; }
-    for (int i = 0; i < MAXH; ++i) { out[27 + 2 * i] = bit_get(tmp->exists, i) ? 1 : 0; out[28 + 2 * i] = hs[i].ip_octet; }
-  }
-  free(tmp); free(hs);
-  return rc;
+  FetchedRow r;
+  if (int rc = r.fetch(h, env)) return rc;
+  for (int i = 0; i < NSUB; ++i) { out[i] = r.st->cidr_octet[i]; out[9 + i] = r.st->n_users[i]; out[18 + i] = r.st->n_servers[i]; }
+  for (int i = 0; i < MAXH; ++i) { out[27 + 2 * i] = bit_get(r.st->exists, i) ? 1 : 0; out[28 + 2 * i] = r.cold->hs[i].ip_octet; }
+  return 0;
 }
 
 int cc4_enable_event_log(cc4_handle* h, int32_t enable) {
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  if (join_groups(h)) return -1;
+  if (int rc = enter(h, "cc4_enable_event_log")) return rc;
   hipLaunchKernelGGL(k_set_evlog, dim3((h->cfg.num_envs + 255) / 256), dim3(256), 0, h->stream, h->d_cold, h->cold_row, h->cfg.num_envs, enable ? 1u : 0u);
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1037,9 +968,7 @@ int cc4_keep_previous(cc4_handle* h, int32_t on) {
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   const size_t n = (size_t)h->cfg.num_envs;
   if (on && !h->d_prev_state) {
-    HIPCHK(h, hipMalloc(&h->d_prev_state, n * sizeof(EnvState)));
-    HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&h->d_prev_cold), n * h->cold_row));
-    HIPCHK(h, hipMalloc(&h->d_prev_out, h->out_bytes));
+    if (dev_alloc(h, &h->d_prev_state, n * sizeof(EnvState)) || dev_alloc(h, &h->d_prev_cold, n * h->cold_row) || dev_alloc(h, &h->d_prev_out, h->out_bytes)) return -1;
   }
   h->keep_prev = on != 0;
   h->prev_valid = false;
@@ -1047,8 +976,7 @@ int cc4_keep_previous(cc4_handle* h, int32_t on) {
 }
 int cc4_replay_logged(cc4_handle* h) {
   if (!h->keep_prev) { h->err = "cc4_replay_logged: cc4_keep_previous is off"; return -2; }
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  if (join_groups(h)) return -1;
+  if (int rc = enter(h, "cc4_replay_logged")) return rc;
   const int n = h->cfg.num_envs;
   if (!h->prev_valid) {      // no step since the reset (or steps whose inputs are gone): an enabled, empty log
     hipLaunchKernelGGL(k_set_evlog, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->d_cold, h->cold_row, n, 1u);
@@ -1080,17 +1008,11 @@ int cc4_replay_logged(cc4_handle* h) {
 }
 int64_t cc4_get_true_state(cc4_handle* h, int32_t env, char* json, size_t cap) {
   if (env < 0 || env >= h->cfg.num_envs) { h->err = "cc4_get_true_state: env out of range"; return -2; }
-  EnvState* st = (EnvState*)malloc(sizeof(EnvState));
-  EnvCold* cold = (EnvCold*)malloc(h->cold_row);
-  int64_t rc = cc4_get_state(h, env, st);
-  if (rc == 0) rc = cc4_get_cold(h, env, cold);
-  if (rc == 0) {
-    std::string doc = export_true_state(*st, *cold);
-    rc = (int64_t)doc.size() + 1;
-    if (json && cap >= doc.size() + 1) memcpy(json, doc.c_str(), doc.size() + 1);
-  }
-  free(st); free(cold);
-  return rc;
+  FetchedRow r;
+  if (int rc = r.fetch(h, env)) return rc;
+  const std::string doc = export_true_state(*r.st, *r.cold);
+  if (json && cap >= doc.size() + 1) memcpy(json, doc.c_str(), doc.size() + 1);
+  return (int64_t)doc.size() + 1;
 }
 
 }  // extern "C"

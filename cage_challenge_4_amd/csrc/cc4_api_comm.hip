@@ -13,11 +13,11 @@ int xchg_begin(cc4_handle* h, int k, XchgArgs* x) {
   const size_t groups = (size_t)(xchg_groups32_alloc(h->cfg.num_envs) > h->cus ? xchg_groups32_alloc(h->cfg.num_envs) : h->cus);
   {
     const size_t nb = (size_t)h->cfg.num_envs * OBS_PACKED;
-    if (!h->d_xslab) HIPCHK(h, hipMalloc(&h->d_xslab, nb * cc4_handle::XRING));
-    if (!h->d_xall) HIPCHK(h, hipMalloc(&h->d_xall, nb * (size_t)h->world * cc4_handle::XRING));
+    if (!h->d_xslab && dev_alloc(h, &h->d_xslab, nb * cc4_handle::XRING)) return -1;
+    if (!h->d_xall && dev_alloc(h, &h->d_xall, nb * (size_t)h->world * cc4_handle::XRING)) return -1;
   }
-  if (!h->d_xflags) { HIPCHK(h, hipMalloc(&h->d_xflags, 2 * sizeof(uint32_t))); h->xflags_clean = 0; }
-  if (!h->d_xgcnt) { HIPCHK(h, hipMalloc(&h->d_xgcnt, groups * cc4_handle::XRING * sizeof(uint32_t))); h->xflags_clean = 0; }
+  if (!h->d_xflags) { if (dev_alloc(h, &h->d_xflags, 2 * sizeof(uint32_t))) return -1; h->xflags_clean = 0; }
+  if (!h->d_xgcnt) { if (dev_alloc(h, &h->d_xgcnt, groups * cc4_handle::XRING * sizeof(uint32_t))) return -1; h->xflags_clean = 0; }
   if (ensure_watchdog_word(h)) return -1;
   *h->h_xtimeout = 0;
   if (!h->xflags_clean) {       // normally cleared behind the previous call already (xchg_end): nothing of it in front of this call's launch
@@ -91,7 +91,7 @@ int xchg_end(cc4_handle* h, int k) {
     h->last_gathered = nullptr; h->gather_buf = -1;
     if (h->d_xlog) h->xlog_n = h->xlog_n >= k ? h->xlog_n - k : 0;
     h->err = "the in-kernel exchange timed out in the last cc4_run_random_steps call (episodes intact; its all-gathers are void; per-step launches from now on)";
-    (void)hipFree(h->d_xall); h->d_xall = nullptr;      // (the gathered twin of the ring: world times the ring; the ring itself still holds the last step's rows)
+    release(h, &h->d_xall);      // (the gathered twin of the ring: world times the ring; the ring itself still holds the last step's rows)
     fprintf(stderr, "[cc4] the in-kernel exchange timed out (a step waited > %d ms for the all-gather of %d steps earlier): this handle returns to per-step launches with the exchange\n",
             h->xchg_watchdog_ms, cc4_handle::XRING);
   }
@@ -106,8 +106,7 @@ int cc4_comm_unique_id(void* id128) {
   return 0;
 }
 int cc4_comm_init(cc4_handle* h, int32_t rank, int32_t world, const void* id128) {
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  if (join_groups(h)) return -1;
+  if (int rc = enter(h, "cc4_comm_init")) return rc;
   ncclUniqueId id;
   memcpy(&id, id128, 128);
   ncclResult_t r = ncclCommInitRank(&h->comm, world, id, rank);
@@ -125,24 +124,23 @@ int cc4_comm_init(cc4_handle* h, int32_t rank, int32_t world, const void* id128)
       const int old = h->ngroups;
       configure_groups(h, ng);
       for (int g = old; g < h->ngroups; ++g) {
-        if (!h->gstream[g]) HIPCHK(h, hipStreamCreateWithFlags(&h->gstream[g], hipStreamNonBlocking));
-        if (!h->gev[g]) HIPCHK(h, hipEventCreateWithFlags(&h->gev[g], hipEventDisableTiming));
+        if (!h->gstream[g] && new_stream(h, &h->gstream[g])) return -1;
+        if (!h->gev[g] && new_event(h, &h->gev[g], hipEventDisableTiming)) return -1;
       }
       h->main_ahead = true;
     }
   }
   size_t nb = (size_t)h->cfg.num_envs * OBS_PACKED;
-  HIPCHK(h, hipStreamCreateWithFlags(&h->comm_stream, hipStreamNonBlocking));
+  if (new_stream(h, &h->comm_stream)) return -1;
   for (int b = 0; b < cc4_handle::OBS_RING; ++b) {
-    HIPCHK(h, hipMalloc(&h->d_obs8[b], nb));
-    HIPCHK(h, hipMalloc(&h->d_all_obs8[b], nb * (size_t)world));
+    if (dev_alloc(h, &h->d_obs8[b], nb) || dev_alloc(h, &h->d_all_obs8[b], nb * (size_t)world)) return -1;
     HIPCHK(h, hipMemsetAsync(h->d_obs8[b], 0, nb, h->stream));
-    for (int g = 0; g < h->ngroups; ++g) HIPCHK(h, hipEventCreateWithFlags(&h->ev_step[b][g], hipEventDisableTiming));
-    HIPCHK(h, hipEventCreateWithFlags(&h->ev_comm[b], hipEventDisableTiming));
+    for (int g = 0; g < h->ngroups; ++g) if (new_event(h, &h->ev_step[b][g], hipEventDisableTiming)) return -1;
+    if (new_event(h, &h->ev_comm[b], hipEventDisableTiming)) return -1;
   }
   // (the ring of step slabs the one-launch kernels write, XchgArgs, and its gathered twin -- 32 x (1 + world) x N x 148 B -- are allocated by
   // the first call that takes a one-launch form: xchg_begin)
-  HIPCHK(h, hipEventCreateWithFlags(&h->xev, hipEventDisableTiming));
+  if (new_event(h, &h->xev, hipEventDisableTiming)) return -1;
   int can_wait = 0;
   (void)hipDeviceGetAttribute(&can_wait, hipDeviceAttributeCanUseStreamWaitValue, h->cfg.device_id);
   h->xchg_on = can_wait != 0;
@@ -174,10 +172,10 @@ int cc4_debug_gather_log(cc4_handle* h, int32_t steps) {
   if (!h->comm) { h->err = "cc4_debug_gather_log: cc4_comm_init was not called"; return -2; }
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   HIPCHK(h, hipStreamSynchronize(h->comm_stream));
-  if (h->d_xlog) { (void)hipFree(h->d_xlog); h->d_xlog = nullptr; }
+  release(h, &h->d_xlog);
   h->xlog_cap = 0; h->xlog_n = 0;
   if (steps > 0) {
-    HIPCHK(h, hipMalloc(&h->d_xlog, (size_t)steps * h->world * h->cfg.num_envs * OBS_PACKED));
+    if (dev_alloc(h, &h->d_xlog, (size_t)steps * h->world * h->cfg.num_envs * OBS_PACKED)) return -1;
     h->xlog_cap = steps;
   }
   return 0;
@@ -270,7 +268,7 @@ int cc4_unpack_obs_device(cc4_handle* h, uint8_t** d_obs_u8) {
   if (!h->last_gathered) { h->err = "cc4_unpack_obs_device: no all-gather has been issued"; return -2; }
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   const size_t rows = (size_t)h->world * h->cfg.num_envs;
-  if (!h->d_unpacked) HIPCHK(h, hipMalloc(&h->d_unpacked, rows * OBS_TOTAL));
+  if (!h->d_unpacked && dev_alloc(h, &h->d_unpacked, rows * OBS_TOTAL)) return -1;
   hipLaunchKernelGGL(k_unpack_obs, dim3((unsigned)rows), dim3(192), 0, h->comm_stream, h->last_gathered, h->d_unpacked, (int)rows);
   HIPCHK(h, hipGetLastError());
   if (d_obs_u8) *d_obs_u8 = h->d_unpacked;

@@ -7,7 +7,7 @@
 int timeline_report(cc4_handle* h, int k, bool timed) {
   std::vector<unsigned long long> tl(4 * (size_t)h->run_grid);
   HIPCHK(h, hipMemcpy(tl.data(), h->d_timeline, tl.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-  (void)hipFree(h->d_timeline); h->d_timeline = nullptr;
+  release(h, &h->d_timeline);
 #ifdef CC4_BOUNDARY_PROF
   // the measurement build's words of a k_run_philox1 launch (bit 63 of word 0; persist_loop's tl_flush): the hand-over between two items of a wave in four parts
   { double sA = 0, sB = 0, sC = 0, sD = 0, sn = 0, items = 0, busy_ticks = 0; int nw = 0; std::vector<double> per;
@@ -86,12 +86,11 @@ int cc4_debug_rollout_state(cc4_handle* h, int64_t* out /* [22] */) {
 
 // debug: enable (buf != NULL first call allocates) / read per-episode cycle counters [N][64] (16 phase slots, then 8 per red agent)
 int cc4_debug_profile(cc4_handle* h, int enable, unsigned long long* out) {
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  if (join_groups(h)) return -1;
+  if (int rc = enter(h, "cc4_debug_profile")) return rc;
   size_t bytes = (size_t)h->cfg.num_envs * PROF_SLOTS * sizeof(unsigned long long);
-  if (enable && !h->d_prof) { HIPCHK(h, hipMalloc(&h->d_prof, bytes)); HIPCHK(h, hipMemsetAsync(h->d_prof, 0, bytes, h->stream)); }
+  if (enable && !h->d_prof) { if (dev_alloc(h, &h->d_prof, bytes)) return -1; HIPCHK(h, hipMemsetAsync(h->d_prof, 0, bytes, h->stream)); }
   if (out && h->d_prof) { HIPCHK(h, hipMemcpyAsync(out, h->d_prof, bytes, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream)); }
-  if (!enable && h->d_prof) { (void)hipFree(h->d_prof); h->d_prof = nullptr; }
+  if (!enable) release(h, &h->d_prof);
   return 0;
 }
 
@@ -107,10 +106,9 @@ int cc4_debug_stop_phase(cc4_handle* h, int phase) {
 // test hook: the persistent schedule's progress words as if `base` steps had run since they were last cleared (every episode's word = base, no
 // runner; pool_base = base) -- the wrap of persist_launch within a few steps' reach
 int cc4_debug_persist_base(cc4_handle* h, uint32_t base) {
-  if (h->rollout_k > 0) { h->err = "cc4_debug_persist_base: a rollout is in flight on this handle"; return -2; }
+  if (h->rollout_k > 0) { h->err = "cc4_debug_persist_base: a rollout is in flight on this handle"; return -2; }      // (its own, shorter sentence)
   if (base > PROGRESS_CLEAR_AT) { char msg[64]; snprintf(msg, sizeof msg, "cc4_debug_persist_base: base 0 .. %#x", PROGRESS_CLEAR_AT); h->err = msg; return -2; }
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  if (join_groups(h)) return -1;
+  if (int rc = enter(h, "cc4_debug_persist_base")) return rc;
   if (h->persist_state == 0) { if (persist_setup(h)) return -1; }
   if (h->persist_state != 1) { h->err = "cc4_debug_persist_base: this handle has no persistent kernel"; return -2; }
   HIPCHK(h, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->d_run), (int)base, (size_t)h->cfg.num_envs, h->stream));
@@ -119,8 +117,7 @@ int cc4_debug_persist_base(cc4_handle* h, uint32_t base) {
   return 0;
 }
 int cc4_debug_copy_from_device(cc4_handle* h, void* host_dst, const void* device_src, size_t bytes) {
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  if (join_groups(h)) return -1;
+  if (int rc = enter(h, "cc4_debug_copy_from_device")) return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   for (int g = 0; g < 4; ++g) if (h->gpolicy[g]) HIPCHK(h, hipStreamSynchronize(h->gpolicy[g]));
   HIPCHK(h, hipMemcpy(host_dst, device_src, bytes, hipMemcpyDeviceToHost));

@@ -19,19 +19,17 @@ int cc4_rollout_begin(cc4_handle* h, int32_t k) {
   h->prev_valid = false;
   const size_t n = (size_t)h->cfg.num_envs, row = n * OBS_PACKED;
   if (!h->d_ract) {
-    HIPCHK(h, hipMalloc(&h->d_ract, 2 * n * NBLUE * sizeof(int32_t)));
-    HIPCHK(h, hipMalloc(&h->d_rready, (size_t)CC4_SLOTS * 32 * sizeof(uint32_t)));
-    HIPCHK(h, hipMalloc(&h->d_rcnt, (size_t)h->run_P * RPG_MAX * cc4_handle::XRING * sizeof(uint32_t)));
-    HIPCHK(h, hipMalloc(&h->d_rfail, sizeof(uint32_t)));
-    for (int g = 0; g < RPG_MAX; ++g) HIPCHK(h, hipStreamCreateWithFlags(&h->gpolicy[g], hipStreamNonBlocking));
+    if (dev_alloc(h, &h->d_ract, 2 * n * NBLUE * sizeof(int32_t)) || dev_alloc(h, &h->d_rready, (size_t)CC4_SLOTS * 32 * sizeof(uint32_t)) ||
+        dev_alloc(h, &h->d_rcnt, (size_t)h->run_P * RPG_MAX * cc4_handle::XRING * sizeof(uint32_t)) || dev_alloc(h, &h->d_rfail, sizeof(uint32_t))) return -1;
+    for (int g = 0; g < RPG_MAX; ++g) if (new_stream(h, &h->gpolicy[g])) return -1;
     h->policy_stream = h->gpolicy[0];
-    HIPCHK(h, hipEventCreateWithFlags(&h->rev, hipEventDisableTiming));
+    if (new_event(h, &h->rev, hipEventDisableTiming)) return -1;
     if (const char* v = getenv("CC4_ROLLOUT_WATCHDOG_MS")) h->rollout_watchdog_ms = atoi(v) > 0 ? atoi(v) : 2000;
     if (const char* v = getenv("CC4_ROLLOUT_MARGIN")) h->rollout_margin = atoi(v) >= 0 ? atoi(v) : 1;
     if (const char* v = getenv("CC4_ROLLOUT_GROUPS")) { h->rpg = atoi(v); if (h->rpg < 1) h->rpg = 1; if (h->rpg > RPG_MAX) h->rpg = RPG_MAX; }
   }
-  if (!h->d_xslab) HIPCHK(h, hipMalloc(&h->d_xslab, row * cc4_handle::XRING));
-  if (!h->d_xflags) { HIPCHK(h, hipMalloc(&h->d_xflags, 2 * sizeof(uint32_t))); }
+  if (!h->d_xslab && dev_alloc(h, &h->d_xslab, row * cc4_handle::XRING)) return -1;
+  if (!h->d_xflags && dev_alloc(h, &h->d_xflags, 2 * sizeof(uint32_t))) return -1;
   if (ensure_watchdog_word(h)) return -1;
   *h->h_xtimeout = 0;
   HIPCHK(h, hipMemsetAsync(h->d_xflags, 0, 2 * sizeof(uint32_t), h->stream));

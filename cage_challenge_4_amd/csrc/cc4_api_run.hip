@@ -137,14 +137,15 @@ int persist_setup(cc4_handle* h) {
     return 0;
   }
   if (join_groups(h)) return -1;
-  int32_t* d_count = nullptr;
-  HIPCHK(h, hipMalloc(&d_count, CC4_SLOTS * sizeof(int32_t)));
-  HIPCHK(h, hipMemsetAsync(d_count, 0, CC4_SLOTS * sizeof(int32_t), h->stream));
-  hipLaunchKernelGGL(k_discover, dim3(24 * h->cus), dim3(WAVE), 0, h->stream, d_count, 100LL * wall_khz(h) / 1000);   // ~100 us each
   std::vector<int32_t> count(CC4_SLOTS);
-  HIPCHK(h, hipMemcpyAsync(count.data(), d_count, CC4_SLOTS * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  (void)hipFree(d_count);
+  {
+    DevTemp<int32_t> d_count;
+    if (d_count.alloc(h, CC4_SLOTS * sizeof(int32_t))) return -1;
+    HIPCHK(h, hipMemsetAsync(d_count.p, 0, CC4_SLOTS * sizeof(int32_t), h->stream));
+    hipLaunchKernelGGL(k_discover, dim3(24 * h->cus), dim3(WAVE), 0, h->stream, d_count.p, 100LL * wall_khz(h) / 1000);   // ~100 us each
+    HIPCHK(h, hipMemcpyAsync(count.data(), d_count.p, CC4_SLOTS * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+  }
   std::vector<int32_t> table(CC4_SLOTS, 0);
   int P = 0;
   for (int sl = 0; sl < CC4_SLOTS; ++sl) if (count[sl] > 0) table[sl] = ++P;        // 1 + partition, in slot order: an XCD's CUs own neighbouring partitions
@@ -192,14 +193,13 @@ int persist_setup(cc4_handle* h) {
     h->persist_refused = true;
     return 0;
   }
-  if (!h->d_pool) HIPCHK(h, hipMalloc(&h->d_pool, 2 * (size_t)CC4_SLOTS * TK_STRIDE * sizeof(uint32_t)));
+  if (!h->d_pool && dev_alloc(h, &h->d_pool, 2 * (size_t)CC4_SLOTS * TK_STRIDE * sizeof(uint32_t))) return -1;
   HIPCHK(h, hipMemset(h->d_pool, 0, 2 * (size_t)CC4_SLOTS * TK_STRIDE * sizeof(uint32_t)));
   h->pool_base = 0; h->pool_parity = 0;
-  if (!h->d_slot_part) HIPCHK(h, hipMalloc(&h->d_slot_part, CC4_SLOTS * sizeof(int32_t)));
+  if (!h->d_slot_part && dev_alloc(h, &h->d_slot_part, CC4_SLOTS * sizeof(int32_t))) return -1;
   HIPCHK(h, hipMemcpy(h->d_slot_part, table.data(), CC4_SLOTS * sizeof(int32_t), hipMemcpyHostToDevice));
-  if (h->d_run) { (void)hipFree(h->d_run); h->d_run = nullptr; }
   h->run_words = (size_t)n;                                                           // the progress words
-  HIPCHK(h, hipMalloc(&h->d_run, h->run_words * sizeof(uint32_t)));
+  if (dev_alloc(h, &h->d_run, h->run_words * sizeof(uint32_t))) return -1;
   HIPCHK(h, hipMemset(h->d_run, 0, h->run_words * sizeof(uint32_t)));
   h->persist_state = 1;
   // the sampled self-check's shadow handle is created HERE, with the path itself (the first persistent call of a handle: normally a warm-up) -- a
@@ -214,7 +214,7 @@ static int run_random_steps_impl(cc4_handle* h, uint64_t seed0, uint32_t t0, int
 // from the same starting rows with per-step launches on a shadow handle, and the two outcomes are compared episode by episode.
 int verify_digest(cc4_handle* h, std::vector<uint64_t>& out) {
   const int n = h->cfg.num_envs;
-  if (!h->d_digest) HIPCHK(h, hipMalloc(&h->d_digest, 3 * (size_t)n * sizeof(uint64_t)));
+  if (!h->d_digest && dev_alloc(h, &h->d_digest, 3 * (size_t)n * sizeof(uint64_t))) return -1;
   if (join_groups(h)) return -1;
   hipLaunchKernelGGL(k_digest, dim3(n), dim3(WAVE), 0, h->stream, h->d_state, h->d_cold, h->cold_row, h->d_obs, h->d_reward, h->d_done, h->d_err, h->d_actions, h->d_digest, n);
   HIPCHK(h, hipGetLastError());
@@ -346,9 +346,13 @@ int persist_launch(cc4_handle* h, StepArgs a, int k, uint32_t t0, const XchgArgs
     HIPCHK(h, hipMemsetAsync(h->d_run, 0, h->run_words * sizeof(uint32_t), h->stream));
     h->pool_base = 0;
   }
-  unsigned long long* d_tl = nullptr;
-  if (getenv("CC4_PERSIST_TIMELINE")) { HIPCHK(h, hipMalloc(&d_tl, 4 * sizeof(unsigned long long) * (size_t)h->run_grid)); HIPCHK(h, hipMemsetAsync(d_tl, 0, 4 * sizeof(unsigned long long) * (size_t)h->run_grid, h->stream)); }
-  h->d_timeline = d_tl;
+  // (debug, CC4_PERSIST_TIMELINE: the handle's from the start, so that no path loses it; the stamps of a call nobody reported -- a rollout's -- go back here)
+  if (h->d_timeline) release(h, &h->d_timeline);
+  if (getenv("CC4_PERSIST_TIMELINE")) {
+    const size_t tl_bytes = 4 * sizeof(unsigned long long) * (size_t)h->run_grid;
+    if (dev_alloc(h, &h->d_timeline, tl_bytes)) return -1;
+    HIPCHK(h, hipMemsetAsync(h->d_timeline, 0, tl_bytes, h->stream));
+  }
   // the headline build knows its call's shape at compile time -- actions drawn in the kernel, none given, no messages, nothing of the debug or
   // exchange arguments: a call of any other shape takes the build that reads them at run time
   const bool head = !rollout && !pl && h->cfg.rng_mode != 0 && !h->comm && head_shape(a, x);
@@ -356,7 +360,7 @@ int persist_launch(cc4_handle* h, StepArgs a, int k, uint32_t t0, const XchgArgs
   ra.ticket = h->d_pool + (size_t)h->pool_parity * CC4_SLOTS * TK_STRIDE;
   ra.ticket_next = h->d_pool + (size_t)(h->pool_parity ^ 1) * CC4_SLOTS * TK_STRIDE;
   ra.base = h->pool_base;
-  ra.timeline = d_tl;
+  ra.timeline = h->d_timeline;
   h->pool_parity ^= 1; h->pool_base += (uint32_t)k;
   if (rollout) {
     ra.runs = run_split_steps(k);
@@ -383,9 +387,8 @@ int persist_launch(cc4_handle* h, StepArgs a, int k, uint32_t t0, const XchgArgs
 // the timing events of cc4_run_random_steps (cc4_handle::evs): at least `count` of them
 static int ensure_events(cc4_handle* h, size_t count) {
   while (h->evs.size() < count) {
-    hipEvent_t e = nullptr;
-    HIPCHK(h, hipEventCreate(&e));
-    h->evs.push_back(e);
+    h->evs.push_back(nullptr);
+    if (new_event(h, &h->evs.back(), hipEventDefault)) return -1;
   }
   return 0;
 }
@@ -439,11 +442,9 @@ static int run_threaded_groups(cc4_handle* h, uint64_t seed0, uint32_t t0, int32
   const int G = h->ngroups;
   EnqPool* P = h->pool;
   if (ms_step_kernels && ensure_events(h, 2 * (size_t)G)) return -1;
-  if (h->main_ahead) {
-    HIPCHK(h, hipEventRecord(h->mev, h->stream));
-    for (int g = 1; g < G; ++g) HIPCHK(h, hipStreamWaitEvent(h->gstream[g], h->mev, 0));
-    h->main_ahead = false;
-  }
+  // (this schedule runs with a pool of ngroups - 1 >= 1 threads only -- run_random_steps_impl -- so the test of ngroups > 1 in fork_groups, which the
+  // copy that stood here did without, is always true here)
+  if (fork_groups(h)) return -1;
   P->a = step_args(h);
   P->a.rand_out = h->d_actions; P->a.rand_seed0 = seed0; P->a.rand_t = t0;
   P->a.full_obs = 0;            // (enq_run_group sets it per launch: first_full_obs)
@@ -496,11 +497,7 @@ static int run_per_step(cc4_handle* h, uint64_t seed0, uint32_t t0, int32_t k, f
       if (i == k - 1) for (int g = 0; g < G; ++g) h->tev_stop[g] = ev(0, g, 1);
     }
     if (ms_step_kernels && !attach && i % TIMED_CHUNK == 0) {
-      if (G > 1 && h->main_ahead) {     // the group streams' first event must not be recorded ahead of what their first launch waits for
-        HIPCHK(h, hipEventRecord(h->mev, h->stream));
-        for (int g = 1; g < G; ++g) HIPCHK(h, hipStreamWaitEvent(h->gstream[g], h->mev, 0));
-        h->main_ahead = false;
-      }
+      if (fork_groups(h)) return -1;     // the group streams' first event must not be recorded ahead of what their first launch waits for
       for (int g = 0; g < G; ++g) HIPCHK(h, hipEventRecord(ev(i / TIMED_CHUNK, g, 0), h->gstream[g]));
     }
     auto c0 = std::chrono::steady_clock::now();
@@ -572,7 +569,7 @@ static int run_plan_impl(cc4_handle* h, int32_t k, const int32_t* d_act, const u
   const int tpb = 256, nb = (int)((n + tpb - 1) / tpb);
   if (join_groups(h)) return -1;
   if (!h->d_plan_err) {
-    HIPCHK(h, hipMalloc(&h->d_plan_err, n * sizeof(uint32_t)));
+    if (dev_alloc(h, &h->d_plan_err, n * sizeof(uint32_t))) return -1;
     HIPCHK(h, hipMemsetAsync(h->d_plan_err, 0, n * sizeof(uint32_t), h->stream));
   }
   if (one_launch) {
@@ -583,7 +580,7 @@ static int run_plan_impl(cc4_handle* h, int32_t k, const int32_t* d_act, const u
     const PlanArgs pl{d_act, d_msg, d_rew, d_done, d_packed, h->d_plan_err};
     if (persist_launch(h, a, k, 0u, XchgArgs{}, nullptr, nullptr, false, &pl)) return -1;
     HIPCHK(h, hipGetLastError());
-    if (h->d_timeline) { (void)hipFree(h->d_timeline); h->d_timeline = nullptr; }      // (debug, CC4_PERSIST_TIMELINE: only cc4_run_random_steps reports it)
+    release(h, &h->d_timeline);      // (debug, CC4_PERSIST_TIMELINE: only cc4_run_random_steps reports it)
     h->stat_steps += k;
     h->full_obs_next = false;
     // the call's flags into the handle's error words; reward / done of the last step went into the trajectory's last row only
@@ -621,8 +618,7 @@ const char* cc4_plan_kernel_for(cc4_handle* h, int32_t k) {
 }
 int cc4_run_plan_device(cc4_handle* h, int32_t k, const int32_t* d_actions, const uint8_t* d_messages, float* d_rewards, uint8_t* d_dones, uint8_t* d_obs_packed) {
   const char* who = "cc4_run_plan_device";
-  if (h->comm) { h->err = std::string(who) + ": not on a handle with a communicator"; return -2; }
-  if (h->rollout_k > 0) { h->err = std::string(who) + ": a rollout is in flight on this handle: cc4_rollout_end first"; return -2; }
+  if (int rc = enter_refused(h, who, EN_NO_COMM | EN_NO_ROLLOUT)) return rc;
   if (k < 1 || !d_actions) { h->err = std::string(who) + ": k < 1, or no plan"; return -2; }
   if (reinterpret_cast<uintptr_t>(d_obs_packed) % 4 || reinterpret_cast<uintptr_t>(d_rewards) % 4 || reinterpret_cast<uintptr_t>(d_actions) % 4) {
     h->err = std::string(who) + ": plan, rewards and packed observation rows must be 4-byte aligned"; return -2;
@@ -640,18 +636,18 @@ int cc4_run_plan_device(cc4_handle* h, int32_t k, const int32_t* d_actions, cons
   if (shadow_seed(h)) return -1;
   cc4_handle* sh = h->shadow;
   const size_t n = (size_t)h->cfg.num_envs;
-  float* s_rew = nullptr; uint8_t* s_done = nullptr; uint8_t* s_packed = nullptr;
-  auto release = [&]() { if (s_rew) (void)hipFree(s_rew); if (s_done) (void)hipFree(s_done); if (s_packed) (void)hipFree(s_packed); };
-  if (d_rewards && hipMalloc(&s_rew, (size_t)k * n * sizeof(float)) != hipSuccess) { h->err = "CC4_PERSIST_VERIFY: no memory for the shadow's trajectory"; return -1; }
-  if (d_dones && hipMalloc(&s_done, (size_t)k * n) != hipSuccess) { release(); h->err = "CC4_PERSIST_VERIFY: no memory for the shadow's trajectory"; return -1; }
-  if (d_obs_packed && hipMalloc(&s_packed, (size_t)k * n * OBS_PACKED) != hipSuccess) { release(); h->err = "CC4_PERSIST_VERIFY: no memory for the shadow's trajectory"; return -1; }
+  DevTemp<float> t_rew; DevTemp<uint8_t> t_done, t_packed;      // the shadow's trajectory: this call's alone
+  if ((d_rewards && t_rew.alloc(h, (size_t)k * n * sizeof(float))) || (d_dones && t_done.alloc(h, (size_t)k * n)) || (d_obs_packed && t_packed.alloc(h, (size_t)k * n * OBS_PACKED))) {
+    h->err = "CC4_PERSIST_VERIFY: no memory for the shadow's trajectory"; return -1;
+  }
+  float* const s_rew = t_rew.p; uint8_t* const s_done = t_done.p; uint8_t* const s_packed = t_packed.p;
   int rc = run_plan_impl(h, k, d_actions, d_messages, d_rewards, d_dones, d_obs_packed, true);
-  if (rc) { release(); return rc; }
+  if (rc) return rc;
   rc = run_plan_impl(sh, k, d_actions, d_messages, s_rew, s_done, s_packed, false);
-  if (rc) { release(); h->err = "CC4_PERSIST_VERIFY: the shadow run failed: " + sh->err; return rc; }
-  if (plant_apply(h, s_rew, s_done, s_packed)) { release(); return -1; }
+  if (rc) { h->err = "CC4_PERSIST_VERIFY: the shadow run failed: " + sh->err; return rc; }
+  if (plant_apply(h, s_rew, s_done, s_packed)) return -1;
   std::string bad;
-  if (shadow_compare(h, bad)) { release(); return -1; }
+  if (shadow_compare(h, bad)) return -1;
   // the trajectory, a step's row at a time (both streams are drained: shadow_compare waited for them) -- whether or not the final digests differ: the
   // first step at which the recorded rows part is what places a disagreement in the call's runs, the digest's episode alone does not
   std::vector<uint8_t> ra, rb;
@@ -678,7 +674,6 @@ int cc4_run_plan_device(cc4_handle* h, int32_t k, const int32_t* d_actions, cons
                                                                     : std::string(" (the row could not be fetched)"));
     bad = bad.empty() ? traj : bad + "; " + traj;
   } else if (!bad.empty()) bad += "; no recorded trajectory row differs";
-  release();
   if (!bad.empty()) return verify_mismatch(h, std::string(cc4_plan_kernel_for(h, k)) + " and the per-step launches disagree after a plan of " + std::to_string(k) + " steps: " + bad);
   return 0;
 }
@@ -688,8 +683,7 @@ int cc4_unpack_rows_device(cc4_handle* h, int64_t rows, const uint8_t* d_packed,
   static const uintptr_t align[4] = {1, 2, 2, 4};
   if (reinterpret_cast<uintptr_t>(d_out) % align[obs_dtype]) { h->err = "cc4_unpack_rows_device: the output buffer is not aligned to its element size"; return -2; }
   if (rows == 0) return 0;
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  if (join_groups(h)) return -1;
+  if (int rc = enter(h, "cc4_unpack_rows_device")) return rc;
   const long long bytes = (long long)rows * OBS_PACKED;
   const dim3 grid((unsigned)std::max(1LL, std::min((bytes + 255) / 256, 32LL * h->cus))), block(256);
   switch (obs_dtype) {

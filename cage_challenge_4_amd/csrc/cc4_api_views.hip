@@ -19,7 +19,7 @@
 constexpr int VIEW_GO = 1;
 static int view_check(cc4_handle* h, const char* who, const char* bad, int32_t n, const void* out0, size_t align0, const void* out1, size_t align1,
                       const char* outs, const void* d_bank, int32_t capacity) {
-  if (h->rollout_k > 0) { h->err = std::string(who) + ": a rollout is in flight on this handle: cc4_rollout_end first"; return -2; }
+  if (int rc = enter_refused(h, who, EN_NO_ROLLOUT)) return rc;
   if (n < 0) { h->err = std::string(who) + ": n < 0"; return -2; }
   if (bad) { h->err = std::string(who) + ": " + bad; return -2; }
   if (n == 0) return 0;
@@ -29,9 +29,8 @@ static int view_check(cc4_handle* h, const char* who, const char* bad, int32_t n
   return VIEW_GO;
 }
 // ... and the launch: the source every view reads from, then what is particular to the view (its outputs; max_edges), one wavefront per entry.
-template <class Args, class... Rest> static int view_launch(cc4_handle* h, void (*k_view)(Args), const void* d_bank, int32_t capacity, const int32_t* d_ids, int32_t n, Rest... rest) {
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  if (join_groups(h)) return -1;
+template <class Args, class... Rest> static int view_launch(cc4_handle* h, const char* who, void (*k_view)(Args), const void* d_bank, int32_t capacity, const int32_t* d_ids, int32_t n, Rest... rest) {
+  if (int rc = enter(h, who)) return rc;
   const Args a{ViewSrc{h->d_state, h->d_cold, h->cold_row, static_cast<const uint8_t*>(d_bank), slot_bytes(h->cold_row), d_ids, n,
                        d_bank ? capacity : h->cfg.num_envs, h->cfg.steps, h->cfg.rng_mode, h->d_copy_fault}, rest...};
   hipLaunchKernelGGL(k_view, dim3(n), dim3(WAVE), 0, h->stream, a);
@@ -42,18 +41,18 @@ template <class Args, class... Rest> static int view_launch(cc4_handle* h, void 
 int cc4_state_features_device(cc4_handle* h, const void* d_bank, int32_t capacity, const int32_t* d_ids, int32_t n, uint8_t* d_hosts, int32_t* d_global) {
   const int rc = view_check(h, "cc4_state_features_device", nullptr, n, d_hosts, 16, d_global, 4,
                             "the host-feature buffer is required and must be 16-byte aligned (the episode words: 4-byte aligned or NULL)", d_bank, capacity);
-  return rc == VIEW_GO ? view_launch(h, k_state_features, d_bank, capacity, d_ids, n, d_hosts, d_global) : rc;
+  return rc == VIEW_GO ? view_launch(h, "cc4_state_features_device", k_state_features, d_bank, capacity, d_ids, n, d_hosts, d_global) : rc;
 }
 int cc4_red_view_device(cc4_handle* h, const void* d_bank, int32_t capacity, const int32_t* d_ids, int32_t n, uint8_t* d_hosts, int32_t* d_scalars) {
   const int rc = view_check(h, "cc4_red_view_device", nullptr, n, d_hosts, 16, d_scalars, 4,
                             "the host-view buffer is required and must be 16-byte aligned (the agent words: 4-byte aligned or NULL)", d_bank, capacity);
-  return rc == VIEW_GO ? view_launch(h, k_red_view, d_bank, capacity, d_ids, n, d_hosts, d_scalars) : rc;
+  return rc == VIEW_GO ? view_launch(h, "cc4_red_view_device", k_red_view, d_bank, capacity, d_ids, n, d_hosts, d_scalars) : rc;
 }
 // of the cold rows: the event log and the sus lists
 int cc4_blue_view_device(cc4_handle* h, const void* d_bank, int32_t capacity, const int32_t* d_ids, int32_t n, uint8_t* d_hosts, int32_t* d_scalars) {
   const int rc = view_check(h, "cc4_blue_view_device", nullptr, n, d_hosts, 8, d_scalars, 4,
                             "the host-view buffer is required and must be 8-byte aligned (the agent words: 4-byte aligned or NULL)", d_bank, capacity);
-  return rc == VIEW_GO ? view_launch(h, k_blue_view, d_bank, capacity, d_ids, n, d_hosts, d_scalars) : rc;
+  return rc == VIEW_GO ? view_launch(h, "cc4_blue_view_device", k_blue_view, d_bank, capacity, d_ids, n, d_hosts, d_scalars) : rc;
 }
 // of the hot rows exists and step_count, of the cold rows the event log
 int cc4_blue_edges_device(cc4_handle* h, const void* d_bank, int32_t capacity, const int32_t* d_ids, int32_t n, int32_t max_edges, int32_t* d_edges,
@@ -61,13 +60,13 @@ int cc4_blue_edges_device(cc4_handle* h, const void* d_bank, int32_t capacity, c
   const std::string range = "max_edges must be 1 .. " + std::to_string((int)BE_MAX);
   const int rc = view_check(h, "cc4_blue_edges_device", max_edges < 1 || max_edges > BE_MAX ? range.c_str() : nullptr, n, d_edges, 16, d_counts, 4,
                             "the edge buffer is required and must be 16-byte aligned (the counts: 4-byte aligned or NULL)", d_bank, capacity);
-  return rc == VIEW_GO ? view_launch(h, k_blue_edges, d_bank, capacity, d_ids, n, (int)max_edges, d_edges, d_counts) : rc;
+  return rc == VIEW_GO ? view_launch(h, "cc4_blue_edges_device", k_blue_edges, d_bank, capacity, d_ids, n, (int)max_edges, d_edges, d_counts) : rc;
 }
 // of the cold rows: the record
 int cc4_reward_terms_device(cc4_handle* h, const void* d_bank, int32_t capacity, const int32_t* d_ids, int32_t n, int32_t* d_terms, int32_t* d_words) {
   const int rc = view_check(h, "cc4_reward_terms_device", nullptr, n, d_terms, 16, d_words, 16,
                             "the terms buffer is required and must be 16-byte aligned (the words: 16-byte aligned or NULL)", d_bank, capacity);
-  return rc == VIEW_GO ? view_launch(h, k_reward_terms, d_bank, capacity, d_ids, n, d_terms, d_words) : rc;
+  return rc == VIEW_GO ? view_launch(h, "cc4_reward_terms_device", k_reward_terms, d_bank, capacity, d_ids, n, d_terms, d_words) : rc;
 }
 // of the hot rows exists and the agents' busy bytes; beside the rows one input, the logits.  The refusals of its own, in their order:
 static const char* sample_bad(int32_t dtype, const void* logits, float temperature, int32_t flags) {
@@ -81,7 +80,7 @@ int cc4_sample_actions_device(cc4_handle* h, const void* d_bank, int32_t capacit
                               uint64_t seed0, uint32_t t, float temperature, int32_t flags, int32_t* d_actions, float* d_stats) {
   const int rc = view_check(h, "cc4_sample_actions_device", sample_bad(logits_dtype, d_logits, temperature, flags), n, d_actions, 4, d_stats, 4,
                             "the action buffer is required and must be 4-byte aligned (the stats: 4-byte aligned or NULL)", d_bank, capacity);
-  return rc == VIEW_GO ? view_launch(h, k_sample_actions, d_bank, capacity, d_ids, n, d_logits, (int)logits_dtype, seed0, t, 1.0f / temperature, (int)flags,
+  return rc == VIEW_GO ? view_launch(h, "cc4_sample_actions_device", k_sample_actions, d_bank, capacity, d_ids, n, d_logits, (int)logits_dtype, seed0, t, 1.0f / temperature, (int)flags,
                                      d_actions, d_stats) : rc;
 }
 
@@ -89,11 +88,9 @@ int cc4_sample_actions_device(cc4_handle* h, const void* d_bank, int32_t capacit
 // none-records, ext_seen set -- so launch_step and the `plain` tests of cc4_api_run.hip select the full builds and pass a.ext with no condition of their own.
 int cc4_enable_reward_terms(cc4_handle* h, int32_t enable) {
   const char* who = "cc4_enable_reward_terms";
-  if (h->rollout_k > 0) { h->err = std::string(who) + ": a rollout is in flight on this handle: cc4_rollout_end first"; return -2; }
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  if (join_groups(h)) return -1;
+  if (int rc = enter(h, who, EN_NO_ROLLOUT)) return rc;
   if (enable) {
-    if (!h->d_ext) HIPCHK(h, hipMalloc(&h->d_ext, (size_t)h->cfg.num_envs * EXT_PER_ENV * sizeof(ExtAct)));
+    if (!h->d_ext && dev_alloc(h, &h->d_ext, (size_t)h->cfg.num_envs * EXT_PER_ENV * sizeof(ExtAct))) return -1;
     if (!h->ext_seen || h->ext_dirty || h->ext_green_dirty) {
       HIPCHK(h, hipMemsetAsync(h->d_ext, 0xFF, (size_t)h->cfg.num_envs * EXT_PER_ENV * sizeof(ExtAct), h->stream));     // type -1 everywhere: nothing submitted
       h->ext_dirty = false; h->ext_green_dirty = false;
@@ -108,19 +105,8 @@ int cc4_enable_reward_terms(cc4_handle* h, int32_t enable) {
 int cc4_reward_terms_enabled(cc4_handle* h) { return h && h->terms_on ? 1 : 0; }
 
 // ---- the same definitions on the host, from one hot row and (for the views that read it, optionally) its cold row -- cc4_get_state / cc4_get_cold, a
-// checkpoint: no device, no handle.  The caller's bytes may sit at any address, so the hot row and the parts of the cold row a view reads are copied
-// into aligned memory: RowCopy owns the copies and frees them on every path.
-struct RowCopy {
-  EnvState* s = nullptr;
-  EvLog* lg = nullptr; uint32_t* sus = nullptr; RewardRec* rwd = nullptr;      // null without a cold row
-  ~RowCopy() { free(s); free(lg); free(sus); free(rwd); }
-};
+// checkpoint: no device, no handle, through aligned copies of what a view reads (RowCopy, row_copy: cc4_host.h).
 enum : unsigned { RC_EVLOG = 1, RC_SUS = 2, RC_RWD = 4 };
-static void* row_copy(const void* src, size_t bytes, size_t align) {
-  void* p = aligned_alloc(align, (bytes + align - 1) / align * align);
-  if (p) memcpy(p, src, bytes);
-  return p;
-}
 // 0, -1 (no memory) or -2 (no such episode length).  steps: null for a view that takes none; else <= 0 becomes the length the row itself was generated
 // for, and it sizes the sus lists.  parts: what of the cold row the view reads.
 static int row_copies(RowCopy& r, const void* hot_row, const void* cold_row, int32_t* steps, unsigned parts) {

@@ -1,5 +1,6 @@
-// cc4_host.h -- what the host-side translation units of libcc4.so share (cc4_api*.hip; no kernel unit includes it): the handle, the enqueue
-// threads' block, and the helpers that are called across units.  Those are part of no ABI: hidden, so that libcc4.so exports the C ABI only.
+// cc4_host.h -- what the host-side translation units of libcc4.so share (cc4_api*.hip; no kernel unit includes it): the handle, who owns what it
+// allocates (dev_alloc .. release over cc4_owned.h: the only place that allocates or frees device memory, pinned memory, events and streams), the
+// enqueue threads' block, and the helpers that are called across units.  Those are part of no ABI: hidden, so that libcc4.so exports the C ABI only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -10,6 +11,7 @@
 #include <string>
 #include <chrono>
 #include <vector>
+#include <deque>
 #include <map>
 #include <algorithm>
 #include <thread>
@@ -22,10 +24,21 @@
 #include "cc4_kernel_decls.h"
 #include "cc4_export.h"
 #include "cc4_digest.h"
+#include "cc4_owned.h"
 #define CC4_HOST __attribute__((visibility("hidden")))
+
+// the runtime's releasers for the owner of a handle's resources (cc4_handle::own), in the order of OwnedKind
+inline void free_device(void* p) { (void)hipFree(p); }
+inline void free_pinned(void* p) { (void)hipHostFree(p); }
+inline void free_event(void* p) { (void)hipEventDestroy(static_cast<hipEvent_t>(p)); }
+inline void free_stream(void* p) { (void)hipStreamDestroy(static_cast<hipStream_t>(p)); }
 
 struct cc4_handle {
   cc4_config cfg;
+  // every device block, pinned block, event and stream below is registered here by the call that creates it (dev_alloc, pin_alloc, new_event,
+  // new_stream), wherever and whenever that is; cc4_destroy releases the list.  Not registered, because nothing frees them: pointers INTO a block (d_msgs,
+  // d_reward, d_err, d_done, d_copy_fault), device addresses of pinned memory (d_xtimeout; d_actions and d_obs of a small handle), second names (gstream[0], tev_*).
+  OwnedList own{{free_device, free_pinned, free_event, free_stream}, {}};
   hipStream_t stream = nullptr;
   EnvState* d_state = nullptr; EnvCold* d_cold = nullptr;
   size_t cold_row = 0;             // bytes per cold row: fixed part + the containers sized from cfg.steps (cold_row_bytes)
@@ -76,7 +89,7 @@ struct cc4_handle {
   int glo[MAX_GROUPS + 1] = {};                  // group g = episodes [glo[g], glo[g + 1])
   hipStream_t gstream[MAX_GROUPS] = {};          // gstream[0] == stream
   hipEvent_t gev[MAX_GROUPS] = {};               // group stream -> main stream ordering (join_groups)
-  hipEvent_t mev = nullptr;                      // main stream -> group streams ordering (fork_groups)
+  hipEvent_t mev = nullptr;                      // main stream -> group streams ordering: recorded and waited for in fork_groups (cc4_api.hip), nowhere else
   hipEvent_t ev_wait = nullptr, ev_signal = nullptr;   // a caller's stream -> main stream (cc4_stream_wait), main stream -> a caller's stream (cc4_stream_signal)
   bool auto_groups = true;                       // the number of groups is the library's choice (no CC4_GROUPS)
   bool groups_busy = false;                      // a group stream other than the main one may hold unfinished step launches
@@ -183,8 +196,8 @@ struct cc4_handle {
   uint32_t* d_claim = nullptr; uint32_t* d_copy_fault = nullptr; uint8_t* d_mask_stale = nullptr;
   int32_t* d_copy_idx = nullptr; uint64_t* d_copy_seeds = nullptr;
   int8_t* d_pol = nullptr;       // [6 n] staging of the host-array surface of the per-episode classes (cc4_set_policies: three [n] inputs; cc4_get_policies: two [n][3] outputs)
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  std::vector<hipEvent_t> evs;                   // timing events of cc4_run_random_steps: [group][2 * timed group of launches + {start, stop}]
+  std::deque<hipEvent_t> evs;                    // timing events of cc4_run_random_steps: [group][2 * timed group of launches + {start, stop}] (a deque: its elements are
+                                                 // owned fields, and they stay where they are when it grows)
   std::string err;
 };
 
@@ -196,6 +209,45 @@ struct cc4_handle {
       return -1;                                                                               \
     }                                                                                          \
   } while (0)
+
+// ---- what a handle allocates (cc4_handle::own).  The field is registered before it is filled, so a failure anywhere later still finds it; a field
+// that holds something already gives that back first (the free-and-reallocate sites: d_run, d_xlog, d_timeline).  0 or -1 with h->err set.
+template <class T> void** own_field(cc4_handle* h, T** field, OwnedKind kind) {
+  void** const f = reinterpret_cast<void**>(field);
+  h->own.add(f, kind); h->own.release(f);
+  return f;
+}
+template <class T> int dev_alloc(cc4_handle* h, T** field, size_t bytes) { HIPCHK(h, hipMalloc(own_field(h, field, OWN_DEVICE), bytes)); return 0; }
+template <class T> int pin_alloc(cc4_handle* h, T** field, size_t bytes) { HIPCHK(h, hipHostMalloc(own_field(h, field, OWN_PINNED), bytes, hipHostMallocDefault)); return 0; }
+inline int new_event(cc4_handle* h, hipEvent_t* ev, unsigned flags) { own_field(h, ev, OWN_EVENT); HIPCHK(h, hipEventCreateWithFlags(ev, flags)); return 0; }
+inline int new_stream(cc4_handle* h, hipStream_t* st) { own_field(h, st, OWN_STREAM); HIPCHK(h, hipStreamCreateWithFlags(st, hipStreamNonBlocking)); return 0; }
+template <class T> void release(cc4_handle* h, T** field) { h->own.release(reinterpret_cast<void**>(field)); }
+// a device block that lives as long as one call: freed on every path out of it
+CC4_HOST extern std::atomic<int64_t> g_scoped_blocks;      // how many of them exist (cc4_debug_live_resources)
+template <class T> struct DevTemp {
+  T* p = nullptr;
+  DevTemp() = default;
+  DevTemp(const DevTemp&) = delete;
+  ~DevTemp() { if (p) { (void)hipFree(p); g_scoped_blocks.fetch_sub(1); } }
+  int alloc(cc4_handle* h, size_t bytes) { HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&p), bytes)); g_scoped_blocks.fetch_add(1); return 0; }
+};
+// ---- host copies of rows, freed on every path.  RowCopy: a caller's bytes (cc4_get_state, a checkpoint) may sit at any address, so what a host-side definition
+// reads is copied into aligned memory (cc4_api_views.hip row_copies; the cold parts are null without a cold row).  FetchedRow: one episode's rows out of a handle.
+struct RowCopy {
+  EnvState* s = nullptr;
+  EvLog* lg = nullptr; uint32_t* sus = nullptr; RewardRec* rwd = nullptr;
+  ~RowCopy() { free(s); free(lg); free(sus); free(rwd); }
+};
+inline void* row_copy(const void* src, size_t bytes, size_t align, size_t room = 0) {      // room: the block's size where it is more than the bytes copied
+  void* p = aligned_alloc(align, (std::max(bytes, room) + align - 1) / align * align);
+  if (p) memcpy(p, src, bytes);
+  return p;
+}
+struct FetchedRow {
+  EnvState* st = nullptr; EnvCold* cold = nullptr;
+  ~FetchedRow() { free(st); free(cold); }
+  CC4_HOST int fetch(cc4_handle* h, int32_t env);      // 0, or what cc4_get_state / cc4_get_cold returned (-1 as well without memory)
+};
 
 // ---- one enqueue thread per group stream (cc4_run_random_steps without a communicator).  The groups of a batch never wait for each
 // other, so their launches need not come from one thread: the first launch on a stream that has been synchronised costs the calling
@@ -217,7 +269,14 @@ constexpr int PIN_MAX_ENVS = 4096;
 
 // cc4_api.hip: stream ordering, the launches of one step, what a handle asks the device once
 CC4_HOST void configure_groups(cc4_handle* h, int ng);
+// The prologue of an entry point.  enter_refused: the refusals the entry point asks for, -2 with `who` in front of the reason, or 0.  enter: those, then
+// the handle's device and join_groups (-1).  An entry point whose own argument checks stand between its refusals and the join calls the two parts itself.
+enum : unsigned { EN_NO_ROLLOUT = 1, EN_NO_COMM = 2 };
+CC4_HOST int enter_refused(cc4_handle* h, const char* who, unsigned refuse);
+CC4_HOST int enter(cc4_handle* h, const char* who, unsigned refuse = 0);
 CC4_HOST int join_groups(cc4_handle* h);
+CC4_HOST int fork_groups(cc4_handle* h);
+CC4_HOST int copy_to_host(cc4_handle* h, const char* who, void* dst, const void* src, size_t bytes, hipMemcpyKind kind);
 CC4_HOST int sync_all(cc4_handle* h);
 CC4_HOST int wall_khz(cc4_handle* h);
 CC4_HOST int ensure_watchdog_word(cc4_handle* h);

@@ -88,6 +88,11 @@ int cc4_debug_digest(cc4_handle* h, uint64_t* out /* [N][3] */);
  * `step` steps or fewer, a plan call that does not record that row -- steps nothing, disarms it and returns -2. */
 int cc4_debug_verify_plant(cc4_handle* h, int32_t part, int32_t env, int64_t offset, int32_t step);
 
+/* What the handles of this process hold: out[0] device blocks, out[1] pinned host blocks, out[2] events, out[3] streams -- every live handle's (shadow
+ * handles of the self-check among them) and the call-local device blocks of calls in flight.  A handle registers what it allocates, whichever call
+ * does so and however late, and cc4_destroy releases all of it: the counts are back where they stood once the handles made since are destroyed. */
+int cc4_debug_live_resources(int64_t out[4]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,10 +6,9 @@ sanitizers and run as a child process (never loaded into Python).  The row, the 
 their size.  Exit status 0: all agreed."""
 import os
 import re
-import shutil
-import subprocess
 
 from conftest import ROOT
+from cpp_check import build_and_run
 
 SRC = os.path.join(ROOT, 'tests', 'cpp', 'blue_edges_check.cpp')
 
@@ -62,23 +61,6 @@ def test_python_entry_points_check_max_edges():
     assert (edges == -1).all() and counts.tolist() == [0, 0, 0, 0, 0, 0, 0, 4]
 
 
-def _compiler():
-    for cxx in (os.environ.get('CXX'), 'g++', 'c++', 'clang++'):
-        if cxx and shutil.which(cxx):
-            return shutil.which(cxx)
-    return None
-
-
 def test_serial_statement_against_a_map_formulation_under_the_sanitizers(tmp_path):
-    cxx = _compiler()
-    assert cxx is not None, 'no host C++ compiler found (CXX, g++, c++, clang++): the stand-alone check cannot be built (the oracle needs one too)'
-    exe = str(tmp_path / 'blue_edges_check')
-    flags = ['-std=c++17', '-O1', '-g', '-ffp-contract=off', '-fsanitize=address,undefined', '-fno-sanitize-recover=undefined']
-    # the sanitizer runtimes inside the program itself (clang's default; gcc needs to be told), so that it depends on no shared runtime
-    if 'clang' not in subprocess.run([cxx, '--version'], capture_output=True, text=True).stdout:
-        flags += ['-static-libasan', '-static-libubsan']
-    cc = subprocess.run([cxx] + flags + ['-o', exe, SRC], capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stdout + cc.stderr
-    run = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert run.returncode == 0, run.stdout + run.stderr
+    run = build_and_run(SRC, tmp_path, required=True, timeout=300, flags=['-ffp-contract=off'])
     assert ' 0 mismatches' in run.stdout, run.stdout

@@ -7,10 +7,9 @@ sanitizers and run as a child process (never loaded into Python).  The log and t
 Exit status 0: all agreed."""
 import os
 import re
-import shutil
-import subprocess
 
 from conftest import ROOT
+from cpp_check import build_and_run
 
 SRC = os.path.join(ROOT, 'tests', 'cpp', 'blue_view_check.cpp')
 
@@ -42,23 +41,6 @@ def test_surface_header_exports_bindings_constants_and_resources():
     assert 4 * (2 * 137 + (5 * 137 + 1) // 2 + 10) <= lds <= 4 * 1280, rows[0]
 
 
-def _compiler():
-    for cxx in (os.environ.get('CXX'), 'g++', 'c++', 'clang++'):
-        if cxx and shutil.which(cxx):
-            return shutil.which(cxx)
-    return None
-
-
 def test_serial_statement_on_crafted_rows_under_the_sanitizers(tmp_path):
-    cxx = _compiler()
-    assert cxx is not None, 'no host C++ compiler found (CXX, g++, c++, clang++): the stand-alone check cannot be built (the oracle needs one too)'
-    exe = str(tmp_path / 'blue_view_check')
-    flags = ['-std=c++17', '-O1', '-g', '-ffp-contract=off', '-fsanitize=address,undefined', '-fno-sanitize-recover=undefined']
-    # the sanitizer runtimes inside the program itself (clang's default; gcc needs to be told), so that it depends on no shared runtime
-    if 'clang' not in subprocess.run([cxx, '--version'], capture_output=True, text=True).stdout:
-        flags += ['-static-libasan', '-static-libubsan']
-    cc = subprocess.run([cxx] + flags + ['-o', exe, SRC], capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stdout + cc.stderr
-    run = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert run.returncode == 0, run.stdout + run.stderr
+    run = build_and_run(SRC, tmp_path, required=True, timeout=300, flags=['-ffp-contract=off'])
     assert ' 0 mismatches' in run.stdout, run.stdout

@@ -18,15 +18,13 @@ at most one handed-over entry for each session another agent's exploit created i
 exploit each): 16 + 5 < MAX_OBS.  test_obs_list_is_cleared_before_it_is_written pins the first half of that argument."""
 import json
 import os
-import shutil
-import subprocess
-import time
 
 import numpy as np
 import pytest
 
 import capacity_util as U
 from oracle_binding import OracleVecEnv, random_actions
+from cpp_check import build_and_run
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SEED = 1030                # every scenario's first step does what its operation says, in both RNG modes (see the module docstring)
@@ -210,26 +208,8 @@ def test_long_runs_of_every_scenario_report_where_flags_come_up(crafted, capsys)
     ora.close()
 
 
-def _compiler():
-    for cxx in (os.environ.get('CXX'), 'g++', 'c++', 'clang++'):
-        if cxx and shutil.which(cxx):
-            return shutil.which(cxx)
-    return None
-
-
 def test_capacity_states_under_sanitizers(tmp_path, capsys):
-    cxx = _compiler()
-    if cxx is None:
-        pytest.skip('no host C++ compiler found (CXX, g++, c++, clang++): the stand-alone check cannot be built')
-    exe = str(tmp_path / 'capacity_check')
-    flags = ['-std=c++17', '-O1', '-g', '-ffp-contract=off', '-fsanitize=address,undefined', '-fno-sanitize-recover=undefined']
-    if 'clang' not in subprocess.run([cxx, '--version'], capture_output=True, text=True).stdout:
-        flags += ['-static-libasan', '-static-libubsan']
-    cc = subprocess.run([cxx] + flags + ['-o', exe, os.path.join(ROOT, 'tests', 'cpp', 'capacity_check.cpp')], capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stdout + cc.stderr
-    t0 = time.time()
-    run = subprocess.run([exe], capture_output=True, text=True, timeout=600)
-    assert run.returncode == 0, run.stdout[-4000:] + run.stderr[-8000:]
+    run = build_and_run(os.path.join(ROOT, 'tests', 'cpp', 'capacity_check.cpp'), tmp_path, required=False, timeout=600, flags=['-ffp-contract=off'])
     assert ' 0 failures' in run.stdout and 'E_PROC ' in run.stdout, run.stdout
     with capsys.disabled():
-        print(f'\n  {run.stdout.strip().splitlines()[-1]} ({time.time() - t0:.1f} s)', end='')
+        print(f'\n  {run.stdout.strip().splitlines()[-1]} ({run.seconds:.1f} s)', end='')

@@ -5,33 +5,14 @@ with the address and undefined-behaviour sanitizers and run as a child process (
 0..255, both policies); the reservation over all 64 Exploit sets x pools whose next free records straddle every
 word boundary, pools with 0..7 free records and random fills; the Impact sum over all phases x subnets x 64 sets.  Exit status 0: all agreed."""
 import os
-import shutil
-import subprocess
 
-import pytest
+from cpp_check import build_and_run
+
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, 'tests', 'cpp', 'fsm_tail_forms_check.cpp')
 
 
-def _compiler():
-    for cxx in (os.environ.get('CXX'), 'g++', 'c++', 'clang++'):
-        if cxx and shutil.which(cxx):
-            return shutil.which(cxx)
-    return None
-
-
 def test_fsm_tables_and_lane_forms_equal_their_serial_forms(tmp_path):
-    cxx = _compiler()
-    if cxx is None:
-        pytest.skip('no host C++ compiler found (CXX, g++, c++, clang++): the stand-alone check cannot be built')
-    exe = str(tmp_path / 'fsm_tail_forms_check')
-    flags = ['-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=undefined']
-    # the sanitizer runtimes inside the program itself (clang's default; gcc needs to be told), so that it depends on no shared runtime
-    if 'clang' not in subprocess.run([cxx, '--version'], capture_output=True, text=True).stdout:
-        flags += ['-static-libasan', '-static-libubsan']
-    cc = subprocess.run([cxx] + flags + ['-o', exe, SRC], capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stdout + cc.stderr
-    run = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert run.returncode == 0, run.stdout + run.stderr
+    run = build_and_run(SRC, tmp_path, required=False, timeout=300)
     assert ' 0 mismatches' in run.stdout, run.stdout

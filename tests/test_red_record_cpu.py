@@ -8,10 +8,9 @@ cc4_step_ex over a grid of types, hosts and args, the record's bytes member by m
 row from elsewhere (list entries past the pool, hosts past the table, lengths past the lists) is never read past.  Exit status 0: all agreed."""
 import os
 import re
-import shutil
-import subprocess
 
 from conftest import ROOT
+from cpp_check import build_and_run
 
 SRC = os.path.join(ROOT, 'tests', 'cpp', 'red_record_check.cpp')
 
@@ -41,23 +40,6 @@ def test_surface_header_exports_bindings_constants_and_resources():
         assert re.search(r'scratch\s+0 vgpr_spill\s+0 sgpr_spill\s+0 ', r[0]), r[0]
 
 
-def _compiler():
-    for cxx in (os.environ.get('CXX'), 'g++', 'c++', 'clang++'):
-        if cxx and shutil.which(cxx):
-            return shutil.which(cxx)
-    return None
-
-
 def test_record_conversion_and_host_view_under_the_sanitizers(tmp_path):
-    cxx = _compiler()
-    assert cxx is not None, 'no host C++ compiler found (CXX, g++, c++, clang++): the stand-alone check cannot be built (the oracle needs one too)'
-    exe = str(tmp_path / 'red_record_check')
-    flags = ['-std=c++17', '-O1', '-g', '-ffp-contract=off', '-fsanitize=address,undefined', '-fno-sanitize-recover=undefined']
-    # the sanitizer runtimes inside the program itself (clang's default; gcc needs to be told), so that it depends on no shared runtime
-    if 'clang' not in subprocess.run([cxx, '--version'], capture_output=True, text=True).stdout:
-        flags += ['-static-libasan', '-static-libubsan']
-    cc = subprocess.run([cxx] + flags + ['-o', exe, SRC], capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stdout + cc.stderr
-    run = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert run.returncode == 0, run.stdout + run.stderr
+    run = build_and_run(SRC, tmp_path, required=True, timeout=300, flags=['-ffp-contract=off'])
     assert ' 0 mismatches' in run.stdout, run.stdout

@@ -11,7 +11,6 @@
   submitted while busy."""
 import os
 import re
-import shutil
 import subprocess
 import sys
 
@@ -24,6 +23,7 @@ from cage_challenge_4_amd import reward_terms as RT
 from oracle_binding import OracleVecEnv
 import reward_terms_util as U
 import test_scripted as TS
+from cpp_check import build_and_run
 
 SRC = os.path.join(ROOT, 'tests', 'cpp', 'reward_terms_check.cpp')
 
@@ -63,25 +63,8 @@ def test_importing_the_module_imports_neither_torch_nor_the_oracle():
     assert run.returncode == 0, run.stdout + run.stderr
 
 
-def _compiler():
-    for cxx in (os.environ.get('CXX'), 'g++', 'c++', 'clang++'):
-        if cxx and shutil.which(cxx):
-            return shutil.which(cxx)
-    return None
-
-
 def test_serial_statement_on_crafted_rows_under_the_sanitizers(tmp_path):
-    cxx = _compiler()
-    assert cxx is not None, 'no host C++ compiler found (CXX, g++, c++, clang++): the stand-alone check cannot be built (the oracle needs one too)'
-    exe = str(tmp_path / 'reward_terms_check')
-    flags = ['-std=c++17', '-O1', '-g', '-ffp-contract=off', '-fsanitize=address,undefined', '-fno-sanitize-recover=undefined']
-    # the sanitizer runtimes inside the program itself (clang's default; gcc needs to be told), so that it depends on no shared runtime
-    if 'clang' not in subprocess.run([cxx, '--version'], capture_output=True, text=True).stdout:
-        flags += ['-static-libasan', '-static-libubsan']
-    cc = subprocess.run([cxx] + flags + ['-o', exe, SRC], capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stdout + cc.stderr
-    run = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert run.returncode == 0, run.stdout + run.stderr
+    run = build_and_run(SRC, tmp_path, required=True, timeout=300, flags=['-ffp-contract=off'])
     assert ' 0 mismatches' in run.stdout, run.stdout
 
 

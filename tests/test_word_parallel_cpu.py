@@ -5,33 +5,14 @@ compiler at -O1 with the address and undefined-behaviour sanitizers and run as a
 exhaustive where the domain is small (all 7-bit status patterns, all masks 1..255 x n below the population count, every nsvc, all 256
 allowed masks x 2048 server-count words x every c below the total) and random on the live-host words.  Exit status 0: all agreed."""
 import os
-import shutil
-import subprocess
 
-import pytest
+from cpp_check import build_and_run
+
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, 'tests', 'cpp', 'word_parallel_check.cpp')
 
 
-def _compiler():
-    for cxx in (os.environ.get('CXX'), 'g++', 'c++', 'clang++'):
-        if cxx and shutil.which(cxx):
-            return shutil.which(cxx)
-    return None
-
-
 def test_word_parallel_forms_equal_their_loops(tmp_path):
-    cxx = _compiler()
-    if cxx is None:
-        pytest.skip('no host C++ compiler found (CXX, g++, c++, clang++): the stand-alone check cannot be built')
-    exe = str(tmp_path / 'word_parallel_check')
-    flags = ['-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=undefined']
-    # the sanitizer runtimes inside the program itself (clang's default; gcc needs to be told), so that it depends on no shared runtime
-    if 'clang' not in subprocess.run([cxx, '--version'], capture_output=True, text=True).stdout:
-        flags += ['-static-libasan', '-static-libubsan']
-    cc = subprocess.run([cxx] + flags + ['-o', exe, SRC], capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stdout + cc.stderr
-    run = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert run.returncode == 0, run.stdout + run.stderr
+    run = build_and_run(SRC, tmp_path, required=False, timeout=300)
     assert ' 0 mismatches' in run.stdout, run.stdout
