@@ -3,6 +3,7 @@
 // the kernels: cc4_k_feat.hip, cc4_k_red.hip, cc4_k_blue.hip, cc4_k_edges.hip, cc4_k_reward.hip, cc4_k_sample.hip; the definitions: cc4_features.h,
 // cc4_red_view.h, cc4_blue_view.h, cc4_blue_edges.h, cc4_reward_terms.h, cc4_sample.h).  Every view has a device entry point and the same definition on the host from one row; the call shape of the device entry
 // points is stated at ViewSrc (cc4_args.h) and implemented once here: view_check, view_launch.
+// Beside the views, the learner's half of the sampling, which reads no row at all: log-probabilities of stored actions with gradients (cc4_k_logp.hip; cc4_logp.h).
 #include "cc4_host.h"
 #include "cc4_features.h"
 #include "cc4_red_view.h"
@@ -10,6 +11,7 @@
 #include "cc4_blue_edges.h"
 #include "cc4_reward_terms.h"
 #include "cc4_sample.h"
+#include "cc4_logp.h"
 
 // ---- the device entry points.  One launch on the main stream behind the group streams, no host synchronisation; a view only reads rows -- as the
 // last step left them -- so the next step launches need no ordering behind it beyond the main stream's own.
@@ -82,6 +84,42 @@ int cc4_sample_actions_device(cc4_handle* h, const void* d_bank, int32_t capacit
                             "the action buffer is required and must be 4-byte aligned (the stats: 4-byte aligned or NULL)", d_bank, capacity);
   return rc == VIEW_GO ? view_launch(h, "cc4_sample_actions_device", k_sample_actions, d_bank, capacity, d_ids, n, d_logits, (int)logits_dtype, seed0, t, 1.0f / temperature, (int)flags,
                                      d_actions, d_stats) : rc;
+}
+
+// ---- the learner's half of the sampling: log-probability and entropy of stored actions under new logits, and their derivative (cc4_logp.h;
+// cc4_k_logp.hip).  Pure functions of the caller's tensors: no handle and so no entry prologue, no stream of the library's -- one launch on the
+// caller's stream on the device current to the calling thread (autograd's backward thread is as good as any).  -2 with nothing enqueued: a null
+// pointer, n < 0, a dtype outside 1..3, a temperature that is not finite and positive; n == 0 a no-op; -1: the launch failed.
+static bool logp_bad(int32_t dtype, int32_t n, float temperature) {
+  return dtype < 1 || dtype > 3 || n < 0 || !(temperature > 0.0f) || !std::isfinite(temperature);
+}
+static int logp_blocks(int32_t n) { return (int)(((int64_t)n + LP_WAVES - 1) / LP_WAVES); }
+int cc4_logp_actions_device(void* stream, const void* d_logits, int32_t dtype, const uint8_t* d_mask, const int32_t* d_actions, int32_t n, float temperature,
+                            float* d_aux, int32_t* d_fault) {
+  if (!d_logits || !d_mask || !d_actions || !d_aux || !d_fault || logp_bad(dtype, n, temperature)) return -2;
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(k_logp_fwd, dim3(logp_blocks(n)), dim3(LP_WAVES * WAVE), 0, static_cast<hipStream_t>(stream), d_logits, (int)dtype, d_mask, d_actions,
+                     (int)n, 1.0f / temperature, d_aux, d_fault);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+int cc4_logp_actions_grad_device(void* stream, const void* d_logits, int32_t dtype, const uint8_t* d_mask, const int32_t* d_actions, int32_t n,
+                                 float temperature, const float* d_aux, const float* d_g, void* d_grad) {
+  if (!d_logits || !d_mask || !d_actions || !d_aux || !d_g || !d_grad || logp_bad(dtype, n, temperature)) return -2;
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(k_logp_bwd, dim3(logp_blocks(n)), dim3(LP_WAVES * WAVE), 0, static_cast<hipStream_t>(stream), d_logits, (int)dtype, d_mask, d_actions,
+                     (int)n, 1.0f / temperature, d_aux, d_g, d_grad);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+// ... and on the host, one row of float32 logits: the number of refused agents (0 .. 5), or -2; the derivative 0 or -2.  No device.
+int cc4_logp_actions_host(const float* logits, const uint8_t* mask, const int32_t* actions, float temperature, float* aux) {
+  if (!logits || !mask || !actions || !aux || logp_bad(3, 0, temperature)) return -2;
+  return logp_from_row(logits, mask, actions, 1.0f / temperature, aux);
+}
+int cc4_logp_actions_grad_host(const float* logits, const uint8_t* mask, const int32_t* actions, float temperature, const float* aux, const float* g,
+                               float* grad) {
+  if (!logits || !mask || !actions || !aux || !g || !grad || logp_bad(3, 0, temperature)) return -2;
+  logp_grad_from_row(logits, mask, actions, 1.0f / temperature, aux, g, grad);
+  return 0;
 }
 
 // The switch of the reward record: the handle behaves as after a cc4_step_red_device whose records were all "the scripted class acts" -- d_ext filled with

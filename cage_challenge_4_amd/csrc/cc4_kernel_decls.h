@@ -64,6 +64,16 @@ __global__ void k_blue_edges(BlueEdgesArgs a);
 __global__ void k_reward_terms(RewardArgs a);
 // masked sampling of the blue actions from policy logits (cc4_k_sample.hip): one wavefront per requested episode or bank slot
 __global__ void k_sample_actions(SampleArgs a);
+// log-probability and entropy of stored blue actions, and their derivative (cc4_k_logp.hip): one wavefront per row of the caller's tensors,
+// LP_WAVES rows per workgroup (measured: profiles/r29_logp.txt; make EXTRA=-DCC4_LOGP_WAVES=k builds another)
+#ifndef CC4_LOGP_WAVES
+#define CC4_LOGP_WAVES 4
+#endif
+constexpr int LP_WAVES = CC4_LOGP_WAVES;
+__global__ void k_logp_fwd(const void* __restrict__ logits, int dtype, const uint8_t* __restrict__ mask, const int32_t* __restrict__ actions, int n,
+                           float inv_t, float* __restrict__ aux, int32_t* __restrict__ fault);
+__global__ void k_logp_bwd(const void* __restrict__ logits, int dtype, const uint8_t* __restrict__ mask, const int32_t* __restrict__ actions, int n,
+                           float inv_t, const float* __restrict__ aux, const float* __restrict__ g, void* __restrict__ grad);
 // per-episode opponent classes (cc4_k_misc.hip): one lane per episode
 __global__ void k_set_policies(EnvState* st, const int8_t* __restrict__ red, const int8_t* __restrict__ green, const int8_t* __restrict__ blue, int n, uint32_t* fault);
 __global__ void k_get_policies(const EnvState* __restrict__ st, int8_t* __restrict__ live, int8_t* __restrict__ assigned, int n);

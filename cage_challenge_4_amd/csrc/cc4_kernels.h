@@ -19,6 +19,8 @@
 //   cc4_k_edges.hip    the Monitor's connections as edge lists: k_blue_edges (cc4_blue_edges_device); only cc4_blue_edges.h
 //   cc4_k_reward.hip   the pieces of the step reward as tensors: k_reward_terms (cc4_reward_terms_device); only cc4_reward_terms.h
 //   cc4_k_sample.hip   policy logits to valid blue actions: k_sample_actions (cc4_sample_actions_device); only cc4_sample.h
+//   cc4_k_logp.hip     stored blue actions under new logits, with gradients: k_logp_fwd, k_logp_bwd (cc4_logp_actions_device, cc4_logp_actions_grad_device);
+//                      only cc4_logp.h, no rows and no handle
 // cc4_kernel_decls.h declares them for the host side.  No MFMA anywhere: the path is integer / indexing.
 #pragma once
 #include "cc4_args.h"

@@ -75,6 +75,8 @@ class CC4TorchVecEnv:
     sample_actions(logits=None, *, seed=0, t=None, temperature=1.0, greedy=False, busy_aware=True, ids=None, bank=None, out=None)
                                                   -> (actions [n, 5] int32, stats [n, 5, 2] float32)   a policy's [n, 570] logits to the indices
                                                   step() takes in one launch: masked, busy agents -1, logp and entropy of the draw
+    evaluate_actions(logits, mask, actions, temperature=1.0) -> (logp [..., 5], entropy [..., 5]) float32   the update's half: stored actions
+                                                  under new logits, with the gradient back to the logits (cage_challenge_4_amd.action_logp)
 
     Mixed opponents in one batch (include/cc4.h cc4_set_policies_device, cc4_reset_device):
     set_opponents(red=None, green=None, blue=None)   integer tensors [N] on the device: the classes each episode regenerates into from its next
@@ -391,6 +393,12 @@ class CC4TorchVecEnv:
             t, self._sample_t = self._sample_t, self._sample_t + 1
         return self._view('cc4_sample_actions_device', ids, bank, out, (((L.NUM_BLUE,), torch.int32, 4), ((L.NUM_BLUE, 2), torch.float32, 4)),
                           code, lp, int(seed) & (2 ** 64 - 1), int(t) & 0xFFFFFFFF, temperature, flags_of(greedy, busy_aware))
+
+    def evaluate_actions(self, logits, mask, actions, temperature=1.0):
+        """action_logp.evaluate_actions: (logp, entropy) of stored actions under new logits, differentiable with respect to the logits -- the
+        update's half of sample_actions().  A pure function of its tensors (the env is not read); action_logp.check_errors() reports refusals."""
+        from .action_logp import evaluate_actions
+        return evaluate_actions(logits, mask, actions, temperature)
 
     def enable_event_log(self, on=True):
         """CC4VecEnv.enable_event_log (cc4_enable_event_log): record the HostEvents entries of every step, which fills the event columns of
