@@ -12,11 +12,10 @@ Three ways to the same numbers:
   CC4VecEnv.sample_actions() / CC4TorchVecEnv.sample_actions()   the HIP kernel over the batch (k_sample_actions), float32
   from_row(hot, logits, seed, t, e, ...)     the same definition compiled for the host (cc4_sample_actions_from_row), float32, no GPU
   reference(mask, busy, logits, seed, t, e, ...)   a NumPy restatement in float64 from the mask row and the busy flags only, with a NumPy Philox"""
-import ctypes
 import math
 import numpy as np
 from . import _lib as L
-from ._view_util import _bytes
+from ._view_util import _bytes, call_from_row
 
 NUM_BLUE = L.NUM_BLUE
 SLOTS = L.MASK_PER_ENV
@@ -36,6 +35,11 @@ def flags_of(greedy, busy_aware):
     return (GREEDY if greedy else 0) | (BUSY if busy_aware else 0)
 
 
+def noise_words(seed, t):
+    """(seed, t) as the uint64 and uint32 words the entry points take: any Python integers, reduced modulo 2^64 and 2^32."""
+    return int(seed) & (2 ** 64 - 1), int(t) & 0xFFFFFFFF
+
+
 def _logits_row(logits):
     if logits is None:
         return None
@@ -51,18 +55,10 @@ def from_row(hot, logits, seed, t, e, temperature=1.0, greedy=False, busy_aware=
     """(actions [5] int32, stats [5, 2] float32 (logp, entropy), refused bool) of one packed hot row (CC4VecEnv.get_state(e)) and its [570]
     logits (float16 / float32 / float64 values, taken as float32; None: uniform over the valid slots).  e: the id of the entry -- the episode
     or bank slot the row belongs to.  refused: some agent's valid logits held a NaN or +inf or were all -inf (its action is -1)."""
-    lib = L.load()
     temperature = check_temperature(temperature)
-    hot = _bytes(hot, lib.cc4_state_bytes(), 'a hot row')
-    lg = _logits_row(logits)
-    actions = np.zeros(NUM_BLUE, np.int32)
-    stats = np.zeros((NUM_BLUE, 2), np.float32)
-    vp = ctypes.c_void_p
-    rc = lib.cc4_sample_actions_from_row(hot.ctypes.data_as(vp), None if lg is None else lg.ctypes.data_as(vp), int(seed) & (2 ** 64 - 1),
-                                         int(t) & 0xFFFFFFFF, int(e), temperature, flags_of(greedy, busy_aware), actions.ctypes.data_as(vp),
-                                         stats.ctypes.data_as(vp))
-    if rc not in (0, 1):
-        raise L.CC4Error(f'cc4_sample_actions_from_row failed (rc={rc})')
+    hot = _bytes(hot, L.load().cc4_state_bytes(), 'a hot row')
+    seed, t = noise_words(seed, t)
+    actions, stats, rc = call_from_row('sample_actions', hot, _logits_row(logits), seed, t, int(e), temperature, flags_of(greedy, busy_aware), ok=(0, 1))
     return actions, stats, bool(rc)
 
 

@@ -17,10 +17,10 @@ Three ways to the same numbers:
   from_row(hot, cold, steps, max_edges)   the same definition compiled for the host (cc4_blue_edges_from_row), in a process without a GPU
   from_true_state(doc, max_edges)         a NumPy restatement from the true-state document only: independent of the packed rows
 and to_edge_index(edges) turns a batch of lists into the [2, M] node-id pairs a PyG-style layer takes."""
-import ctypes
-import numpy as np
 from . import _lib as L
-from ._view_util import MAX_EVENTS, ZONE_OF_SUBNET, _bytes, _doc, events_valid  # noqa: F401  (MAX_EVENTS: part of this module's surface)
+from . import _views as V
+from ._views import check_max_edges
+from ._view_util import MAX_EVENTS, ZONE_OF_SUBNET, _doc, _rows, call_from_row, events_valid  # noqa: F401  (MAX_EVENTS: part of this module's surface)
 
 NUM_BLUE, MAX_EDGES, EDGE_COLUMNS, EDGE_WORDS = L.NUM_BLUE, L.BLUE_EDGES_MAX, L.BLUE_EDGES_COLUMNS, L.BLUE_EDGES_WORDS
 HOSTS = 137
@@ -28,39 +28,20 @@ COLUMNS = {'agent': 0, 'host': 1, 'local': 2, 'remote': 3, 'local_port': 4, 'rem
 WORDS = {'edges_0': 0, 'edges_1': 1, 'edges_2': 2, 'edges_3': 3, 'edges_4': 4, 'total': 5, 'events_valid': 6, 'step_count': 7}
 
 
-def _check_max(max_edges):
-    max_edges = int(max_edges)
-    if not 1 <= max_edges <= MAX_EDGES:
-        raise ValueError(f'max_edges must be 1 .. {MAX_EDGES}, got {max_edges}')
-    return max_edges
-
-
 def from_row(hot, cold, steps=0, max_edges=MAX_EDGES):
     """(edges [max_edges, 8] int32, counts [8] int32) of one packed hot row (CC4VecEnv.get_state(e)) and its cold row (the second part of
     CC4VecEnv.snapshot(e); the whole cc4_cold_bytes() of that env).  cold=None: no edges, events_valid 0.  steps: the episode length of the
     env the rows come from; 0: the length the hot row itself records."""
-    lib = L.load()
-    max_edges = _check_max(max_edges)
-    hot = _bytes(hot, lib.cc4_state_bytes(), 'a hot row')
-    if cold is not None:
-        cold = _bytes(cold, None, 'a cold row')
-    edges = np.zeros((max_edges, EDGE_COLUMNS), np.int32)
-    counts = np.zeros(EDGE_WORDS, np.int32)
-    vp = ctypes.c_void_p
-    rc = lib.cc4_blue_edges_from_row(hot.ctypes.data_as(vp), None if cold is None else cold.ctypes.data_as(vp), int(steps), max_edges,
-                                     edges.ctypes.data_as(vp), counts.ctypes.data_as(vp))
-    if rc:
-        raise L.CC4Error(f'cc4_blue_edges_from_row failed (rc={rc})')
-    return edges, counts
+    max_edges = check_max_edges(max_edges)
+    return call_from_row('blue_edges', *_rows(hot, cold), int(steps), max_edges, max_edges=max_edges)[:2]
 
 
 def from_true_state(doc, max_edges=MAX_EDGES):
     """The same arrays from a true-state document (the JSON text of cc4_get_true_state, its parsed form, or true_state.TrueState): from
     "events" / "events_step" / "events_total", "step" and the ids of "hosts" only, with a dictionary and a Python sort."""
     d = _doc(doc)
-    max_edges = _check_max(max_edges)
-    edges = np.full((max_edges, EDGE_COLUMNS), -1, np.int32)
-    counts = np.zeros(EDGE_WORDS, np.int32)
+    edges, counts = V.empty('blue_edges', max_edges=max_edges)
+    max_edges = len(edges)
     valid = events_valid(d)
     counts[6], counts[7] = int(valid), d['step']
     if not valid:

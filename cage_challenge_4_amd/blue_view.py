@@ -15,10 +15,10 @@ Three ways to the same numbers:
                                       a checkpoint, in a process without a GPU
   from_true_state(doc)                a NumPy restatement from the true-state document only: independent of the packed rows.  The document does not
                                       carry the queued action, so words 1..3 of the scalars (DOC_UNDEFINED_WORDS) stay zero."""
-import ctypes
 import numpy as np
 from . import _lib as L
-from ._view_util import MAX_EVENTS, ZONE_OF_SUBNET, _bytes, _doc, events_valid  # noqa: F401  (MAX_EVENTS, events_valid: part of this module's surface)
+from . import _views as V
+from ._view_util import MAX_EVENTS, ZONE_OF_SUBNET, _doc, _rows, call_from_row, events_valid  # noqa: F401  (MAX_EVENTS, events_valid: part of this module's surface)
 
 NUM_BLUE, VIEW_HOSTS, VIEW_PER_HOST, VIEW_SCALARS = L.NUM_BLUE, L.BLUE_VIEW_HOSTS, L.BLUE_VIEW_PER_HOST, L.BLUE_VIEW_SCALARS
 
@@ -39,18 +39,7 @@ def from_row(hot, cold=None, steps=0):
     CC4VecEnv.snapshot(e)).  cold=None: the event columns, 'sus_pids' and the decoy bits are zero and events_valid is 0.  steps: the episode
     length of the env the rows come from (it sizes the cold row, which must be the whole cc4_cold_bytes() of that env); 0: the length the hot
     row itself records."""
-    lib = L.load()
-    hot = _bytes(hot, lib.cc4_state_bytes(), 'a hot row')
-    if cold is not None:
-        cold = _bytes(cold, None, 'a cold row')
-    hosts = np.zeros((NUM_BLUE, VIEW_HOSTS, VIEW_PER_HOST), np.uint8)
-    scal = np.zeros((NUM_BLUE, VIEW_SCALARS), np.int32)
-    vp = ctypes.c_void_p
-    rc = lib.cc4_blue_view_from_row(hot.ctypes.data_as(vp), None if cold is None else cold.ctypes.data_as(vp), int(steps),
-                                    hosts.ctypes.data_as(vp), scal.ctypes.data_as(vp))
-    if rc:
-        raise L.CC4Error(f'cc4_blue_view_from_row failed (rc={rc})')
-    return hosts, scal
+    return call_from_row('blue_view', *_rows(hot, cold), int(steps))[:2]
 
 
 def from_true_state(doc):
@@ -58,8 +47,7 @@ def from_true_state(doc):
     "blue" entries (busy / traffic_ok / sus / parent), "last_blue", the hosts' "ev" / "files", "events" / "events_step" / "events_total", "phase"
     and "step" only.  Words DOC_UNDEFINED_WORDS of the scalars are left zero."""
     d = _doc(doc)
-    hosts = np.zeros((NUM_BLUE, VIEW_HOSTS, VIEW_PER_HOST), np.uint8)
-    scal = np.zeros((NUM_BLUE, VIEW_SCALARS), np.int32)
+    hosts, scal = V.empty('blue_view')
     info = {hd['h']: hd for hd in d['hosts']}
     zone = {h: ZONE_OF_SUBNET[h // 17] for h in info}
     count = np.zeros((NUM_BLUE, VIEW_HOSTS, 4), np.int64)            # sus, conn, proc, remote

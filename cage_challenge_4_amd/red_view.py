@@ -18,7 +18,8 @@ stands for the agent's first listed session (auto_sid)."""
 import ctypes
 import numpy as np
 from . import _lib as L
-from ._view_util import _bytes, _doc
+from . import _views as V
+from ._view_util import _bytes, _doc, call_from_row
 
 NUM_RED, VIEW_HOSTS, VIEW_PER_HOST, VIEW_SCALARS = L.NUM_RED, L.RED_VIEW_HOSTS, L.RED_VIEW_PER_HOST, L.RED_VIEW_SCALARS
 ACT_WORDS, SID_AUTO, ACT_NONE = L.RED_ACT_WORDS, L.RED_SID_AUTO, -1
@@ -41,14 +42,7 @@ def _row(row_bytes):
 
 def from_row(row_bytes):
     """(hosts [6, 137, 8] uint8, scalars [6, 16] int32) of one packed hot row (CC4VecEnv.get_state(e), a row of get_states())."""
-    lib, row = _row(row_bytes)
-    hosts = np.zeros((NUM_RED, VIEW_HOSTS, VIEW_PER_HOST), np.uint8)
-    scal = np.zeros((NUM_RED, VIEW_SCALARS), np.int32)
-    vp = ctypes.c_void_p
-    rc = lib.cc4_red_view_from_row(row.ctypes.data_as(vp), hosts.ctypes.data_as(vp), scal.ctypes.data_as(vp))
-    if rc:
-        raise L.CC4Error(f'cc4_red_view_from_row failed (rc={rc})')
-    return hosts, scal
+    return call_from_row('red_view', _row(row_bytes)[1])[:2]
 
 
 def record_from_row(row_bytes, agent, words):
@@ -77,8 +71,7 @@ def from_true_state(doc):
     """The same arrays from a true-state document (the JSON text of cc4_get_true_state, its parsed form, or true_state.TrueState): from the
     "red" entries, "last_red" and "step" only.  Words DOC_UNDEFINED_WORDS of the scalars are left zero."""
     d = _doc(doc)
-    hosts = np.zeros((NUM_RED, VIEW_HOSTS, VIEW_PER_HOST), np.uint8)
-    scal = np.zeros((NUM_RED, VIEW_SCALARS), np.int32)
+    hosts, scal = V.empty('red_view')
     for r, ag in enumerate(d['red']):
         v = hosts[r]
         for h in range(VIEW_HOSTS):

@@ -15,10 +15,8 @@ Two ways to the same numbers:
   CC4VecEnv.reward_terms() / CC4TorchVecEnv.reward_terms()   the HIP kernel over the batch (k_reward_terms)
   from_row(hot, cold=None, steps=0)   the same definition compiled for the host (cc4_reward_terms_from_row): from cc4_get_state / cc4_get_cold
                                       rows or a checkpoint, in a process without a GPU"""
-import ctypes
-import numpy as np
 from . import _lib as L
-from ._view_util import ZONE_OF_SUBNET, _bytes  # noqa: F401  (ZONE_OF_SUBNET: part of this module's surface)
+from ._view_util import ZONE_OF_SUBNET, _rows, call_from_row  # noqa: F401  (ZONE_OF_SUBNET: part of this module's surface)
 
 NUM_BLUE, SUBNETS, COLS, NWORDS = L.NUM_BLUE, L.REWARD_SUBNETS, L.REWARD_COLS, L.REWARD_WORDS
 
@@ -37,15 +35,4 @@ def from_row(hot, cold=None, steps=0):
     """(terms [9, 4] int32, words [16] int32) of one packed hot row (CC4VecEnv.get_state(e)) and its cold row (the second part of
     CC4VecEnv.snapshot(e)).  cold=None: valid is 0.  steps: the episode length of the env the rows come from; 0: the length the hot row itself
     records."""
-    lib = L.load()
-    hot = _bytes(hot, lib.cc4_state_bytes(), 'a hot row')
-    if cold is not None:
-        cold = _bytes(cold, None, 'a cold row')         # (the whole cc4_cold_bytes() of its env: the record lies in its fixed part)
-    terms = np.zeros((SUBNETS, COLS), np.int32)
-    words = np.zeros(NWORDS, np.int32)
-    vp = ctypes.c_void_p
-    rc = lib.cc4_reward_terms_from_row(hot.ctypes.data_as(vp), None if cold is None else cold.ctypes.data_as(vp), int(steps),
-                                       terms.ctypes.data_as(vp), words.ctypes.data_as(vp))
-    if rc:
-        raise L.CC4Error(f'cc4_reward_terms_from_row failed (rc={rc})')
-    return terms, words
+    return call_from_row('reward_terms', *_rows(hot, cold), int(steps))[:2]       # (the record lies in the cold row's fixed part)

@@ -10,10 +10,10 @@ Three ways to the same numbers:
   from_true_state(ts)          a NumPy restatement from a decoded true-state document (true_state.decode): independent of the packed row, and
                                what a user of the single-episode facade gets
 """
-import ctypes
 import numpy as np
 from . import _lib as L
-from ._view_util import _bytes
+from . import _views as V
+from ._view_util import _bytes, call_from_row
 
 FEAT_HOSTS, FEAT_PER_HOST, FEAT_GLOBAL = L.FEAT_HOSTS, L.FEAT_PER_HOST, L.FEAT_GLOBAL
 
@@ -29,15 +29,7 @@ _RS_ROOT = 2
 
 def from_row(row_bytes):
     """(hosts [137, 16] uint8, glob [32] int32) of one packed hot row (CC4VecEnv.get_state(e), a row of get_states())."""
-    lib = L.load()
-    row = _bytes(row_bytes, lib.cc4_state_bytes(), 'a hot row')
-    hosts = np.zeros((FEAT_HOSTS, FEAT_PER_HOST), np.uint8)
-    glob = np.zeros(FEAT_GLOBAL, np.int32)
-    vp = ctypes.c_void_p
-    rc = lib.cc4_state_features_from_row(row.ctypes.data_as(vp), hosts.ctypes.data_as(vp), glob.ctypes.data_as(vp))
-    if rc:
-        raise L.CC4Error(f'cc4_state_features_from_row failed (rc={rc})')
-    return hosts, glob
+    return call_from_row('state_features', _bytes(row_bytes, L.load().cc4_state_bytes(), 'a hot row'))[:2]
 
 
 def host_kind(h):
@@ -51,8 +43,7 @@ def from_true_state(ts, steps=0, err=0):
     """The same arrays from a decoded true-state document (true_state.TrueState, or the parsed JSON of cc4_get_true_state).  The document
     does not carry the episode length nor the error flags (CC4VecEnv.err): words 1 and 29 are `steps` and `err` as given."""
     d = ts if isinstance(ts, dict) else ts.raw
-    hosts = np.zeros((FEAT_HOSTS, FEAT_PER_HOST), np.uint8)
-    glob = np.zeros(FEAT_GLOBAL, np.int32)
+    hosts, glob = V.empty('state_features')
     nsess, root, agents = np.zeros(FEAT_HOSTS, np.int64), np.zeros(FEAT_HOSTS, bool), np.zeros(FEAT_HOSTS, np.int64)
     for r, ag in enumerate(d['red']):
         for _sid, h, _pid, fl in ag['sessions']:

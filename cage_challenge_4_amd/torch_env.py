@@ -1,7 +1,7 @@
 """CC4TorchVecEnv -- CC4VecEnv for a PyTorch learner on the same GPU: actions in, observations / masks / rewards / dones out, as torch
 tensors on the device, with no host copy and no host synchronisation in step().
 
-The engine's work runs on the handle's own (non-blocking) HIP streams; every call here is ordered against torch.cuda.current_stream()
+The engine's work runs on the handle's own (non-blocking) HIP streams; every call here is ordered against torch's current stream
 in both directions (cc4_stream_wait / cc4_stream_signal, include/cc4.h), and one kernel (k_policy_outputs, cc4_policy_outputs) writes
 the outputs straight into this object's tensors in the dtype the policy wants.  Importing this module imports torch; importing the
 package does not."""
@@ -9,10 +9,76 @@ import ctypes
 import numpy as np
 import torch
 from . import _lib as L
-from .vec_env import CC4VecEnv, raise_on_copy_faults, split_obs, split_mask  # noqa: F401  (split_obs / split_mask slice tensors too)
+from . import _views as V
+from .vec_env import CC4VecEnv, as_env_mask, as_ptr, as_seeds, raise_on_copy_faults, split_obs, split_mask  # noqa: F401  (split_obs / split_mask slice tensors too)
 
 _OBS_DTYPES = {torch.uint8: 0, torch.float16: 1, torch.bfloat16: 2, torch.float32: 3}
 _LOGIT_DTYPES = {torch.float16: 1, torch.bfloat16: 2, torch.float32: 3}      # the same codes: what sample_actions() takes
+_TORCH_DTYPES = {np.dtype(np.uint8): torch.uint8, np.dtype(np.int32): torch.int32, np.dtype(np.float32): torch.float32}      # of the views' outputs
+
+
+# ---- the tensor checks: a ValueError that names the argument, or the contiguous cast (on the current stream, as step() casts its actions)
+def int_tensor(x, shape, device, what, *, to, saturate=False, bool_ok=False):
+    """x as a contiguous tensor of dtype `to`: an integer tensor (bool_ok: or a bool one) of `shape` (None: any extent) on `device`.
+    saturate: a value beyond `to` stays out of range instead of wrapping into it."""
+    if (not torch.is_tensor(x) or x.dtype.is_floating_point or x.dtype.is_complex or (x.dtype == torch.bool and not bool_ok) or x.dim() != len(shape)
+            or any(w is not None and w != g for w, g in zip(shape, x.shape)) or x.device != device):
+        want = ', '.join('k' if w is None else str(w) for w in shape)
+        raise ValueError(f'{what} must be an integer {"or bool " if bool_ok else ""}tensor [{want}] on {device}')
+    if saturate and x.dtype != to:
+        x = x.clamp(torch.iinfo(to).min, torch.iinfo(to).max)
+    return x.to(to).contiguous()
+
+
+def seed_tensor(x, n, device, what='seeds'):
+    """Seeds as the int64 words the entry points read: a uint64 tensor is viewed, any other integer dtype cast."""
+    if torch.is_tensor(x) and x.dtype == torch.uint64 and tuple(x.shape) == (n,) and x.device == device:
+        return x.view(torch.int64).contiguous()
+    return int_tensor(x, (n,), device, what, to=torch.int64)
+
+
+def _dptr(t):
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def mask_tensor(x, n, device, what='env_mask'):
+    """An episode mask as uint8: bool or uint8 only.  (A bool tensor -- the env's own `done`, which a reset's outputs rewrite -- is copied.)"""
+    if torch.is_tensor(x) and x.dtype not in (torch.bool, torch.uint8):
+        raise ValueError(f'{what} must be a bool or uint8 tensor [{n}] on {device}')
+    return int_tensor(x, (n,), device, what, to=torch.uint8, bool_ok=True)
+
+
+class _Ordered:
+    """The stream bracket every call of CC4TorchVecEnv that orders against the caller's stream goes through.  On entry: the env's device, and the
+    handle's streams wait for what torch's current stream holds at this moment (cc4_stream_wait) -- so argument checks, casts and staging copies
+    come BEFORE the bracket: a refused call enqueues nothing, and a cast is waited for.  The body enqueues the library's work.  On exit the stream
+    waits for the handle's: behind the kernel that writes the env's output tensors (outputs=True: _outputs), or as they stand
+    (cc4_stream_signal).  Temporaries of the casts live on that stream, so the signal also orders their reuse behind their reader.  A body that
+    raises leaves the stream unsignalled: nothing of that call is to be read.  (A plain class, not a generator: step() passes here every step.)"""
+    __slots__ = ('env', 'outputs', 'guard', 's')
+
+    def __init__(self, env, outputs=False):
+        self.env, self.outputs = env, outputs
+
+    def __enter__(self):
+        env = self.env
+        self.guard = torch.cuda.device(env.device)
+        self.guard.__enter__()
+        self.s = ctypes.c_void_p(torch.cuda.current_stream(env.device).cuda_stream)
+        rc = env.lib.cc4_stream_wait(env._h, self.s)
+        if rc:
+            self.guard.__exit__(None, None, None)
+            env.venv._chk(rc, 'cc4_stream_wait')
+        return self.s
+
+    def __exit__(self, kind, exc, tb):
+        try:
+            if kind is None and self.outputs:
+                self.env._outputs(self.s)
+            elif kind is None:
+                self.env.venv._chk(self.env.lib.cc4_stream_signal(self.env._h, self.s), 'cc4_stream_signal')
+        finally:
+            self.guard.__exit__(kind, exc, tb)
 
 
 class CC4TorchVecEnv:
@@ -26,7 +92,7 @@ class CC4TorchVecEnv:
         actions   integer tensor [N, 5] of wrapper action indices on the env's device (negative: no action), any integer dtype;
         messages  optional [N, 5, 8] tensor of 0 / 1 bytes;
         obs [N, 578] obs_dtype, reward [N] float32, done [N] bool, info {'action_mask': [N, 570] bool, 'err': [N] int32}.
-    Everything runs on torch.cuda.current_stream() as it stands at the call: whatever the caller enqueued there before (the policy that
+    Everything runs on torch's current stream of the env's device as it stands at the call: whatever the caller enqueued there before (the policy that
     wrote `actions`) happens before the step, and whatever it enqueues after the call sees the step's outputs.  Callers that switch
     streams between calls order those streams themselves, as with any torch tensor.
 
@@ -125,87 +191,49 @@ class CC4TorchVecEnv:
             self.venv._chk(rc, 'cc4_policy_outputs')
         self.venv._chk(lib.cc4_stream_signal(h, s), 'cc4_stream_signal')
 
-    def _reset_device(self, seeds, env_mask):
-        """reset() from device tensors (cc4_reset_device): no upload, no host wait.  A NumPy array or scalar beside a tensor is moved to the device."""
-        n = self.num_envs
-        with torch.cuda.device(self.device):
-            s = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            sp = mp = None
-            if seeds is not None:           # (casts and uploads on s; the allocator keeps the temporaries on s, which cc4_stream_signal orders behind their reader)
-                if not torch.is_tensor(seeds):
-                    seeds = np.uint64(seeds) + np.arange(n, dtype=np.uint64) if np.isscalar(seeds) else np.ascontiguousarray(seeds, dtype=np.uint64)
-                    seeds = torch.from_numpy(seeds.view(np.int64)).to(self.device)
-                if tuple(seeds.shape) != (n,) or seeds.dtype.is_floating_point or seeds.dtype == torch.bool or seeds.device != self.device:
-                    raise ValueError(f'seeds must be an integer tensor [{n}] on {self.device}')
-                seeds = (seeds.view(torch.int64) if seeds.dtype == torch.uint64 else seeds.to(torch.int64)).contiguous()
-                sp = ctypes.c_void_p(seeds.data_ptr())
-            if env_mask is not None:
-                if not torch.is_tensor(env_mask):
-                    env_mask = torch.from_numpy(np.ascontiguousarray(env_mask, dtype=np.uint8)).to(self.device)
-                if tuple(env_mask.shape) != (n,) or env_mask.dtype not in (torch.bool, torch.uint8) or env_mask.device != self.device:
-                    raise ValueError(f'env_mask must be a bool or uint8 tensor [{n}] on {self.device}')
-                env_mask = env_mask.to(torch.uint8).contiguous()        # (a bool tensor -- this object's own `done`, which the reset's outputs rewrite -- is copied)
-                mp = ctypes.c_void_p(env_mask.data_ptr())
-            rc = self.lib.cc4_stream_wait(self._h, s) or self.lib.cc4_reset_device(self._h, sp, mp)
+    def _call(self, entry, *args, outputs=False):
+        """One entry point of the library inside the stream bracket."""
+        with _Ordered(self, outputs):
+            rc = getattr(self.lib, entry)(self._h, *args)
             if rc:
-                self.venv._chk(rc, 'cc4_reset_device')
-            self._outputs(s)
-        return self.obs, self._info()
+                self.venv._chk(rc, entry)
 
     def reset(self, seeds=None, env_mask=None):
         """seeds / env_mask as CC4VecEnv.reset (NumPy arrays, a scalar, None: cc4_reset, which waits for the device) -- or tensors on the env's
         device (seeds any integer dtype, env_mask bool or uint8, e.g. env.reset(env_mask=env.done)): cc4_reset_device on the current stream, no
-        host wait."""
+        host wait; a NumPy array or scalar beside a tensor is moved to the device."""
+        n = self.num_envs
+        seeds, env_mask = (x if torch.is_tensor(x) else f(x, n) for x, f in ((seeds, as_seeds), (env_mask, as_env_mask)))
         if torch.is_tensor(seeds) or torch.is_tensor(env_mask):
-            return self._reset_device(seeds, env_mask)
-        with torch.cuda.device(self.device):
-            s = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            up = lambda a, dt: a if a is None or torch.is_tensor(a) else torch.from_numpy(a.view(dt)).to(self.device)      # noqa: E731
+            seeds, env_mask = up(seeds, np.int64), up(env_mask, np.uint8)
+            seeds = None if seeds is None else seed_tensor(seeds, n, self.device)
+            env_mask = None if env_mask is None else mask_tensor(env_mask, n, self.device)
+            self._call('cc4_reset_device', _dptr(seeds), _dptr(env_mask), outputs=True)
+        else:
             # the reset rewrites rows the last step's kernels may still read, and the outputs go into tensors the caller's stream may
-            # still read: everything on s first (cc4_reset itself waits for the device before it returns)
-            self.venv._chk(self.lib.cc4_stream_wait(self._h, s), 'cc4_stream_wait')
-            sp = mp = None
-            if seeds is not None:
-                if np.isscalar(seeds):
-                    seeds = np.uint64(seeds) + np.arange(self.num_envs, dtype=np.uint64)
-                seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
-                assert seeds.shape == (self.num_envs,)
-                sp = seeds.ctypes.data_as(ctypes.c_void_p)
-            if env_mask is not None:
-                env_mask = np.ascontiguousarray(env_mask, dtype=np.uint8)
-                assert env_mask.shape == (self.num_envs,)
-                mp = env_mask.ctypes.data_as(ctypes.c_void_p)
-            self.venv._chk(self.lib.cc4_reset(self._h, sp, mp), 'cc4_reset')
-            self._outputs(s)
+            # still read: everything on the stream first (cc4_reset itself waits for the device before it returns)
+            self._call('cc4_reset', as_ptr(seeds), as_ptr(env_mask), outputs=True)
         return self.obs, self._info()
 
     def step(self, actions, messages=None, red_actions=None):
-        with torch.cuda.device(self.device):
-            if tuple(actions.shape) != (self.num_envs, L.NUM_BLUE) or (messages is not None and tuple(messages.shape) != tuple(self._messages.shape)):
-                raise ValueError(f'actions must be [{self.num_envs}, {L.NUM_BLUE}] and messages [{self.num_envs}, {L.NUM_BLUE}, {L.MSG_LEN}]')
-            if red_actions is not None:
-                shape = (self.num_envs, L.NUM_RED, L.RED_ACT_WORDS)
-                if (not torch.is_tensor(red_actions) or tuple(red_actions.shape) != shape or red_actions.dtype.is_floating_point
-                        or red_actions.dtype == torch.bool or red_actions.device != self.device):
-                    raise ValueError(f'red_actions must be an integer tensor {list(shape)} (type, host, arg, session) on {self.device}')
-                if self._red is None:
-                    self._red = torch.zeros(shape, dtype=torch.int32, device=self.device)
-            s = torch.cuda.current_stream(self.device)
-            # staging copies on s: any integer dtype cast, and the env no longer depends on the lifetime of the caller's tensors
-            self._actions.copy_(actions)
-            if messages is not None:
-                self._messages.copy_(messages)
-            lib, h, sp = self.lib, self._h, ctypes.c_void_p(s.cuda_stream)
-            mp = self._p_msg if messages is not None else None
-            if red_actions is None:
-                rc = lib.cc4_stream_wait(h, sp) or lib.cc4_step_device(h, self._p_act, mp)
-            else:
-                if red_actions.dtype != torch.int32:     # (a value beyond int32 stays out of range instead of wrapping into it)
-                    red_actions = red_actions.clamp(-2 ** 31, 2 ** 31 - 1)
-                self._red.copy_(red_actions)
-                rc = lib.cc4_stream_wait(h, sp) or lib.cc4_step_red_device(h, self._p_act, mp, ctypes.c_void_p(self._red.data_ptr()))
-            if rc:
-                self.venv._chk(rc, 'cc4_step_device' if red_actions is None else 'cc4_step_red_device')
-            self._outputs(sp)
+        if tuple(actions.shape) != (self.num_envs, L.NUM_BLUE) or (messages is not None and tuple(messages.shape) != tuple(self._messages.shape)):
+            raise ValueError(f'actions must be [{self.num_envs}, {L.NUM_BLUE}] and messages [{self.num_envs}, {L.NUM_BLUE}, {L.MSG_LEN}]')
+        if red_actions is not None:
+            red_actions = int_tensor(red_actions, (self.num_envs, L.NUM_RED, L.RED_ACT_WORDS), self.device, 'red_actions (type, host, arg, session)',
+                                     to=torch.int32, saturate=True)
+            if self._red is None:
+                self._red = torch.zeros_like(red_actions)
+            self._red.copy_(red_actions)
+        # staging copies on the current stream: any integer dtype cast, and the env no longer depends on the lifetime of the caller's tensors
+        self._actions.copy_(actions)
+        if messages is not None:
+            self._messages.copy_(messages)
+        mp = self._p_msg if messages is not None else None
+        if red_actions is None:
+            self._call('cc4_step_device', self._p_act, mp, outputs=True)
+        else:
+            self._call('cc4_step_red_device', self._p_act, mp, _dptr(self._red), outputs=True)
         return self.obs, self.reward, self.done, self._info()
 
     def step_plan(self, actions, messages=None, record_obs=False):
@@ -216,35 +244,25 @@ class CC4TorchVecEnv:
         info['obs_seq'] [k, N, 578] obs_dtype -- the observations after every step -- with record_obs.  Ordered on the current stream both
         ways like step(); no host copy, no host wait."""
         n = self.num_envs
-        if (not torch.is_tensor(actions) or actions.dim() != 3 or actions.shape[0] < 1 or tuple(actions.shape[1:]) != (n, L.NUM_BLUE)
-                or actions.dtype.is_floating_point or actions.dtype == torch.bool or actions.device != self.device):
-            raise ValueError(f'actions must be an integer tensor [k, {n}, {L.NUM_BLUE}] (k >= 1) on {self.device}')
-        k = int(actions.shape[0])
-        if messages is not None and (not torch.is_tensor(messages) or tuple(messages.shape) != (k, n, L.NUM_BLUE, L.MSG_LEN)
-                                     or messages.dtype.is_floating_point or messages.device != self.device):
-            raise ValueError(f'messages must be an integer or bool tensor [{k}, {n}, {L.NUM_BLUE}, {L.MSG_LEN}] on {self.device}')
-        with torch.cuda.device(self.device):
-            s = torch.cuda.current_stream(self.device)
-            vp = ctypes.c_void_p
-            # on s: casts (no copy when the plan is int32 / uint8 and contiguous already) and the trajectory's tensors; the allocator keeps them
-            # on s, whose later work cc4_stream_signal orders behind the plan
-            plan = actions.to(torch.int32).contiguous()
-            msgs = messages.to(torch.uint8).contiguous() if messages is not None else None
-            rewards = torch.empty((k, n), dtype=torch.float32, device=self.device)
-            dones = torch.empty((k, n), dtype=torch.bool, device=self.device)
-            packed = torch.empty((k, n, L.OBS_PACKED_BYTES), dtype=torch.uint8, device=self.device) if record_obs else None
-            lib, h, sp = self.lib, self._h, vp(s.cuda_stream)
-            rc = lib.cc4_stream_wait(h, sp) or lib.cc4_run_plan_device(h, k, vp(plan.data_ptr()), vp(msgs.data_ptr()) if msgs is not None else None,
-                                                                       vp(rewards.data_ptr()), vp(dones.data_ptr()),
-                                                                       vp(packed.data_ptr()) if record_obs else None)
+        # the casts (no copy when the plan is int32 / uint8 and contiguous already) and the trajectory's tensors, on the current stream
+        plan = int_tensor(actions, (None, n, L.NUM_BLUE), self.device, 'actions', to=torch.int32)
+        k = int(plan.shape[0])
+        if k < 1:
+            raise ValueError(f'actions must be an integer tensor [k, {n}, {L.NUM_BLUE}] with k >= 1')
+        msgs = None if messages is None else int_tensor(messages, (k, n, L.NUM_BLUE, L.MSG_LEN), self.device, 'messages', to=torch.uint8, bool_ok=True)
+        z = dict(device=self.device)
+        rewards, dones = torch.empty((k, n), dtype=torch.float32, **z), torch.empty((k, n), dtype=torch.bool, **z)
+        packed = torch.empty((k, n, L.OBS_PACKED_BYTES), dtype=torch.uint8, **z) if record_obs else None
+        seq = torch.empty((k, n, L.OBS_PER_ENV), dtype=self.obs_dtype, **z) if record_obs else None
+        info = self._info()
+        with _Ordered(self, outputs=True):
+            lib, h = self.lib, self._h
+            rc = lib.cc4_run_plan_device(h, k, _dptr(plan), _dptr(msgs), _dptr(rewards), _dptr(dones), _dptr(packed))
             if rc:
                 self.venv._chk(rc, 'cc4_run_plan_device')
-            info = self._info()
             if record_obs:
-                seq = torch.empty((k, n, L.OBS_PER_ENV), dtype=self.obs_dtype, device=self.device)
-                self.venv._chk(lib.cc4_unpack_rows_device(h, k * n, vp(packed.data_ptr()), self._dt, vp(seq.data_ptr())), 'cc4_unpack_rows_device')
+                self.venv._chk(lib.cc4_unpack_rows_device(h, k * n, _dptr(packed), self._dt, _dptr(seq)), 'cc4_unpack_rows_device')
                 info['obs_seq'] = seq
-            self._outputs(sp)       # (signals s: what the caching allocator hands out on s once plan / msgs / packed die is ordered behind their readers)
         return self.obs, rewards, dones, info
 
     @property
@@ -256,9 +274,7 @@ class CC4TorchVecEnv:
         return torch.zeros((int(capacity), self.snapshot_bytes), dtype=torch.uint8, device=self.device)
 
     def _index(self, x, what):
-        if not torch.is_tensor(x) or x.dim() != 1 or x.dtype.is_floating_point or x.dtype == torch.bool or x.device != self.device:
-            raise ValueError(f'{what} must be a 1-D integer tensor on {self.device}')
-        return x.to(torch.int32).contiguous()       # (on the current stream, as step() casts its actions)
+        return int_tensor(x, (None,), self.device, what, to=torch.int32)
 
     def _bank(self, bank):
         if (not torch.is_tensor(bank) or bank.dtype != torch.uint8 or bank.dim() != 2 or bank.shape[1] != self.snapshot_bytes
@@ -267,28 +283,16 @@ class CC4TorchVecEnv:
         return ctypes.c_void_p(bank.data_ptr()), int(bank.shape[0])
 
     def _copy(self, src, dst, src_bank=None, dst_bank=None, seeds=None):
-        with torch.cuda.device(self.device):
-            s = torch.cuda.current_stream(self.device)
-            src, dst = self._index(src, 'source indices'), self._index(dst, 'destination indices')
-            if src.shape != dst.shape:
-                raise ValueError('source and destination indices must have the same length')
-            sb, sc = self._bank(src_bank) if src_bank is not None else (None, 0)
-            db, dc = self._bank(dst_bank) if dst_bank is not None else (None, 0)
-            sd = None
-            if seeds is not None:
-                if not torch.is_tensor(seeds) or seeds.shape != src.shape or seeds.device != self.device:
-                    raise ValueError('seeds must be a tensor with one entry per copy on the env\'s device')
-                seeds = (seeds.view(torch.int64) if seeds.dtype == torch.uint64 else seeds.to(torch.int64)).contiguous()
-                sd = ctypes.c_void_p(seeds.data_ptr())
-            lib, h, sp = self.lib, self._h, ctypes.c_void_p(s.cuda_stream)
-            rc = lib.cc4_stream_wait(h, sp) or lib.cc4_copy_episodes_device(h, int(src.numel()), sb, sc, ctypes.c_void_p(src.data_ptr()), db, dc,
-                                                                               ctypes.c_void_p(dst.data_ptr()), sd)
-            if rc:
-                self.venv._chk(rc, 'cc4_copy_episodes_device')
-            self._outputs(sp)
-            if dst_bank is None and dst.numel():
-                valid = (dst >= 0) & (dst < self.num_envs)
-                self._fresh.scatter_reduce_(0, dst.clamp(0, self.num_envs - 1).long(), valid.to(torch.uint8), 'amax')
+        src, dst = self._index(src, 'source indices'), self._index(dst, 'destination indices')
+        if src.shape != dst.shape:
+            raise ValueError('source and destination indices must have the same length')
+        sb, sc = self._bank(src_bank) if src_bank is not None else (None, 0)
+        db, dc = self._bank(dst_bank) if dst_bank is not None else (None, 0)
+        seeds = None if seeds is None else seed_tensor(seeds, int(src.numel()), self.device, 'seeds (one entry per copy)')
+        self._call('cc4_copy_episodes_device', int(src.numel()), sb, sc, _dptr(src), db, dc, _dptr(dst), _dptr(seeds), outputs=True)
+        if dst_bank is None and dst.numel():
+            valid = (dst >= 0) & (dst < self.num_envs)
+            self._fresh.scatter_reduce_(0, dst.clamp(0, self.num_envs - 1).long(), valid.to(torch.uint8), 'amax')
         return self.obs, self._info()
 
     def clone_episodes(self, src, dst, seeds=None):
@@ -300,34 +304,24 @@ class CC4TorchVecEnv:
     def load_episodes(self, bank, slots, env_ids, seeds=None):
         return self._copy(slots, env_ids, src_bank=bank, seeds=seeds)
 
-    def _view(self, entry, ids, bank, out, specs, *extra):
-        """What the tensor methods of the derived views share.  entry: the cc4_*_device entry point; ids, bank, out as state_features() documents
-        them; specs: (shape of one entry, dtype, required alignment in bytes) of the view's two tensors; extra: arguments in front of the two output
-        pointers.  Ordered on the current stream both ways like step(); no host copy, no host wait."""
-        with torch.cuda.device(self.device):
-            s = torch.cuda.current_stream(self.device)
-            vp = ctypes.c_void_p
-            bp, cap = self._bank(bank) if bank is not None else (None, 0)
-            if ids is not None:
-                ids = self._index(ids, 'ids')
-                n, ip = int(ids.numel()), vp(ids.data_ptr())
-            else:
-                n, ip = (cap if bank is not None else self.num_envs), None
-            shapes = [(n,) + tuple(tail) for tail, _dt, _al in specs]
-            if out is None:
-                a, b = (torch.empty(shp, dtype=dt, device=self.device) for shp, (_tail, dt, _al) in zip(shapes, specs))
-            else:
-                a, b = out
-                for x, shp, (_tail, dt, al) in zip((a, b), shapes, specs):
-                    if (not torch.is_tensor(x) or tuple(x.shape) != shp or x.dtype != dt or x.device != self.device or not x.is_contiguous()
-                            or x.data_ptr() % al):
-                        want = ', '.join(f'{str(dt_).replace("torch.", "")} {list(shp_)} ({al_}-byte aligned)' for shp_, (_t, dt_, al_) in zip(shapes, specs))
-                        raise ValueError(f'out must be contiguous tensors ({want}) on {self.device}')
-            lib, h, sp = self.lib, self._h, vp(s.cuda_stream)
-            rc = lib.cc4_stream_wait(h, sp) or getattr(lib, entry)(h, bp, cap, ip, n, *extra, vp(a.data_ptr()), vp(b.data_ptr()))
-            if rc:
-                self.venv._chk(rc, entry)
-            self.venv._chk(lib.cc4_stream_signal(h, sp), 'cc4_stream_signal')
+    def _view(self, view, ids, bank, out, *extra, max_edges=None):
+        """What the tensor methods of the derived views share.  view: its name in _views.VIEWS, which says what its two tensors are and how the
+        entry point wants them aligned; ids, bank, out as state_features() documents them; extra: arguments in front of the two output pointers.
+        Ordered on the current stream both ways like step(); no host copy, no host wait."""
+        bp, cap = self._bank(bank) if bank is not None else (None, 0)
+        ids = None if ids is None else self._index(ids, 'ids')
+        n = int(ids.numel()) if ids is not None else (cap if bank is not None else self.num_envs)
+        specs = [((n,) + o.tail, _TORCH_DTYPES[o.dtype], o.align) for o in V.outs(view, max_edges)]
+        if out is None:
+            a, b = (torch.empty(shp, dtype=dt, device=self.device) for shp, dt, _al in specs)
+        else:
+            a, b = out
+            for x, (shp, dt, al) in zip((a, b), specs):
+                if (not torch.is_tensor(x) or tuple(x.shape) != shp or x.dtype != dt or x.device != self.device or not x.is_contiguous()
+                        or x.data_ptr() % al):
+                    want = ', '.join(f'{str(dt_).replace("torch.", "")} {list(shp_)} (aligned to {al_} bytes)' for shp_, dt_, al_ in specs)
+                    raise ValueError(f'out must be contiguous tensors ({want}) on {self.device}')
+        self._call(V.VIEWS[view].device, bp, cap, _dptr(ids), n, *extra, _dptr(a), _dptr(b))
         return a, b
 
     def state_features(self, ids=None, bank=None, out=None):
@@ -337,14 +331,13 @@ class CC4TorchVecEnv:
         out=(hosts, glob) reuses the caller's tensors.  Ordered on the current stream both ways like step(); no host copy, no host wait.  A
         faulty entry (an index out of range, a slot never written or written by another configuration) gives an all-zero row, and
         check_errors() raises CC4EngineError for it."""
-        return self._view('cc4_state_features_device', ids, bank, out, (((L.FEAT_HOSTS, L.FEAT_PER_HOST), torch.uint8, 1), ((L.FEAT_GLOBAL,), torch.int32, 1)))
+        return self._view('state_features', ids, bank, out)
 
     def red_view(self, ids=None, bank=None, out=None):
         """What each red agent knows (cc4_red_view_device, include/cc4.h; columns and words: red_view.HOST_COLUMNS / SCALAR_WORDS) as tensors on
         the env's device: (hosts [n, 6, 137, 8] uint8, scalars [n, 6, 16] int32).  ids, bank, out and the ordering on the current stream as
         state_features(); no host copy, no host wait.  A faulty entry gives all-zero rows, and check_errors() raises CC4EngineError for it."""
-        return self._view('cc4_red_view_device', ids, bank, out, (((L.NUM_RED, L.RED_VIEW_HOSTS, L.RED_VIEW_PER_HOST), torch.uint8, 1),
-                                                                 ((L.NUM_RED, L.RED_VIEW_SCALARS), torch.int32, 1)))
+        return self._view('red_view', ids, bank, out)
 
     def blue_view(self, ids=None, bank=None, out=None):
         """Blue's own knowledge (cc4_blue_view_device, include/cc4.h; columns and words: blue_view.HOST_COLUMNS / SCALAR_WORDS) as tensors on the
@@ -352,8 +345,7 @@ class CC4TorchVecEnv:
         the deployed decoy, suspicious pids, and with enable_event_log() the Monitor's entries per host (scalars[..., 10]: whether they are
         filled).  ids, bank, out and the ordering on the current stream as state_features(); no host copy, no host wait.  A faulty entry gives
         all-zero rows, and check_errors() raises CC4EngineError for it."""
-        return self._view('cc4_blue_view_device', ids, bank, out, (((L.NUM_BLUE, L.BLUE_VIEW_HOSTS, L.BLUE_VIEW_PER_HOST), torch.uint8, 1),
-                                                                  ((L.NUM_BLUE, L.BLUE_VIEW_SCALARS), torch.int32, 1)))
+        return self._view('blue_view', ids, bank, out)
 
     def blue_edges(self, ids=None, bank=None, out=None, max_edges=L.BLUE_EDGES_MAX):
         """The Monitor's connection entries of the step just taken as edge lists (cc4_blue_edges_device, include/cc4.h; columns and words:
@@ -364,11 +356,8 @@ class CC4TorchVecEnv:
         one launch per step, and leaves the one-launch forms of run / plan calls); without it every row is -1 and counts[:, 6] is 0.
         ids, bank, out and the ordering on the current stream as state_features(); no host copy, no host wait.  A faulty entry gives -1 rows
         and zero counts, and check_errors() raises CC4EngineError for it."""
-        max_edges = int(max_edges)
-        if not 1 <= max_edges <= L.BLUE_EDGES_MAX:
-            raise ValueError(f'max_edges must be 1 .. {L.BLUE_EDGES_MAX}, got {max_edges}')
-        return self._view('cc4_blue_edges_device', ids, bank, out, (((max_edges, L.BLUE_EDGES_COLUMNS), torch.int32, 16), ((L.BLUE_EDGES_WORDS,), torch.int32, 1)),
-                          max_edges)
+        max_edges = V.check_max_edges(max_edges)
+        return self._view('blue_edges', ids, bank, out, max_edges, max_edges=max_edges)
 
     def sample_actions(self, logits=None, *, seed=0, t=None, temperature=1.0, greedy=False, busy_aware=True, ids=None, bank=None, out=None):
         """Valid blue actions drawn from policy logits in one launch (cc4_sample_actions_device, include/cc4.h; the definition:
@@ -380,7 +369,7 @@ class CC4TorchVecEnv:
         ids, bank, out and the ordering on the current stream as state_features(); no host copy, no host wait.  A faulty entry gives -1 actions
         and zero stats, an agent whose valid logits hold a NaN or +inf or are all -inf gets -1 alone; check_errors() raises CC4EngineError for
         either."""
-        from .action_sampling import check_temperature, flags_of
+        from .action_sampling import check_temperature, flags_of, noise_words
         temperature = check_temperature(temperature)
         n = int(ids.numel()) if torch.is_tensor(ids) else (int(bank.shape[0]) if torch.is_tensor(bank) else self.num_envs)
         code, lp = 3, None
@@ -388,11 +377,10 @@ class CC4TorchVecEnv:
             if (not torch.is_tensor(logits) or tuple(logits.shape) != (n, L.MASK_PER_ENV) or logits.dtype not in _LOGIT_DTYPES
                     or logits.device != self.device or not logits.is_contiguous()):
                 raise ValueError(f'logits must be a contiguous float16, bfloat16 or float32 tensor [{n}, {L.MASK_PER_ENV}] on {self.device}')
-            code, lp = _LOGIT_DTYPES[logits.dtype], ctypes.c_void_p(logits.data_ptr())
+            code, lp = _LOGIT_DTYPES[logits.dtype], _dptr(logits)
         if t is None:
             t, self._sample_t = self._sample_t, self._sample_t + 1
-        return self._view('cc4_sample_actions_device', ids, bank, out, (((L.NUM_BLUE,), torch.int32, 4), ((L.NUM_BLUE, 2), torch.float32, 4)),
-                          code, lp, int(seed) & (2 ** 64 - 1), int(t) & 0xFFFFFFFF, temperature, flags_of(greedy, busy_aware))
+        return self._view('sample_actions', ids, bank, out, code, lp, *noise_words(seed, t), temperature, flags_of(greedy, busy_aware))
 
     def evaluate_actions(self, logits, mask, actions, temperature=1.0):
         """action_logp.evaluate_actions: (logp, entropy) of stored actions under new logits, differentiable with respect to the logits -- the
@@ -405,10 +393,7 @@ class CC4TorchVecEnv:
         blue_view() (entries per host, ports, remote hosts, the deployed decoy).  The log has a price: an env with the log on runs the full
         builds of its step kernel, one launch per step, and leaves the one-launch forms of run / plan calls.  Without it blue_view() still
         carries busy / success / what Analyse found / sus_pids."""
-        with torch.cuda.device(self.device):
-            s = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            self.venv._chk(self.lib.cc4_stream_wait(self._h, s), 'cc4_stream_wait')
-            self.venv.enable_event_log(on)
+        self._call('cc4_enable_event_log', int(bool(on)))
 
     def reward_terms(self, ids=None, bank=None, out=None):
         """Why the last step's reward was what it was (cc4_reward_terms_device, include/cc4.h; columns and words: reward_terms.TERM_COLUMNS /
@@ -418,52 +403,28 @@ class CC4TorchVecEnv:
         (enable_reward_terms(), or an env that steps with red_actions); then words[:, 3] + words[:, 4] == reward.  ids, bank, out and the
         ordering on the current stream as state_features(); no host copy, no host wait.  A faulty entry gives all-zero rows, and
         check_errors() raises CC4EngineError for it."""
-        return self._view('cc4_reward_terms_device', ids, bank, out, (((L.REWARD_SUBNETS, L.REWARD_COLS), torch.int32, 16), ((L.REWARD_WORDS,), torch.int32, 16)))
+        return self._view('reward_terms', ids, bank, out)
 
     def enable_reward_terms(self, on=True):
         """CC4VecEnv.enable_reward_terms (cc4_enable_reward_terms): record the pieces of every step's reward, which reward_terms() turns into
         tensors.  The record has a price: the env runs the full builds of its step kernel, one launch per step, and leaves the one-launch
         forms of run / plan calls (after a plan only the last step's terms exist).  An env that steps with red_actions records anyway."""
-        with torch.cuda.device(self.device):
-            s = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            self.venv._chk(self.lib.cc4_stream_wait(self._h, s), 'cc4_stream_wait')
-            self.venv.enable_reward_terms(on)
-            self.venv._chk(self.lib.cc4_stream_signal(self._h, s), 'cc4_stream_signal')
+        self._call('cc4_enable_reward_terms', int(bool(on)))
 
     def set_opponents(self, red=None, green=None, blue=None):
         """Assign opponent classes per episode from the device (cc4_set_policies_device, include/cc4.h): red (0..3), green (0..1), blue (0..1) each
         an integer tensor [N] on the env's device or None (keep); an entry may be L.POLICY_KEEP or L.POLICY_DEFAULT.  Takes effect at each
         episode's next regeneration (reset, autoreset), never mid-episode.  On the current stream, no host wait; a refused entry (a class out of
         range) leaves its episode as it was, and check_errors() raises CC4EngineError for it."""
-        n = self.num_envs
-        with torch.cuda.device(self.device):
-            s = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            ptrs, keep = [], []
-            for x, what in ((red, 'red'), (green, 'green'), (blue, 'blue')):
-                if x is None:
-                    ptrs.append(None)
-                    continue
-                if not torch.is_tensor(x) or tuple(x.shape) != (n,) or x.dtype.is_floating_point or x.dtype == torch.bool or x.device != self.device:
-                    raise ValueError(f'{what} must be an integer tensor [{n}] on {self.device}')
-                x = x.clamp(-128, 127).to(torch.int8).contiguous()      # (a value beyond int8 stays out of range instead of wrapping into it)
-                keep.append(x)
-                ptrs.append(ctypes.c_void_p(x.data_ptr()))
-            rc = self.lib.cc4_stream_wait(self._h, s) or self.lib.cc4_set_policies_device(self._h, *ptrs)
-            if rc:
-                self.venv._chk(rc, 'cc4_set_policies_device')
-            self.venv._chk(self.lib.cc4_stream_signal(self._h, s), 'cc4_stream_signal')
+        classes = [None if x is None else int_tensor(x, (self.num_envs,), self.device, what, to=torch.int8, saturate=True)
+                   for x, what in ((red, 'red'), (green, 'green'), (blue, 'blue'))]
+        self._call('cc4_set_policies_device', *map(_dptr, classes))
 
     def opponents(self):
         """(live, assigned): two fresh [N, 3] int8 tensors of (red, green, blue) classes -- what every episode runs now, and what it regenerates
         into (L.POLICY_DEFAULT where it carries no assignment).  On the current stream, no host wait."""
-        with torch.cuda.device(self.device):
-            s = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            live = torch.empty((self.num_envs, 3), dtype=torch.int8, device=self.device)
-            assigned = torch.empty((self.num_envs, 3), dtype=torch.int8, device=self.device)
-            rc = self.lib.cc4_stream_wait(self._h, s) or self.lib.cc4_policies_device(self._h, ctypes.c_void_p(live.data_ptr()), ctypes.c_void_p(assigned.data_ptr()))
-            if rc:
-                self.venv._chk(rc, 'cc4_policies_device')
-            self.venv._chk(self.lib.cc4_stream_signal(self._h, s), 'cc4_stream_signal')
+        live, assigned = (torch.empty((self.num_envs, 3), dtype=torch.int8, device=self.device) for _ in range(2))
+        self._call('cc4_policies_device', _dptr(live), _dptr(assigned))
         return live, assigned
 
     def check_errors(self):

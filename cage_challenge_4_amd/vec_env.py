@@ -7,6 +7,7 @@ Observations are returned as one int32 array [N, 578] = agents 0..3 (92 each) th
 import ctypes
 import numpy as np
 from . import _lib as L
+from . import _views as V
 
 RNG_PCG64 = 0    # numpy Generator(PCG64(SeedSequence(seed))): bit-exact with the reference under the same seed
 RNG_PHILOX = 1   # Philox4x32-10 keyed by seed, counter (draw, stream, step, episode)
@@ -60,6 +61,99 @@ def raise_on_engine_error(err):
     bad = np.nonzero(err)[0]
     raise CC4EngineError(f"engine error flags on {bad.size} episode(s), first: episode {int(bad[0])} {err_names(err[bad[0]])} "
                          f"(see ERR_NAMES / include/cc4.h; results of a flagged episode may differ from the reference)")
+
+
+# ---- the argument path of the host surface: whatever the caller holds -> a contiguous array of the entry point's dtype (None stays None), or a
+# ValueError that names the argument and the shape it must have.  An array of that dtype, contiguous already, passes through without a copy.
+def _shaped(x, dtype, shape, what):
+    """shape: the extents; None: any extent of at least one."""
+    a = np.ascontiguousarray(x, dtype=dtype)
+    if a.shape != shape and (a.ndim != len(shape) or any(g < 1 if w is None else g != w for w, g in zip(shape, a.shape))):
+        want = ', '.join('k' if w is None else str(w) for w in shape)
+        raise ValueError(f'{what} must have shape [{want}]{" with k >= 1" if None in shape else ""}, got {list(a.shape)}')
+    return a
+
+
+def as_seeds(x, n, what='seeds'):
+    """uint64 [n]; a scalar s stands for s, s + 1, ..."""
+    if x is None:
+        return None
+    return _shaped(np.uint64(x) + np.arange(n, dtype=np.uint64) if np.isscalar(x) else x, np.uint64, (n,), what)
+
+
+def as_env_mask(x, n):
+    """uint8 [n]: nonzero selects the episode."""
+    return None if x is None else _shaped(x, np.uint8, (n,), 'env_mask')
+
+
+def _batch(x, dtype, n, k, tail, what):
+    """[n, *tail]; with k a plan of them, [k, n, *tail] (k = 0: of any length k >= 1)."""
+    return None if x is None else _shaped(x, dtype, (() if k is None else (k or None,)) + (n,) + tail, what)
+
+
+def as_actions(x, n, k=None):
+    """int32 [n, 5] wrapper indices, from any integer dtype; with k a plan [k, n, 5] (k = 0: of any length k >= 1)."""
+    return _batch(x, np.int32, n, k, (L.NUM_BLUE,), 'actions')
+
+
+def as_messages(x, n, k=None):
+    """uint8 [n, 5, 8] of 0 / 1; with k the messages of a plan [k, n, 5, 8]."""
+    return _batch(x, np.uint8, n, k, (L.NUM_BLUE, L.MSG_LEN), 'messages')
+
+
+def as_ptr(x):
+    """What ctypes takes for a void*: an array's data, a device address (int), a ctypes.c_void_p as it is, None."""
+    if x is None or isinstance(x, ctypes.c_void_p):
+        return x
+    return x.ctypes.data_as(ctypes.c_void_p) if isinstance(x, np.ndarray) else ctypes.c_void_p(int(x))
+
+
+def stage_layout(parts):
+    """Where the parts of one staging allocation lie: parts are input arrays (placed at 16 bytes) or outputs (nbytes, alignment); returns
+    (offsets, total) with every part at a multiple of its alignment, in the order given, none overlapping."""
+    offsets, end = [], 0
+    for p in parts:
+        nbytes, align = (p.nbytes, 16) if isinstance(p, np.ndarray) else p
+        offsets.append(-(-end // align) * align)
+        end = offsets[-1] + nbytes
+    return offsets, end
+
+
+class Staged:
+    """One device allocation laid out by stage_layout, for the host-array forms of calls that work on device memory.  The leading input arrays go
+    up in one copy on entry, ptr(i) is part i's device address, down(i, out) copies output part i into the array `out`; freed on every path."""
+
+    def __init__(self, device, parts):
+        self.device, self.parts, self.d = device, parts, ctypes.c_void_p()
+        self.offsets, self.total = stage_layout(parts)
+
+    def __enter__(self):
+        hip = _hip()
+        _hip_chk(hip.hipSetDevice(self.device), 'hipSetDevice')
+        _hip_chk(hip.hipMalloc(ctypes.byref(self.d), max(self.total, 1)), 'hipMalloc')
+        try:
+            ins = [p for p in self.parts if isinstance(p, np.ndarray)]
+            if len(ins) > 1:                  # (several inputs: put together on the host as they will lie, so that one copy takes them up)
+                up = np.zeros(self.offsets[len(ins) - 1] + ins[-1].nbytes, np.uint8)
+                for a, o in zip(ins, self.offsets):
+                    up[o:o + a.nbytes] = a.reshape(-1).view(np.uint8)
+                ins = [up]
+            if ins and ins[0].nbytes:
+                _hip_chk(hip.hipMemcpy(self.d, as_ptr(ins[0]), ins[0].nbytes, 1), 'hipMemcpy')
+        except BaseException:
+            hip.hipFree(self.d)
+            raise
+        return self
+
+    def __exit__(self, *exc):
+        _hip().hipFree(self.d)
+
+    def ptr(self, i):
+        return ctypes.c_void_p(self.d.value + self.offsets[i])
+
+    def down(self, i, out):
+        _hip_chk(_hip().hipMemcpy(as_ptr(out), self.ptr(i), out.nbytes, 2), 'hipMemcpy')
+        return out
 
 
 class CC4VecEnv:
@@ -128,18 +222,8 @@ class CC4VecEnv:
     # -- API
     def reset(self, seeds=None, env_mask=None):
         """seeds: None (streams continue, == reference reset(seed=None)), int (seed+i per env) or array [N]."""
-        sp = None
-        if seeds is not None:
-            if np.isscalar(seeds):
-                seeds = np.uint64(seeds) + np.arange(self.num_envs, dtype=np.uint64)
-            seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
-            assert seeds.shape == (self.num_envs,)
-            sp = seeds.ctypes.data_as(ctypes.c_void_p)
-        mp = None
-        if env_mask is not None:
-            env_mask = np.ascontiguousarray(env_mask, dtype=np.uint8)
-            mp = env_mask.ctypes.data_as(ctypes.c_void_p)
-        self._chk(self.lib.cc4_reset(self._h, sp, mp), 'cc4_reset')
+        seeds, env_mask = as_seeds(seeds, self.num_envs), as_env_mask(env_mask, self.num_envs)
+        self._chk(self.lib.cc4_reset(self._h, as_ptr(seeds), as_ptr(env_mask)), 'cc4_reset')
         return self._fetch(mask=True)[0]
 
     def _policy_array(self, v, name):
@@ -160,8 +244,11 @@ class CC4VecEnv:
         at the episode's next regeneration (reset, autoreset), never mid-episode.  Refused entries (a class out of range) leave their
         episodes as they were and raise CC4EngineError after the others applied."""
         arrs = [self._policy_array(v, k) for k, v in (('red', red), ('green', green), ('blue', blue))]
-        ptrs = [None if a is None else a.ctypes.data_as(ctypes.c_void_p) for a in arrs]
-        self._chk(self.lib.cc4_set_policies(self._h, *ptrs), 'cc4_set_policies')
+        self._chk(self.lib.cc4_set_policies(self._h, *map(as_ptr, arrs)), 'cc4_set_policies')
+        self._raise_copy_faults()
+
+    def _raise_copy_faults(self):
+        """Read (and clear) the faults the copies, views and assignments recorded since the last read; CC4EngineError if there are any."""
         faults = ctypes.c_uint32(0)
         self._chk(self.lib.cc4_copy_faults(self._h, ctypes.byref(faults)), 'cc4_copy_faults')
         raise_on_copy_faults(faults.value)
@@ -176,18 +263,9 @@ class CC4VecEnv:
 
     def step(self, actions=None, messages=None):
         """actions: int array [N,5] of wrapper indices (None / negative = no action -> Sleep)."""
-        ap = None
-        if actions is not None:
-            actions = np.ascontiguousarray(actions, dtype=np.int32)
-            assert actions.shape == (self.num_envs, L.NUM_BLUE)
-            ap = actions.ctypes.data_as(ctypes.c_void_p)
-        mp = None
-        if messages is not None:
-            messages = np.ascontiguousarray(messages, dtype=np.uint8)
-            assert messages.shape == (self.num_envs, L.NUM_BLUE, L.MSG_LEN)
-            mp = messages.ctypes.data_as(ctypes.c_void_p)
+        actions, messages = as_actions(actions, self.num_envs), as_messages(messages, self.num_envs)
         # cc4_step + cc4_fetch in one call: inputs up in one copy, the launch, the four results down in one copy, one host wait
-        rc = self.lib.cc4_step_fetch(self._h, ap, mp, *self._p_out)
+        rc = self.lib.cc4_step_fetch(self._h, as_ptr(actions), as_ptr(messages), *self._p_out)
         if rc:
             self._chk(rc, 'cc4_step_fetch')
         obs, rew, done = self._check_err()
@@ -203,24 +281,10 @@ class CC4VecEnv:
     def step_ex(self, actions=None, messages=None, red=None, green=None):
         """cc4_step_ex: a step that also takes the red / green entries of the reference's `actions` dict (SimulationController.py:
         236-240) as agent_actions() arrays.  The blue indices may carry `action.duration` in bits 20..27."""
-        ap = mp = rp = gp = None
-        if actions is not None:
-            actions = np.ascontiguousarray(actions, dtype=np.int32)
-            assert actions.shape == (self.num_envs, L.NUM_BLUE)
-            ap = actions.ctypes.data_as(ctypes.c_void_p)
-        if messages is not None:
-            messages = np.ascontiguousarray(messages, dtype=np.uint8)
-            assert messages.shape == (self.num_envs, L.NUM_BLUE, L.MSG_LEN)
-            mp = messages.ctypes.data_as(ctypes.c_void_p)
-        if red is not None:
-            red = np.ascontiguousarray(red, dtype=L.AGENT_ACTION_DTYPE)
-            assert red.shape == (self.num_envs, L.NUM_RED) and red.dtype.itemsize == 24
-            rp = red.ctypes.data_as(ctypes.c_void_p)
-        if green is not None:
-            green = np.ascontiguousarray(green, dtype=L.AGENT_ACTION_DTYPE)
-            assert green.shape == (self.num_envs, L.MAX_GREEN) and green.dtype.itemsize == 24
-            gp = green.ctypes.data_as(ctypes.c_void_p)
-        self._chk(self.lib.cc4_step_ex(self._h, ap, mp, rp, gp), 'cc4_step_ex')
+        n = self.num_envs
+        args = (as_actions(actions, n), as_messages(messages, n), _batch(red, L.AGENT_ACTION_DTYPE, n, None, (L.NUM_RED,), 'red'),
+                _batch(green, L.AGENT_ACTION_DTYPE, n, None, (L.MAX_GREEN,), 'green'))
+        self._chk(self.lib.cc4_step_ex(self._h, *map(as_ptr, args)), 'cc4_step_ex')
         obs, rew, done = self._fetch()
         return obs, rew, done, {'err': self._err}
 
@@ -293,11 +357,9 @@ class CC4VecEnv:
 
     def set_seed(self, seeds):
         """cc4_set_seed: fresh generators (CybORG.set_seed) without touching the episodes."""
-        if np.isscalar(seeds):
-            seeds = np.uint64(seeds) + np.arange(self.num_envs, dtype=np.uint64)
-        seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
-        assert seeds.shape == (self.num_envs,)
-        self._chk(self.lib.cc4_set_seed(self._h, seeds.ctypes.data_as(ctypes.c_void_p)), 'cc4_set_seed')
+        if seeds is None:
+            raise ValueError('seeds must be a scalar or have shape [N]')
+        self._chk(self.lib.cc4_set_seed(self._h, as_ptr(as_seeds(seeds, self.num_envs))), 'cc4_set_seed')
 
     def set_generators(self, generators):
         """cc4_set_rng_state: adopt the streams of numpy Generator(PCG64) objects (one per episode).  The objects themselves are
@@ -398,9 +460,8 @@ class CC4VecEnv:
         return cold
 
     def set_state(self, env, buf):
-        buf = np.ascontiguousarray(buf, dtype=np.uint8)
-        assert buf.size == self.lib.cc4_state_bytes()
-        self._chk(self.lib.cc4_set_state(self._h, int(env), buf.ctypes.data_as(ctypes.c_void_p)), 'cc4_set_state')
+        buf = _shaped(np.ravel(buf), np.uint8, (self.lib.cc4_state_bytes(),), 'a hot row')
+        self._chk(self.lib.cc4_set_state(self._h, int(env), as_ptr(buf)), 'cc4_set_state')
 
     def snapshot(self, env):
         """Full episode snapshot (hot + cold row) for checkpointing / tree search / parity bisecting."""
@@ -411,9 +472,8 @@ class CC4VecEnv:
     def restore(self, env, snap):
         hot, cold = snap
         self.set_state(env, hot)
-        cold = np.ascontiguousarray(cold, dtype=np.uint8)
-        assert cold.size == self.lib.cc4_cold_bytes(self._h)
-        self._chk(self.lib.cc4_set_cold(self._h, int(env), cold.ctypes.data_as(ctypes.c_void_p)), 'cc4_set_cold')
+        cold = _shaped(np.ravel(cold), np.uint8, (self.lib.cc4_cold_bytes(self._h),), 'a cold row')
+        self._chk(self.lib.cc4_set_cold(self._h, int(env), as_ptr(cold)), 'cc4_set_cold')
 
     def clone_episodes(self, src, dst, seeds=None):
         """Episode dst[i] becomes a copy of episode src[i] (cc4_clone_episodes: the device copy of cc4_copy_episodes_device, include/cc4.h);
@@ -424,61 +484,44 @@ class CC4VecEnv:
         dst = np.ascontiguousarray(dst, dtype=np.int32).ravel()
         if src.shape != dst.shape:
             raise ValueError('src and dst must have the same length')
-        sp = None
-        if seeds is not None:
-            seeds = np.ascontiguousarray(seeds, dtype=np.uint64).ravel()
-            if seeds.shape != src.shape:
-                raise ValueError('seeds must have one entry per copy')
-            sp = seeds.ctypes.data_as(ctypes.c_void_p)
-        vp = ctypes.c_void_p
-        self._chk(self.lib.cc4_clone_episodes(self._h, int(src.size), src.ctypes.data_as(vp), dst.ctypes.data_as(vp), sp), 'cc4_clone_episodes')
-        faults = ctypes.c_uint32(0)
-        self._chk(self.lib.cc4_copy_faults(self._h, ctypes.byref(faults)), 'cc4_copy_faults')
+        seeds = as_seeds(None if seeds is None else np.ravel(seeds), src.size, 'seeds (one entry per copy)')
+        self._chk(self.lib.cc4_clone_episodes(self._h, int(src.size), as_ptr(src), as_ptr(dst), as_ptr(seeds)), 'cc4_clone_episodes')
         ok = dst[(dst >= 0) & (dst < self.num_envs)]
         self._err_seen[ok] = 0
         self._chk(self.lib.cc4_fetch(self._h, *self._p_out), 'cc4_fetch')
-        self._chk(self.lib.cc4_get_action_mask(self._h, self._mask.ctypes.data_as(vp)), 'cc4_get_action_mask')
-        raise_on_copy_faults(faults.value)
+        self._chk(self.lib.cc4_get_action_mask(self._h, as_ptr(self._mask)), 'cc4_get_action_mask')
+        self._raise_copy_faults()            # (of this copy: the outputs above are those of the entries that applied)
         return self._check_err()[0]
 
-    def _view(self, entry, ids, outs, *extra):
-        """What the NumPy getters of the derived views share.  entry: the cc4_*_device entry point; ids: episodes (None: all); outs: (shape of one
-        entry, dtype, the fill of the view's empty output) of its two arrays; extra: arguments in front of the two output pointers.  One device
-        allocation [ids | first | second], every part aligned as the entry point asks, the call, a synchronise like the other getters, two copies
-        down.  An index out of range leaves the empty output in its row and raises CC4EngineError after the call."""
+    def _view(self, view, ids, extra=(), max_edges=None, inp=None):
+        """What the NumPy getters of the derived views share.  view: its name in _views.VIEWS, which says what its two arrays are, what an empty
+        row holds and how the entry point wants them aligned; ids: episodes (None: all); inp: an input array that goes up with the ids; extra:
+        the arguments in front of the two output pointers, or a function of inp's device address that gives them.  One staging block
+        [ids | inp | first | second], the call, a synchronise like the other getters, two copies down.  An index out of range leaves the empty
+        output in its row and raises CC4EngineError after the call."""
         ids = None if ids is None else np.ascontiguousarray(ids, dtype=np.int32).ravel()
         n = self.num_envs if ids is None else int(ids.size)
-        a, b = (np.full((n,) + tuple(shape), fill, dtype) for shape, dtype, fill in outs)
+        a, b = V.empty(view, (n,), max_edges)
         if n == 0:
             return a, b
-        hip, vp = _hip(), ctypes.c_void_p
-        b_ids = ((4 * n + 15) & ~15) if ids is not None else 0
-        _hip_chk(hip.hipSetDevice(self._dev), 'hipSetDevice')
-        d = vp()
-        _hip_chk(hip.hipMalloc(ctypes.byref(d), b_ids + a.nbytes + b.nbytes), 'hipMalloc')
-        try:
-            if ids is not None:
-                _hip_chk(hip.hipMemcpy(d, ids.ctypes.data_as(vp), ids.nbytes, 1), 'hipMemcpy')
-            d_a, d_b = vp(d.value + b_ids), vp(d.value + b_ids + a.nbytes)
-            rc = getattr(self.lib, entry)(self._h, None, 0, d if ids is not None else None, n, *extra, d_a, d_b)
+        ins = [x for x in (ids, inp) if x is not None]
+        with Staged(self._dev, ins + [(x.nbytes, o.align) for x, o in zip((a, b), V.VIEWS[view].outs)]) as st:
+            if callable(extra):
+                extra = extra(st.ptr(len(ins) - 1) if inp is not None else None)
+            entry = V.VIEWS[view].device
+            rc = getattr(self.lib, entry)(self._h, None, 0, st.ptr(0) if ids is not None else None, n, *extra, st.ptr(len(ins)), st.ptr(len(ins) + 1))
             rc2 = self.lib.cc4_synchronize(self._h)
             if rc or rc2:
                 self._chk(rc or rc2, entry)
-            _hip_chk(hip.hipMemcpy(a.ctypes.data_as(vp), d_a, a.nbytes, 2), 'hipMemcpy')
-            _hip_chk(hip.hipMemcpy(b.ctypes.data_as(vp), d_b, b.nbytes, 2), 'hipMemcpy')
-        finally:
-            hip.hipFree(d)
+            st.down(len(ins), a), st.down(len(ins) + 1, b)
         if ids is not None and ((ids < 0) | (ids >= self.num_envs)).any():
-            faults = ctypes.c_uint32(0)
-            self._chk(self.lib.cc4_copy_faults(self._h, ctypes.byref(faults)), 'cc4_copy_faults')
-            raise_on_copy_faults(faults.value)
+            self._raise_copy_faults()
         return a, b
 
-    def _view_device(self, entry, d_a, d_b, n, d_ids, d_bank, capacity, *extra):
+    def _view_device(self, view, d_a, d_b, n, d_ids, d_bank, capacity, *extra):
         """The *_device forms of the views: the entry point on device addresses of the caller's (int or ctypes.c_void_p).  Enqueued, no host wait."""
-        vp = ctypes.c_void_p
-        as_p = lambda x: x if x is None or isinstance(x, vp) else vp(int(x))      # noqa: E731
-        rc = getattr(self.lib, entry)(self._h, as_p(d_bank), int(capacity), as_p(d_ids), self.num_envs if n is None else int(n), *extra, as_p(d_a), as_p(d_b))
+        entry = V.VIEWS[view].device
+        rc = getattr(self.lib, entry)(self._h, as_ptr(d_bank), int(capacity), as_ptr(d_ids), self.num_envs if n is None else int(n), *extra, as_ptr(d_a), as_ptr(d_b))
         if rc:
             self._chk(rc, entry)
 
@@ -486,15 +529,13 @@ class CC4VecEnv:
         """The privileged global state of the batch (cc4_state_features_device, include/cc4.h; columns and words: state_features.HOST_COLUMNS /
         GLOBAL_WORDS): (hosts [n, 137, 16] uint8, glob [n, 32] int32) of episodes env_ids (None: all), as NumPy arrays.  Synchronises, like
         the other getters.  An index out of range gives an all-zero row and raises CC4EngineError after the call."""
-        return self._view('cc4_state_features_device', env_ids, (((L.FEAT_HOSTS, L.FEAT_PER_HOST), np.uint8, 0), ((L.FEAT_GLOBAL,), np.int32, 0)))
+        return self._view('state_features', env_ids)
 
     def step_red_device(self, d_actions, d_messages, d_red):
         """cc4_step_red_device: a step with the blue indices [N, 5] int32, the messages [N, 5, 8] bytes (or None) and the red actions
         [N, 6, 4] int32 (red_view.ACTION_WORDS) all in device memory, given as device addresses (int or ctypes.c_void_p).  Enqueued, no host
         wait: fetch the outputs with the getters, or read them on the device."""
-        vp = ctypes.c_void_p
-        as_p = lambda x: x if x is None or isinstance(x, vp) else vp(int(x))      # noqa: E731
-        rc = self.lib.cc4_step_red_device(self._h, as_p(d_actions), as_p(d_messages), as_p(d_red))
+        rc = self.lib.cc4_step_red_device(self._h, as_ptr(d_actions), as_ptr(d_messages), as_ptr(d_red))
         if rc:
             self._chk(rc, 'cc4_step_red_device')
 
@@ -502,34 +543,32 @@ class CC4VecEnv:
         """cc4_red_view_device into device memory of the caller's (device addresses): hosts [n, 6, 137, 8] uint8, 16-byte aligned, scalars
         [n, 6, 16] int32 or None, of episodes d_ids (int32 [n] on the device; None: 0 .. n-1) of the env or of the slots of a snapshot bank.
         Enqueued, no host wait."""
-        self._view_device('cc4_red_view_device', d_hosts, d_scalars, n, d_ids, d_bank, capacity)
+        self._view_device('red_view', d_hosts, d_scalars, n, d_ids, d_bank, capacity)
 
     def red_view(self, env_ids=None):
         """What each red agent knows (cc4_red_view_device, include/cc4.h; columns and words: red_view.HOST_COLUMNS / SCALAR_WORDS):
         (hosts [n, 6, 137, 8] uint8, scalars [n, 6, 16] int32) of episodes env_ids (None: all), as NumPy arrays.  Synchronises, like the other
         getters.  An index out of range gives all-zero rows and raises CC4EngineError after the call."""
-        return self._view('cc4_red_view_device', env_ids, (((L.NUM_RED, L.RED_VIEW_HOSTS, L.RED_VIEW_PER_HOST), np.uint8, 0),
-                                                          ((L.NUM_RED, L.RED_VIEW_SCALARS), np.int32, 0)))
+        return self._view('red_view', env_ids)
 
     def blue_view_device(self, d_hosts, d_scalars=None, n=None, d_ids=None, d_bank=None, capacity=0):
         """cc4_blue_view_device into device memory of the caller's (device addresses): hosts [n, 5, 137, 8] uint8, 8-byte aligned, scalars
         [n, 5, 16] int32 or None, of episodes d_ids (int32 [n] on the device; None: 0 .. n-1) of the env or of the slots of a snapshot bank.
         Enqueued, no host wait."""
-        self._view_device('cc4_blue_view_device', d_hosts, d_scalars, n, d_ids, d_bank, capacity)
+        self._view_device('blue_view', d_hosts, d_scalars, n, d_ids, d_bank, capacity)
 
     def blue_view(self, env_ids=None):
         """Blue's own knowledge (cc4_blue_view_device, include/cc4.h; columns and words: blue_view.HOST_COLUMNS / SCALAR_WORDS):
         (hosts [n, 5, 137, 8] uint8, scalars [n, 5, 16] int32) of episodes env_ids (None: all), as NumPy arrays.  Synchronises, like the other
         getters.  The event columns need enable_event_log(); scalars[..., 10] says whether they are filled.  An index out of range gives
         all-zero rows and raises CC4EngineError after the call."""
-        return self._view('cc4_blue_view_device', env_ids, (((L.NUM_BLUE, L.BLUE_VIEW_HOSTS, L.BLUE_VIEW_PER_HOST), np.uint8, 0),
-                                                           ((L.NUM_BLUE, L.BLUE_VIEW_SCALARS), np.int32, 0)))
+        return self._view('blue_view', env_ids)
 
     def blue_edges_device(self, d_edges, d_counts=None, n=None, d_ids=None, d_bank=None, capacity=0, max_edges=L.BLUE_EDGES_MAX):
         """cc4_blue_edges_device into device memory of the caller's (device addresses): edges [n, max_edges, 8] int32, 16-byte aligned, counts
         [n, 8] int32 or None, of episodes d_ids (int32 [n] on the device; None: 0 .. n-1) of the env or of the slots of a snapshot bank.
         Enqueued, no host wait."""
-        self._view_device('cc4_blue_edges_device', d_edges, d_counts, n, d_ids, d_bank, capacity, int(max_edges))
+        self._view_device('blue_edges', d_edges, d_counts, n, d_ids, d_bank, capacity, int(max_edges))
 
     def blue_edges(self, ids=None, max_edges=L.BLUE_EDGES_MAX):
         """The Monitor's connection entries of the step just taken as edge lists (cc4_blue_edges_device, include/cc4.h; columns and words:
@@ -538,20 +577,17 @@ class CC4VecEnv:
         The per-step log must be on (enable_event_log()) -- an env with the log on runs the full builds of its step kernel, one launch per step,
         and leaves the one-launch forms of run / plan calls; without it every row is -1 and counts[:, 6] is 0.  An index out of range gives
         -1 rows and zero counts and raises CC4EngineError after the call."""
-        max_edges = int(max_edges)
-        if not 1 <= max_edges <= L.BLUE_EDGES_MAX:
-            raise ValueError(f'max_edges must be 1 .. {L.BLUE_EDGES_MAX}, got {max_edges}')
-        return self._view('cc4_blue_edges_device', ids, (((max_edges, L.BLUE_EDGES_COLUMNS), np.int32, -1), ((L.BLUE_EDGES_WORDS,), np.int32, 0)), max_edges)
+        max_edges = V.check_max_edges(max_edges)
+        return self._view('blue_edges', ids, (max_edges,), max_edges)
 
     def sample_actions_device(self, d_actions, d_stats=None, d_logits=None, logits_dtype=3, seed=0, t=0, temperature=1.0, flags=L.SAMPLE_BUSY,
                               n=None, d_ids=None, d_bank=None, capacity=0):
         """cc4_sample_actions_device on device memory of the caller's (device addresses): logits [n, 570] in logits_dtype (1 float16, 2 bfloat16,
         3 float32; None: uniform over the valid slots) -> actions [n, 5] int32 and stats [n, 5, 2] float32 (or None), of episodes d_ids (int32
         [n] on the device; None: 0 .. n-1) of the env or of the slots of a snapshot bank.  Enqueued, no host wait."""
-        vp = ctypes.c_void_p
-        as_p = lambda x: x if x is None or isinstance(x, vp) else vp(int(x))      # noqa: E731
-        self._view_device('cc4_sample_actions_device', d_actions, d_stats, n, d_ids, d_bank, capacity, int(logits_dtype), as_p(d_logits),
-                          int(seed) & (2 ** 64 - 1), int(t) & 0xFFFFFFFF, float(temperature), int(flags))
+        from .action_sampling import noise_words
+        self._view_device('sample_actions', d_actions, d_stats, n, d_ids, d_bank, capacity, int(logits_dtype), as_ptr(d_logits),
+                          *noise_words(seed, t), float(temperature), int(flags))
 
     def sample_actions(self, logits=None, ids=None, seed=0, t=0, temperature=1.0, greedy=False, busy_aware=True):
         """Valid blue actions drawn from policy logits (cc4_sample_actions_device, include/cc4.h; the definition: action_sampling):
@@ -563,11 +599,8 @@ class CC4VecEnv:
         from . import action_sampling as AS
         temperature = AS.check_temperature(temperature)
         n = self.num_envs if ids is None else int(np.asarray(ids).size)
-        extra = lambda dt, p: (dt, p, int(seed) & (2 ** 64 - 1), int(t) & 0xFFFFFFFF, temperature, AS.flags_of(greedy, busy_aware))      # noqa: E731
-        outs = (((L.NUM_BLUE,), np.int32, -1), ((L.NUM_BLUE, 2), np.float32, 0))
-        if logits is None:
-            a, st = self._view('cc4_sample_actions_device', ids, outs, *extra(3, None))
-        else:
+        code, lg = 3, None
+        if logits is not None:
             lg = np.asarray(logits)
             if lg.shape != (n, L.MASK_PER_ENV):
                 raise ValueError(f'logits must have shape ({n}, {L.MASK_PER_ENV}), got {lg.shape}')
@@ -577,20 +610,9 @@ class CC4VecEnv:
             if code is None:
                 raise ValueError(f'logits must be float16, float32 (or uint16: bfloat16 bit patterns), got {lg.dtype}')
             lg = np.ascontiguousarray(lg)
-            if n == 0:
-                return self._view('cc4_sample_actions_device', ids, outs, *extra(code, None))
-            hip, vp = _hip(), ctypes.c_void_p
-            _hip_chk(hip.hipSetDevice(self._dev), 'hipSetDevice')
-            d = vp()
-            _hip_chk(hip.hipMalloc(ctypes.byref(d), lg.nbytes), 'hipMalloc')
-            try:
-                _hip_chk(hip.hipMemcpy(d, lg.ctypes.data_as(vp), lg.nbytes, 1), 'hipMemcpy')
-                a, st = self._view('cc4_sample_actions_device', ids, outs, *extra(code, d))
-            finally:
-                hip.hipFree(d)
-        faults = ctypes.c_uint32(0)
-        self._chk(self.lib.cc4_copy_faults(self._h, ctypes.byref(faults)), 'cc4_copy_faults')
-        raise_on_copy_faults(faults.value)
+        tail = (*AS.noise_words(seed, t), temperature, AS.flags_of(greedy, busy_aware))
+        a, st = self._view('sample_actions', ids, lambda d_logits: (code, d_logits, *tail), inp=lg)       # (the logits go up with the ids)
+        self._raise_copy_faults()
         return a, st
 
     def enable_reward_terms(self, on=True):
@@ -607,14 +629,14 @@ class CC4VecEnv:
         """cc4_reward_terms_device into device memory of the caller's (device addresses): terms [n, 9, 4] int32 and words [n, 16] int32 (or None),
         both 16-byte aligned, of episodes d_ids (int32 [n] on the device; None: 0 .. n-1) of the env or of the slots of a snapshot bank.
         Enqueued, no host wait."""
-        self._view_device('cc4_reward_terms_device', d_terms, d_words, n, d_ids, d_bank, capacity)
+        self._view_device('reward_terms', d_terms, d_words, n, d_ids, d_bank, capacity)
 
     def reward_terms(self, ids=None):
         """Why the last step's reward was what it was (cc4_reward_terms_device, include/cc4.h; columns and words: reward_terms.TERM_COLUMNS /
         WORDS): (terms [n, 9, 4] int32, words [n, 16] int32) of episodes ids (None: all), as NumPy arrays.  Synchronises, like the other
         getters.  words[:, 0] says whether the last step recorded (enable_reward_terms(), or an env that steps with red / green actions).  An
         index out of range gives all-zero rows and raises CC4EngineError after the call."""
-        return self._view('cc4_reward_terms_device', ids, (((L.REWARD_SUBNETS, L.REWARD_COLS), np.int32, 0), ((L.REWARD_WORDS,), np.int32, 0)))
+        return self._view('reward_terms', ids)
 
     def plan_kernel_for(self, k):
         """cc4_plan_kernel_for: the kernel a run_plan / step_plan call of k steps launches ('k_run_philox1p' / 'k_run_pcgp': one launch for the
@@ -628,38 +650,20 @@ class CC4VecEnv:
         after every step -- with record_obs.  The handle ends where k calls of step() would have left it; info['err'] holds every flag some
         step of the plan raised, and strict mode raises for them as step() does (a step past an episode's end raises ValueError in either
         mode); the exception's `plan_outputs` attribute is the tuple the call would have returned."""
-        actions = np.ascontiguousarray(actions, dtype=np.int32)
-        if actions.ndim != 3 or actions.shape[0] < 1 or actions.shape[1:] != (self.num_envs, L.NUM_BLUE):
-            raise ValueError(f'actions must be [k, {self.num_envs}, {L.NUM_BLUE}] with k >= 1')
-        k, n = int(actions.shape[0]), self.num_envs
-        if messages is not None:
-            messages = np.ascontiguousarray(messages, dtype=np.uint8)
-            if messages.shape != (k, n, L.NUM_BLUE, L.MSG_LEN):
-                raise ValueError(f'messages must be [{k}, {n}, {L.NUM_BLUE}, {L.MSG_LEN}]')
-        hip, vp = _hip(), ctypes.c_void_p
-        b_act, b_msg = actions.nbytes, (messages.nbytes if messages is not None else 0)
+        n = self.num_envs
+        actions = as_actions(actions, n, 0)
+        k = int(actions.shape[0])
+        messages = as_messages(messages, n, k)
+        ins = [actions] if messages is None else [actions, messages]             # [actions | messages]: one copy up
         b_rew, b_pk, b_done = 4 * k * n, (L.OBS_PACKED_BYTES * k * n if record_obs else 0), k * n
-        _hip_chk(hip.hipSetDevice(self._dev), 'hipSetDevice')
-        d_in, d_out = vp(), vp()
-        _hip_chk(hip.hipMalloc(ctypes.byref(d_in), b_act + b_msg), 'hipMalloc')
-        try:
-            _hip_chk(hip.hipMalloc(ctypes.byref(d_out), b_rew + b_pk + b_done), 'hipMalloc')
-            staged = np.empty(b_act + b_msg, np.uint8)                 # [actions | messages]: one copy up
-            staged[:b_act] = actions.reshape(-1).view(np.uint8)
-            if messages is not None:
-                staged[b_act:] = messages.reshape(-1)
-            _hip_chk(hip.hipMemcpy(d_in, staged.ctypes.data_as(vp), staged.nbytes, 1), 'hipMemcpy')
-            rc = self.lib.cc4_run_plan_device(self._h, k, d_in, vp(d_in.value + b_act) if messages is not None else None, d_out,
-                                              vp(d_out.value + b_rew + b_pk), vp(d_out.value + b_rew) if record_obs else None)
+        with Staged(self._dev, ins + [(b_rew + b_pk + b_done, 16)]) as st:
+            d_out = st.ptr(len(ins)).value
+            rc = self.lib.cc4_run_plan_device(self._h, k, st.ptr(0), st.ptr(1) if messages is not None else None, as_ptr(d_out),
+                                              as_ptr(d_out + b_rew + b_pk), as_ptr(d_out + b_rew) if record_obs else None)
             rc2 = self.lib.cc4_synchronize(self._h)
             if rc or rc2:
                 self._chk(rc or rc2, 'cc4_run_plan_device')
-            out = np.empty(b_rew + b_pk + b_done, np.uint8)           # [rewards | packed observations | dones]: one copy down
-            _hip_chk(hip.hipMemcpy(out.ctypes.data_as(vp), d_out, out.nbytes, 2), 'hipMemcpy')
-        finally:
-            hip.hipFree(d_in)
-            if d_out:
-                hip.hipFree(d_out)
+            out = st.down(len(ins), np.empty(b_rew + b_pk + b_done, np.uint8))     # [rewards | packed observations | dones]: one copy down
         rewards = out[:b_rew].view(np.float32).reshape(k, n).copy()
         dones = out[b_rew + b_pk:].reshape(k, n).astype(bool)
         info = {}
@@ -772,7 +776,7 @@ _hip_lib = None
 
 def _hip():
     """The HIP runtime libcc4.so is linked against, reached through libcc4.so's own handle (a symbol lookup there searches its dependencies: no
-    second search of the loader's path), for the host-array surface's staging buffers (run_plan, state_features)."""
+    second search of the loader's path), for the host-array surface's staging block (Staged)."""
     global _hip_lib
     if _hip_lib is None:
         lib = ctypes.CDLL(L.LIB_PATH)

@@ -58,27 +58,17 @@ def without_assignment(rows):
 def run_plan_packed(env, plan):
     """cc4_run_plan_device on a CC4VecEnv with the recorded observations left packed (2 bits per value): (rewards [k, n] float32, dones [k, n] uint8,
     packed [k, n, 148] uint8).  CC4VecEnv.run_plan unpacks them to 578 bytes per row, which at 6656 episodes x 100 steps is most of a test's time."""
-    from cage_challenge_4_amd.vec_env import _hip, _hip_chk
-    plan = np.ascontiguousarray(plan, dtype=np.int32)
+    from cage_challenge_4_amd.vec_env import Staged, as_actions
+    plan = as_actions(plan, env.num_envs, 0)
     k, n = plan.shape[:2]
-    assert plan.shape == (k, n, L.NUM_BLUE) and n == env.num_envs
-    hip, vp = _hip(), ctypes.c_void_p
+    vp = ctypes.c_void_p
     b_rew, b_pk, b_done = 4 * k * n, L.OBS_PACKED_BYTES * k * n, k * n
-    _hip_chk(hip.hipSetDevice(env._dev), 'hipSetDevice')
-    d_in, d_out = vp(), vp()
-    _hip_chk(hip.hipMalloc(ctypes.byref(d_in), plan.nbytes), 'hipMalloc')
-    try:
-        _hip_chk(hip.hipMalloc(ctypes.byref(d_out), b_rew + b_pk + b_done), 'hipMalloc')
-        _hip_chk(hip.hipMemcpy(d_in, plan.ctypes.data_as(vp), plan.nbytes, 1), 'hipMemcpy')
-        rc = env.lib.cc4_run_plan_device(env._h, k, d_in, None, d_out, vp(d_out.value + b_rew + b_pk), vp(d_out.value + b_rew))
+    with Staged(env._dev, [plan, (b_rew + b_pk + b_done, 16)]) as st:
+        d_out = st.ptr(1).value
+        rc = env.lib.cc4_run_plan_device(env._h, k, st.ptr(0), None, vp(d_out), vp(d_out + b_rew + b_pk), vp(d_out + b_rew))
         rc2 = env.lib.cc4_synchronize(env._h)
         env._chk(rc or rc2, 'cc4_run_plan_device')
-        out = np.empty(b_rew + b_pk + b_done, np.uint8)
-        _hip_chk(hip.hipMemcpy(out.ctypes.data_as(vp), d_out, out.nbytes, 2), 'hipMemcpy')
-    finally:
-        hip.hipFree(d_in)
-        if d_out:
-            hip.hipFree(d_out)
+        out = st.down(1, np.empty(b_rew + b_pk + b_done, np.uint8))
     return (out[:b_rew].view(np.float32).reshape(k, n), out[b_rew + b_pk:].reshape(k, n), out[b_rew:b_rew + b_pk].reshape(k, n, L.OBS_PACKED_BYTES))
 
 
