@@ -26,6 +26,7 @@ BLUE_EDGES_MAX, BLUE_EDGES_COLUMNS, BLUE_EDGES_WORDS = 160, 8, 8       # CC4_BLU
 REWARD_SUBNETS, REWARD_COLS, REWARD_WORDS = 9, 4, 16                # CC4_REWARD_*: the pieces of the step reward as tensors (reward_terms.py)
 SAMPLE_GREEDY, SAMPLE_BUSY, SAMPLE_TAG = 1, 2, 0x5A3B                    # CC4_SAMPLE_*: blue actions sampled from policy logits (action_sampling.py)
 LOGP_REFUSED = 1                                                         # CC4_LOGP_REFUSED: log-probabilities of stored blue actions (action_logp.py)
+GAE_SKIP_AFTER_DONE, GAE_BOOTSTRAP_DONE, GAE_MAX_HEADS = 1, 2, 8                   # CC4_GAE_*: advantages and returns of a stored rollout (advantages.py)
 POLICY_KEEP, POLICY_DEFAULT = -1, -2                   # CC4_POLICY_*: per-episode opponent classes (cc4_set_policies)
 OBS_LEN = (92, 92, 92, 92, 210)
 ACT_LEN = (82, 82, 82, 82, 242)
@@ -111,6 +112,11 @@ SIGNATURES = {
     'cc4_logp_actions_grad_device': (ctypes.c_int, [_P, _P, ctypes.c_int32, _P, _P, ctypes.c_int32, ctypes.c_float, _P, _P, _P]),
     'cc4_logp_actions_host': (ctypes.c_int, [_P, _P, _P, ctypes.c_float, _P]),
     'cc4_logp_actions_grad_host': (ctypes.c_int, [_P, _P, _P, ctypes.c_float, _P, _P, _P]),
+    'cc4_gae_device': (ctypes.c_int, [_P, _P, ctypes.c_int32, _P, ctypes.c_int32, _P, _P, _P, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,
+                                      ctypes.c_float, ctypes.c_int32, _P, _P, _P]),
+    'cc4_gae_host': (ctypes.c_int, [_P, ctypes.c_int32, _P, _P, _P, _P, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_float,
+                                    ctypes.c_int32, _P, _P, _P]),
+    'cc4_gae_rows': (ctypes.c_int32, []),
     'cc4_set_policies_device': (ctypes.c_int, [_P, _P, _P, _P]),
     'cc4_set_policies': (ctypes.c_int, [_P, _P, _P, _P]),
     'cc4_policies_device': (ctypes.c_int, [_P, _P, _P]),

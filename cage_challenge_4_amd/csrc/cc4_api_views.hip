@@ -3,7 +3,8 @@
 // the kernels: cc4_k_feat.hip, cc4_k_red.hip, cc4_k_blue.hip, cc4_k_edges.hip, cc4_k_reward.hip, cc4_k_sample.hip; the definitions: cc4_features.h,
 // cc4_red_view.h, cc4_blue_view.h, cc4_blue_edges.h, cc4_reward_terms.h, cc4_sample.h).  Every view has a device entry point and the same definition on the host from one row; the call shape of the device entry
 // points is stated at ViewSrc (cc4_args.h) and implemented once here: view_check, view_launch.
-// Beside the views, the learner's half of the sampling, which reads no row at all: log-probabilities of stored actions with gradients (cc4_k_logp.hip; cc4_logp.h).
+// Beside the views, the learner's half of the sampling, which reads no row at all: log-probabilities of stored actions with gradients (cc4_k_logp.hip; cc4_logp.h),
+// and the advantages and returns of a stored rollout (cc4_k_gae.hip; cc4_gae.h).
 #include "cc4_host.h"
 #include "cc4_features.h"
 #include "cc4_red_view.h"
@@ -12,6 +13,7 @@
 #include "cc4_reward_terms.h"
 #include "cc4_sample.h"
 #include "cc4_logp.h"
+#include "cc4_gae.h"
 
 // ---- the device entry points.  One launch on the main stream behind the group streams, no host synchronisation; a view only reads rows -- as the
 // last step left them -- so the next step launches need no ordering behind it beyond the main stream's own.
@@ -121,6 +123,29 @@ int cc4_logp_actions_grad_host(const float* logits, const uint8_t* mask, const i
   logp_grad_from_row(logits, mask, actions, 1.0f / temperature, aux, g, grad);
   return 0;
 }
+
+// ---- advantages, returns and loss weights of a stored rollout (cc4_gae.h; cc4_k_gae.hip).  As the log-probabilities: a pure function of the
+// caller's tensors, no handle, no prologue, one launch on the caller's stream.  -2 with nothing enqueued: a null required pointer or gae_bad;
+// T == 0 or N == 0 a no-op; -1: the launch failed.
+int cc4_gae_device(void* stream, const float* d_rewards, int32_t reward_heads, const void* d_values, int32_t dtype, const void* d_last, const uint8_t* d_dones,
+                   const uint8_t* d_done0, const int32_t* d_actions, int32_t T, int32_t N, int32_t A, float gamma, float lambda, int32_t flags, float* d_adv,
+                   float* d_ret, uint8_t* d_weight) {
+  if (!d_rewards || !d_values || !d_last || !d_dones || !d_adv || !d_ret || dtype < 1 || dtype > 3 || gae_bad(reward_heads, T, N, A, gamma, lambda, flags))
+    return -2;
+  if (T == 0 || N == 0) return 0;
+  const int64_t cols = (int64_t)N * A, per_block = (int64_t)GAE_WAVES * WAVE;
+  const GaeArgs a{d_rewards, d_values, d_last, d_dones, d_done0, d_actions, d_adv, d_ret, d_weight, reward_heads, dtype, T, N, A, flags, gamma, lambda};
+  hipLaunchKernelGGL(k_gae, dim3((unsigned)((cols + per_block - 1) / per_block)), dim3(GAE_WAVES * WAVE), 0, static_cast<hipStream_t>(stream), a);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+// ... and on the host, float32 values; no device
+int cc4_gae_host(const float* rewards, int32_t reward_heads, const float* values, const float* last, const uint8_t* dones, const uint8_t* done0,
+                 const int32_t* actions, int32_t T, int32_t N, int32_t A, float gamma, float lambda, int32_t flags, float* adv, float* ret, uint8_t* weight) {
+  if (!rewards || !values || !last || !dones || !adv || !ret || gae_bad(reward_heads, T, N, A, gamma, lambda, flags)) return -2;
+  gae_columns(rewards, reward_heads, values, last, dones, done0, actions, T, N, A, gamma, lambda, flags, adv, ret, weight);
+  return 0;
+}
+int32_t cc4_gae_rows(void) { return GAE_ROWS; }
 
 // The switch of the reward record: the handle behaves as after a cc4_step_red_device whose records were all "the scripted class acts" -- d_ext filled with
 // none-records, ext_seen set -- so launch_step and the `plain` tests of cc4_api_run.hip select the full builds and pass a.ext with no condition of their own.

@@ -16,6 +16,7 @@
 //               slots and on skipped or refused agents included, so the caller's buffer needs no initialisation.
 #include <hip/hip_runtime.h>
 #include "cc4_logp.h"
+#include "cc4_elem.h"
 #include "cc4_kernel_decls.h"
 
 static_assert(LP_REFUSED == CC4_LOGP_REFUSED && SA_SLOTS == CC4_MASK_PER_ENV && NBLUE == CC4_NUM_BLUE, "include/cc4.h states the bit and the shapes");
@@ -24,23 +25,6 @@ static_assert(LP_ROUNDS == 9 && NBLUE * LP_AUX <= WAVE, "the lanes of step 1 and
 // no slot of agent b among the 64 of round j
 __host__ __device__ constexpr bool lp_round_misses(int j, int b) { return WAVE * j + WAVE - 1 < sa_off(b) || WAVE * j >= sa_off(b) + sa_len(b); }
 
-// the element types of the dtype codes of cc4_policy_outputs (1 float16, 2 bfloat16, 3 float32)
-template <int DT> struct LpElem { using type = uint16_t; };
-template <> struct LpElem<3> { using type = float; };
-template <int DT> __device__ __forceinline__ float lp_to_float(typename LpElem<DT>::type v) {
-  if constexpr (DT == 3) return v;
-  else if constexpr (DT == 2) return __uint_as_float((uint32_t)v << 16);
-  else { _Float16 h; __builtin_memcpy(&h, &v, 2); return (float)h; }
-}
-// ... and back, rounded to nearest even (a NaN stays a quiet NaN)
-template <int DT> __device__ __forceinline__ typename LpElem<DT>::type lp_from_float(float v) {
-  if constexpr (DT == 3) return v;
-  else if constexpr (DT == 2) {
-    const uint32_t u = __float_as_uint(v);
-    if (v != v) return (uint16_t)((u >> 16) | 0x0040u);
-    return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
-  } else { const _Float16 h = (_Float16)v; uint16_t r; __builtin_memcpy(&r, &h, 2); return r; }
-}
 __device__ __forceinline__ float lp_wave_max(float v) {
 #pragma unroll
   for (int d = 1; d < WAVE; d <<= 1) { const float o = __shfl_xor(v, d); v = o > v ? o : v; }

@@ -2,6 +2,7 @@
 // template, explicitly instantiated -- in the translation unit cc4_kernels.h names.
 #pragma once
 #include "cc4_args.h"
+#include "cc4_gae.h"
 
 constexpr int PT = 4 * WAVE;       // threads per episode block of the four-wave kernels (cc4_k_philox4.hip: PW = 4)
 // per-step kernels
@@ -74,6 +75,18 @@ __global__ void k_logp_fwd(const void* __restrict__ logits, int dtype, const uin
                            float inv_t, float* __restrict__ aux, int32_t* __restrict__ fault);
 __global__ void k_logp_bwd(const void* __restrict__ logits, int dtype, const uint8_t* __restrict__ mask, const int32_t* __restrict__ actions, int n,
                            float inv_t, const float* __restrict__ aux, const float* __restrict__ g, void* __restrict__ grad);
+// advantages and returns of a stored rollout (cc4_k_gae.hip): one lane per column of the caller's tensors, GAE_WAVES wavefronts per workgroup,
+// the rows in blocks of GAE_ROWS.  Measured (profiles/r31_gae.txt): 16 rows ahead beat 8 and 4 at T >= 128 (the kernel waits on memory, one wave
+// per SIMD), 24 and 32 spill scalar registers and lose at T = 20; 1, 2 and 4 waves per workgroup are within 2 % of each other at 8192 episodes,
+// one is the fastest at 1024; make EXTRA="-DCC4_GAE_WAVES=k -DCC4_GAE_ROWS=r" builds another
+#ifndef CC4_GAE_WAVES
+#define CC4_GAE_WAVES 1
+#endif
+#ifndef CC4_GAE_ROWS
+#define CC4_GAE_ROWS 16
+#endif
+constexpr int GAE_WAVES = CC4_GAE_WAVES, GAE_ROWS = CC4_GAE_ROWS;
+__global__ void k_gae(GaeArgs a);
 // per-episode opponent classes (cc4_k_misc.hip): one lane per episode
 __global__ void k_set_policies(EnvState* st, const int8_t* __restrict__ red, const int8_t* __restrict__ green, const int8_t* __restrict__ blue, int n, uint32_t* fault);
 __global__ void k_get_policies(const EnvState* __restrict__ st, int8_t* __restrict__ live, int8_t* __restrict__ assigned, int n);

@@ -21,6 +21,7 @@
 //   cc4_k_sample.hip   policy logits to valid blue actions: k_sample_actions (cc4_sample_actions_device); only cc4_sample.h
 //   cc4_k_logp.hip     stored blue actions under new logits, with gradients: k_logp_fwd, k_logp_bwd (cc4_logp_actions_device, cc4_logp_actions_grad_device);
 //                      only cc4_logp.h, no rows and no handle
+//   cc4_k_gae.hip      advantages and returns of a stored rollout: k_gae (cc4_gae_device); only cc4_gae.h, no rows and no handle
 // cc4_kernel_decls.h declares them for the host side.  No MFMA anywhere: the path is integer / indexing.
 #pragma once
 #include "cc4_args.h"

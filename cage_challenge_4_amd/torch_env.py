@@ -143,6 +143,9 @@ class CC4TorchVecEnv:
                                                   step() takes in one launch: masked, busy agents -1, logp and entropy of the draw
     evaluate_actions(logits, mask, actions, temperature=1.0) -> (logp [..., 5], entropy [..., 5]) float32   the update's half: stored actions
                                                   under new logits, with the gradient back to the logits (cage_challenge_4_amd.action_logp)
+    advantages(rewards, values, last_value, dones, *, gamma, lam, done0=None, actions=None, bootstrap=False, out=None)
+                                                  -> (adv, ret, weight) in the shape of values   GAE of a stored rollout in one launch, in this
+                                                  env's autoreset layout: skip rows and -1 actions get weight 0 (cage_challenge_4_amd.advantages)
 
     Mixed opponents in one batch (include/cc4.h cc4_set_policies_device, cc4_reset_device):
     set_opponents(red=None, green=None, blue=None)   integer tensors [N] on the device: the classes each episode regenerates into from its next
@@ -163,6 +166,7 @@ class CC4TorchVecEnv:
         self.obs_dtype = obs_dtype
         self._dt = _OBS_DTYPES[obs_dtype]
         self.device = torch.device('cuda', int(kw.get('device_id', 0)))
+        self.autoreset = bool(kw.get('autoreset', False))
         with torch.cuda.device(self.device):
             z = dict(device=self.device)
             self.obs = torch.zeros((n, L.OBS_PER_ENV), dtype=obs_dtype, **z)
@@ -387,6 +391,13 @@ class CC4TorchVecEnv:
         update's half of sample_actions().  A pure function of its tensors (the env is not read); action_logp.check_errors() reports refusals."""
         from .action_logp import evaluate_actions
         return evaluate_actions(logits, mask, actions, temperature)
+
+    def advantages(self, rewards, values, last_value, dones, *, gamma, lam, done0=None, actions=None, bootstrap=False, out=None):
+        """advantages.gae with autoreset taken from this env's configuration: (adv, ret, weight) of the rows a rollout stored -- done0 is
+        env.done.clone() taken before the rollout's first call.  A pure function of its tensors (the env's state is not read)."""
+        from .advantages import gae
+        return gae(rewards, values, last_value, dones, gamma=gamma, lam=lam, done0=done0, actions=actions, autoreset=self.autoreset,
+                   bootstrap=bootstrap, out=out)
 
     def enable_event_log(self, on=True):
         """CC4VecEnv.enable_event_log (cc4_enable_event_log): record the HostEvents entries of every step, which fills the event columns of
