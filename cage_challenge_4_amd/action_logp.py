@@ -16,11 +16,12 @@ Importing this module imports neither torch nor the library; evaluate_actions() 
 import ctypes
 import numpy as np
 from . import _lib as L
+from . import _tensors as TS
 from .action_sampling import NUM_BLUE, SEGMENTS, SLOTS, check_temperature
 
 REFUSED = L.LOGP_REFUSED
 AUX = {'logp': 0, 'entropy': 1, 'm': 2, 'logS': 3}
-DTYPE_CODES = {'float16': 1, 'bfloat16': 2, 'float32': 3}      # the codes of cc4_policy_outputs
+DTYPE_CODES = TS.DTYPE_CODES      # the codes of cc4_policy_outputs
 launches = {'fwd': 0, 'bwd': 0}          # kernels this module has enqueued (what a caller's test counts)
 
 
@@ -142,22 +143,15 @@ def _function():
         return _state['fn']
     import torch
     from torch.autograd.function import once_differentiable
-    vp = ctypes.c_void_p
-    codes = {getattr(torch, k): c for k, c in DTYPE_CODES.items()}
+    codes, p = TS.torch_codes(torch), TS.dptr
 
     class _EvaluateActions(torch.autograd.Function):
         @staticmethod
         def forward(ctx, logits, mask, actions, temperature):
-            lib, dev = L.load(), logits.device
-            n = logits.numel() // SLOTS
+            dev, n = logits.device, logits.numel() // SLOTS
             aux = torch.empty((n, NUM_BLUE, 4), dtype=torch.float32, device=dev)
-            fault = _fault_word(torch, dev)
-            with torch.cuda.device(dev):
-                rc = lib.cc4_logp_actions_device(vp(torch.cuda.current_stream(dev).cuda_stream), vp(logits.data_ptr()), codes[logits.dtype],
-                                                 vp(mask.data_ptr()), vp(actions.data_ptr()), n, temperature, vp(aux.data_ptr()), vp(fault.data_ptr()))
-            if rc != 0:
-                raise L.CC4Error(f'cc4_logp_actions_device failed (rc={rc})')
-            launches['fwd'] += 1 if n else 0
+            TS.pure_call('cc4_logp_actions_device', dev, p(logits), codes[logits.dtype], p(mask), p(actions), n, temperature, p(aux),
+                         p(_fault_word(torch, dev)), count=(launches, 'fwd') if n else None)
             ctx.save_for_backward(logits, mask, actions, aux)
             ctx.temperature = temperature
             lead = tuple(logits.shape[:-1])
@@ -167,17 +161,12 @@ def _function():
         @once_differentiable
         def backward(ctx, g_logp, g_entropy):
             logits, mask, actions, aux = ctx.saved_tensors
-            lib, dev = L.load(), logits.device
             n = logits.numel() // SLOTS
             g = torch.stack((g_logp, g_entropy), dim=-1).to(torch.float32).reshape(n, NUM_BLUE, 2).contiguous()
             grad = torch.empty_like(logits)
-            with torch.cuda.device(dev):       # (the stream autograd made current for this node: the forward's)
-                rc = lib.cc4_logp_actions_grad_device(vp(torch.cuda.current_stream(dev).cuda_stream), vp(logits.data_ptr()), codes[logits.dtype],
-                                                      vp(mask.data_ptr()), vp(actions.data_ptr()), n, ctx.temperature, vp(aux.data_ptr()),
-                                                      vp(g.data_ptr()), vp(grad.data_ptr()))
-            if rc != 0:
-                raise L.CC4Error(f'cc4_logp_actions_grad_device failed (rc={rc})')
-            launches['bwd'] += 1 if n else 0
+            # (the stream autograd made current for this node: the forward's)
+            TS.pure_call('cc4_logp_actions_grad_device', logits.device, p(logits), codes[logits.dtype], p(mask), p(actions), n, ctx.temperature,
+                         p(aux), p(g), p(grad), count=(launches, 'bwd') if n else None)
             return grad, None, None, None
 
     _state['fn'] = _EvaluateActions
@@ -194,16 +183,10 @@ def evaluate_actions(logits, mask, actions, temperature=1.0):
     check_errors() raises for it.  Wrong shapes, dtypes and devices raise ValueError before anything is enqueued."""
     import torch
     temperature = check_temperature(temperature)
-    if (not torch.is_tensor(logits) or logits.dim() < 1 or logits.shape[-1] != SLOTS or logits.dtype not in [getattr(torch, k) for k in DTYPE_CODES]
-            or not logits.is_cuda or not logits.is_contiguous()):
-        raise ValueError(f'logits must be a contiguous float16, bfloat16 or float32 CUDA tensor [..., {SLOTS}]')
-    lead = tuple(logits.shape[:-1])
-    if (not torch.is_tensor(mask) or tuple(mask.shape) != lead + (SLOTS,) or mask.dtype not in (torch.bool, torch.uint8)
-            or mask.device != logits.device or not mask.is_contiguous()):
-        raise ValueError(f'mask must be a contiguous bool or uint8 tensor {list(lead) + [SLOTS]} on {logits.device}')
-    if (not torch.is_tensor(actions) or tuple(actions.shape) != lead + (NUM_BLUE,) or actions.dtype != torch.int32
-            or actions.device != logits.device or not actions.is_contiguous()):
-        raise ValueError(f'actions must be a contiguous int32 tensor {list(lead) + [NUM_BLUE]} on {logits.device}')
+    lead = tuple(logits.shape[:-1]) if torch.is_tensor(logits) else ()
+    TS.check_tensor(torch, 'logits', logits, shape=lead + (SLOTS,), dtypes=tuple(TS.torch_codes(torch)), device='cuda')
+    TS.check_tensor(torch, 'mask', mask, shape=lead + (SLOTS,), dtypes=(torch.bool, torch.uint8), device=logits.device)
+    TS.check_tensor(torch, 'actions', actions, shape=lead + (NUM_BLUE,), dtypes=(torch.int32,), device=logits.device)
     return _function().apply(logits, mask, actions, temperature)
 
 

@@ -18,12 +18,12 @@ Three ways to the same numbers:
   reference(...)                                                a float64 NumPy restatement written another way: episode segments, explicit sums
 
 Importing this module imports neither torch nor the library; gae() imports torch when it is called."""
-import ctypes
 import numpy as np
 from . import _lib as L
+from . import _tensors as TS
 
 SKIP_AFTER_DONE, BOOTSTRAP_DONE, MAX_HEADS = L.GAE_SKIP_AFTER_DONE, L.GAE_BOOTSTRAP_DONE, L.GAE_MAX_HEADS
-DTYPE_CODES = {'float16': 1, 'bfloat16': 2, 'float32': 3}      # the codes of cc4_policy_outputs
+DTYPE_CODES = TS.DTYPE_CODES      # the codes of cc4_policy_outputs
 launches = {'gae': 0}          # kernels this module has enqueued (what a caller's test counts)
 
 
@@ -135,8 +135,7 @@ def from_arrays(rewards, values, last_value, dones, *, gamma, lam, done0=None, a
     done0 = None if done0 is None else np.ascontiguousarray(done0).view(np.uint8)
     actions = None if actions is None else np.ascontiguousarray(actions.clip(-2 ** 31, 2 ** 31 - 1), np.int32)
     adv, ret, weight = np.zeros(vl.shape, np.float32), np.zeros(vl.shape, np.float32), np.zeros(vl.shape, np.uint8)
-    vp = ctypes.c_void_p
-    p = lambda x: None if x is None else x.ctypes.data_as(vp)      # noqa: E731
+    from .vec_env import as_ptr as p
     rc = lib.cc4_gae_host(p(rw), heads, p(vl), p(lv), p(dn), p(done0), p(actions), T, N, A, gamma, lam, flags, p(adv), p(ret), p(weight))
     if rc != 0:
         raise L.CC4Error(f'cc4_gae_host failed (rc={rc})')
@@ -148,31 +147,23 @@ def _check_tensors(torch, rewards, values, last_value, dones, done0, actions, ou
     given = [('rewards', rewards), ('values', values), ('last_value', last_value), ('dones', dones)]
     given += [(k, x) for k, x in (('done0', done0), ('actions', actions)) if x is not None]
     for name, x in given:
-        if not torch.is_tensor(x):
-            raise ValueError(f'{name} must be a torch tensor, got {type(x).__name__}')
+        TS.check_tensor(torch, name, x, contiguous=False)
     T, N, A, heads = _shapes(lambda x: tuple(x.shape), rewards, values, last_value, dones, done0, actions)
-    codes = {getattr(torch, k): c for k, c in DTYPE_CODES.items()}
-    if values.dtype not in codes:
-        raise ValueError(f'values must be float16, bfloat16 or float32, got {values.dtype}')
+    codes = TS.torch_codes(torch)
+    TS.check_tensor(torch, 'values', values, dtypes=tuple(codes), contiguous=False)
     if last_value.dtype != values.dtype:
         raise ValueError(f'last_value must have the dtype of values ({values.dtype}), got {last_value.dtype}')
-    if rewards.dtype != torch.float32:
-        raise ValueError(f'rewards must be float32, got {rewards.dtype}')
-    for name, x in (('dones', dones), ('done0', done0)):
-        if x is not None and x.dtype not in (torch.bool, torch.uint8):
-            raise ValueError(f'{name} must be bool or uint8, got {x.dtype}')
-    if actions is not None and actions.dtype != torch.int32:
-        raise ValueError(f'actions must be int32, got {actions.dtype}')
+    for name, x, dtypes in (('rewards', rewards, (torch.float32,)), ('dones', dones, (torch.bool, torch.uint8)), ('done0', done0, (torch.bool, torch.uint8)),
+                            ('actions', actions, (torch.int32,))):
+        if x is not None:
+            TS.check_tensor(torch, name, x, dtypes=dtypes, contiguous=False)
     if out is not None:
         if not isinstance(out, (tuple, list)) or len(out) != 3 or not all(torch.is_tensor(o) for o in out):
             raise ValueError('out must be the (adv, ret, weight) triple an earlier call returned')
-        for name, o, dt in zip(('adv', 'ret', 'weight'), out, (torch.float32, torch.float32, torch.bool)):
-            if o.shape != values.shape or o.dtype != dt:
-                raise ValueError(f'out: {name} must be {dt} {list(values.shape)}, got {o.dtype} {list(o.shape)}')
-            given.append((f'out: {name}', o))
+        for name, o, dt in zip(('out: adv', 'out: ret', 'out: weight'), out, (torch.float32, torch.float32, torch.bool)):
+            given.append((name, TS.check_tensor(torch, name, o, shape=tuple(values.shape), dtypes=(dt,), contiguous=False)))
     for name, x in given:
-        if not x.is_cuda or not x.is_contiguous():
-            raise ValueError(f'{name} must be a contiguous CUDA tensor')
+        TS.check_tensor(torch, name, x, device='cuda')
     for name, x in given:
         if x.device != values.device:
             raise ValueError(f'{name} must be on the device of values ({values.device}), got {x.device}')
@@ -194,19 +185,14 @@ def gae(rewards, values, last_value, dones, *, gamma, lam, done0=None, actions=N
     import torch
     gamma, lam, flags = check_params(gamma, lam, autoreset, bootstrap)
     T, N, A, heads, code = _check_tensors(torch, rewards, values, last_value, dones, done0, actions, out)
-    lib, dev = L.load(), values.device
+    dev = values.device
     if out is None:
         out = (torch.empty(values.shape, dtype=torch.float32, device=dev), torch.empty(values.shape, dtype=torch.float32, device=dev),
                torch.empty(values.shape, dtype=torch.bool, device=dev))
     adv, ret, weight = out
     if T == 0 or N == 0:          # nothing to do (and an empty tensor has no address to pass)
         return adv, ret, weight
-    vp = ctypes.c_void_p
-    p = lambda x: None if x is None else vp(x.data_ptr())      # noqa: E731
-    with torch.cuda.device(dev):
-        rc = lib.cc4_gae_device(vp(torch.cuda.current_stream(dev).cuda_stream), p(rewards), heads, p(values), code, p(last_value), p(dones), p(done0),
-                                p(actions), T, N, A, gamma, lam, flags, p(adv), p(ret), p(weight))
-    if rc != 0:
-        raise L.CC4Error(f'cc4_gae_device failed (rc={rc})')
-    launches['gae'] += 1
+    p = TS.dptr
+    TS.pure_call('cc4_gae_device', dev, p(rewards), heads, p(values), code, p(last_value), p(dones), p(done0), p(actions), T, N, A, gamma, lam, flags,
+                 p(adv), p(ret), p(weight), count=(launches, 'gae'))
     return adv, ret, weight

@@ -3,8 +3,7 @@
 // the kernels: cc4_k_feat.hip, cc4_k_red.hip, cc4_k_blue.hip, cc4_k_edges.hip, cc4_k_reward.hip, cc4_k_sample.hip; the definitions: cc4_features.h,
 // cc4_red_view.h, cc4_blue_view.h, cc4_blue_edges.h, cc4_reward_terms.h, cc4_sample.h).  Every view has a device entry point and the same definition on the host from one row; the call shape of the device entry
 // points is stated at ViewSrc (cc4_args.h) and implemented once here: view_check, view_launch.
-// Beside the views, the learner's half of the sampling, which reads no row at all: log-probabilities of stored actions with gradients (cc4_k_logp.hip; cc4_logp.h),
-// and the advantages and returns of a stored rollout (cc4_k_gae.hip; cc4_gae.h).
+// (The learner's pure functions, which read no row at all and take no handle: cc4_api_learn.hip.)
 #include "cc4_host.h"
 #include "cc4_features.h"
 #include "cc4_red_view.h"
@@ -12,8 +11,6 @@
 #include "cc4_blue_edges.h"
 #include "cc4_reward_terms.h"
 #include "cc4_sample.h"
-#include "cc4_logp.h"
-#include "cc4_gae.h"
 
 // ---- the device entry points.  One launch on the main stream behind the group streams, no host synchronisation; a view only reads rows -- as the
 // last step left them -- so the next step launches need no ordering behind it beyond the main stream's own.
@@ -74,8 +71,8 @@ int cc4_reward_terms_device(cc4_handle* h, const void* d_bank, int32_t capacity,
 }
 // of the hot rows exists and the agents' busy bytes; beside the rows one input, the logits.  The refusals of its own, in their order:
 static const char* sample_bad(int32_t dtype, const void* logits, float temperature, int32_t flags) {
-  if (dtype < 1 || dtype > 3) return "logits_dtype must be 1 (float16), 2 (bfloat16) or 3 (float32)";
-  if (!(temperature > 0.0f) || !std::isfinite(temperature)) return "the temperature must be finite and positive";
+  if (!dtype_ok(dtype)) return "logits_dtype must be 1 (float16), 2 (bfloat16) or 3 (float32)";
+  if (!temperature_ok(temperature)) return "the temperature must be finite and positive";
   if (flags & ~(int32_t)SA_FLAGS) return "unknown flag bits (CC4_SAMPLE_GREEDY | CC4_SAMPLE_BUSY)";
   if (reinterpret_cast<uintptr_t>(logits) % 4) return "the logits must be 4-byte aligned";
   return nullptr;
@@ -87,65 +84,6 @@ int cc4_sample_actions_device(cc4_handle* h, const void* d_bank, int32_t capacit
   return rc == VIEW_GO ? view_launch(h, "cc4_sample_actions_device", k_sample_actions, d_bank, capacity, d_ids, n, d_logits, (int)logits_dtype, seed0, t, 1.0f / temperature, (int)flags,
                                      d_actions, d_stats) : rc;
 }
-
-// ---- the learner's half of the sampling: log-probability and entropy of stored actions under new logits, and their derivative (cc4_logp.h;
-// cc4_k_logp.hip).  Pure functions of the caller's tensors: no handle and so no entry prologue, no stream of the library's -- one launch on the
-// caller's stream on the device current to the calling thread (autograd's backward thread is as good as any).  -2 with nothing enqueued: a null
-// pointer, n < 0, a dtype outside 1..3, a temperature that is not finite and positive; n == 0 a no-op; -1: the launch failed.
-static bool logp_bad(int32_t dtype, int32_t n, float temperature) {
-  return dtype < 1 || dtype > 3 || n < 0 || !(temperature > 0.0f) || !std::isfinite(temperature);
-}
-static int logp_blocks(int32_t n) { return (int)(((int64_t)n + LP_WAVES - 1) / LP_WAVES); }
-int cc4_logp_actions_device(void* stream, const void* d_logits, int32_t dtype, const uint8_t* d_mask, const int32_t* d_actions, int32_t n, float temperature,
-                            float* d_aux, int32_t* d_fault) {
-  if (!d_logits || !d_mask || !d_actions || !d_aux || !d_fault || logp_bad(dtype, n, temperature)) return -2;
-  if (n == 0) return 0;
-  hipLaunchKernelGGL(k_logp_fwd, dim3(logp_blocks(n)), dim3(LP_WAVES * WAVE), 0, static_cast<hipStream_t>(stream), d_logits, (int)dtype, d_mask, d_actions,
-                     (int)n, 1.0f / temperature, d_aux, d_fault);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-int cc4_logp_actions_grad_device(void* stream, const void* d_logits, int32_t dtype, const uint8_t* d_mask, const int32_t* d_actions, int32_t n,
-                                 float temperature, const float* d_aux, const float* d_g, void* d_grad) {
-  if (!d_logits || !d_mask || !d_actions || !d_aux || !d_g || !d_grad || logp_bad(dtype, n, temperature)) return -2;
-  if (n == 0) return 0;
-  hipLaunchKernelGGL(k_logp_bwd, dim3(logp_blocks(n)), dim3(LP_WAVES * WAVE), 0, static_cast<hipStream_t>(stream), d_logits, (int)dtype, d_mask, d_actions,
-                     (int)n, 1.0f / temperature, d_aux, d_g, d_grad);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-// ... and on the host, one row of float32 logits: the number of refused agents (0 .. 5), or -2; the derivative 0 or -2.  No device.
-int cc4_logp_actions_host(const float* logits, const uint8_t* mask, const int32_t* actions, float temperature, float* aux) {
-  if (!logits || !mask || !actions || !aux || logp_bad(3, 0, temperature)) return -2;
-  return logp_from_row(logits, mask, actions, 1.0f / temperature, aux);
-}
-int cc4_logp_actions_grad_host(const float* logits, const uint8_t* mask, const int32_t* actions, float temperature, const float* aux, const float* g,
-                               float* grad) {
-  if (!logits || !mask || !actions || !aux || !g || !grad || logp_bad(3, 0, temperature)) return -2;
-  logp_grad_from_row(logits, mask, actions, 1.0f / temperature, aux, g, grad);
-  return 0;
-}
-
-// ---- advantages, returns and loss weights of a stored rollout (cc4_gae.h; cc4_k_gae.hip).  As the log-probabilities: a pure function of the
-// caller's tensors, no handle, no prologue, one launch on the caller's stream.  -2 with nothing enqueued: a null required pointer or gae_bad;
-// T == 0 or N == 0 a no-op; -1: the launch failed.
-int cc4_gae_device(void* stream, const float* d_rewards, int32_t reward_heads, const void* d_values, int32_t dtype, const void* d_last, const uint8_t* d_dones,
-                   const uint8_t* d_done0, const int32_t* d_actions, int32_t T, int32_t N, int32_t A, float gamma, float lambda, int32_t flags, float* d_adv,
-                   float* d_ret, uint8_t* d_weight) {
-  if (!d_rewards || !d_values || !d_last || !d_dones || !d_adv || !d_ret || dtype < 1 || dtype > 3 || gae_bad(reward_heads, T, N, A, gamma, lambda, flags))
-    return -2;
-  if (T == 0 || N == 0) return 0;
-  const int64_t cols = (int64_t)N * A, per_block = (int64_t)GAE_WAVES * WAVE;
-  const GaeArgs a{d_rewards, d_values, d_last, d_dones, d_done0, d_actions, d_adv, d_ret, d_weight, reward_heads, dtype, T, N, A, flags, gamma, lambda};
-  hipLaunchKernelGGL(k_gae, dim3((unsigned)((cols + per_block - 1) / per_block)), dim3(GAE_WAVES * WAVE), 0, static_cast<hipStream_t>(stream), a);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-// ... and on the host, float32 values; no device
-int cc4_gae_host(const float* rewards, int32_t reward_heads, const float* values, const float* last, const uint8_t* dones, const uint8_t* done0,
-                 const int32_t* actions, int32_t T, int32_t N, int32_t A, float gamma, float lambda, int32_t flags, float* adv, float* ret, uint8_t* weight) {
-  if (!rewards || !values || !last || !dones || !adv || !ret || gae_bad(reward_heads, T, N, A, gamma, lambda, flags)) return -2;
-  gae_columns(rewards, reward_heads, values, last, dones, done0, actions, T, N, A, gamma, lambda, flags, adv, ret, weight);
-  return 0;
-}
-int32_t cc4_gae_rows(void) { return GAE_ROWS; }
 
 // The switch of the reward record: the handle behaves as after a cc4_step_red_device whose records were all "the scripted class acts" -- d_ext filled with
 // none-records, ext_seen set -- so launch_step and the `plain` tests of cc4_api_run.hip select the full builds and pass a.ext with no condition of their own.

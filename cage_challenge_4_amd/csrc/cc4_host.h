@@ -8,6 +8,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <cmath>
 #include <string>
 #include <chrono>
 #include <vector>
@@ -209,6 +210,10 @@ struct cc4_handle {
       return -1;                                                                               \
     }                                                                                          \
   } while (0)
+
+// ---- what the entry points that take a tensor's dtype code or a sampling temperature accept (the views' sample_bad, cc4_api_learn.hip)
+inline bool dtype_ok(int32_t dtype) { return dtype >= 1 && dtype <= 3; }      // 1 float16, 2 bfloat16, 3 float32
+inline bool temperature_ok(float t) { return t > 0.0f && std::isfinite(t); }      // finite and positive (a NaN fails the compare)
 
 // ---- what a handle allocates (cc4_handle::own).  The field is registered before it is filled, so a failure anywhere later still finds it; a field
 // that holds something already gives that back first (the free-and-reallocate sites: d_run, d_xlog, d_timeline).  0 or -1 with h->err set.

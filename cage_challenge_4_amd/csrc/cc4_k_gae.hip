@@ -30,7 +30,7 @@ template <class E> struct GaeLane {
 // rows [hi - cnt, hi) of the lane's column, cnt <= GAE_ROWS (every index below is a constant after unrolling: the arrays are registers).  FIRST:
 // the block of the last rows, which reads `last` among its loads -- v_next of row T-1 -- instead of a load and a wait of its own in front of the loop
 template <int DT, bool ACT, bool FIRST>
-__device__ __forceinline__ void gae_block(const GaeArgs& a, GaeLane<typename LpElem<DT>::type>& l, const float last, const int hi, const int cnt,
+__device__ __forceinline__ void gae_block(const GaeArgs& a, GaeLane<typename Elem<DT>::type>& l, const float last, const int hi, const int cnt,
                                           const float gl, GaeCarry& carry) {
   float r[GAE_ROWS], v[GAE_ROWS];
   uint8_t d[GAE_ROWS + 1];         // d[k]: row hi-1-k; d[cnt]: the row in front of the block
@@ -38,7 +38,7 @@ __device__ __forceinline__ void gae_block(const GaeArgs& a, GaeLane<typename LpE
   // 1. the loads, with no branch on cnt among them: a row past the count reads the block's lowest row again and is neither used nor stored
 #pragma unroll
   for (int k = 0; k < GAE_ROWS; ++k) {
-    v[k] = lp_to_float<DT>(*l.v);
+    v[k] = elem_to_float<DT>(*l.v);
     r[k] = *l.r;
     d[k] = *l.d;
     act[k] = 0;
@@ -85,7 +85,7 @@ __device__ __forceinline__ void gae_block(const GaeArgs& a, GaeLane<typename LpE
 // ACT: actions are given (a build of its own: a branch among the loads would put a wait behind each)
 template <int DT, bool ACT>
 __device__ __forceinline__ void gae_column(const GaeArgs& a, const size_t c, const size_t NA) {
-  using E = typename LpElem<DT>::type;
+  using E = typename Elem<DT>::type;
   const uint32_t n = (uint32_t)c / (uint32_t)a.A;      // (N * A <= INT32_MAX: a 32-bit division)
   const bool per_head = a.reward_heads != 1;
   const size_t top = (size_t)(a.T - 1), rrow = per_head ? NA : (size_t)a.N;
@@ -93,7 +93,7 @@ __device__ __forceinline__ void gae_column(const GaeArgs& a, const size_t c, con
                ACT ? a.actions + top * NA + c : nullptr, a.adv + top * NA + c, a.ret + top * NA + c, a.weight ? a.weight + top * NA + c : nullptr,
                NA, rrow, (size_t)a.N, n};
   const float gl = a.gamma * a.lambda;
-  const float last = lp_to_float<DT>(static_cast<const E*>(a.last)[c]);
+  const float last = elem_to_float<DT>(static_cast<const E*>(a.last)[c]);
   GaeCarry carry{0.0f, 0.0f};
   const int tail = a.T % GAE_ROWS, first = tail ? tail : GAE_ROWS;      // (T >= 1)
   gae_block<DT, ACT, true>(a, l, last, a.T, first, gl, carry);

@@ -3,12 +3,12 @@
 // no hot row, no LDS.  One wavefront per row, LP_WAVES rows per workgroup (cc4_kernel_decls.h); a wave never meets another, so there is no barrier
 // and a workgroup's last waves may leave at once.
 //   k_logp_fwd  cc4_logp_actions_device.
-//                 1. lane l owns slots l + 64 j (j < 9) of the 570-slot row, as in k_sample_actions: every load instruction reads 64 consecutive
-//                    mask bytes or logits, so nothing beyond the element's alignment is assumed of a row; the scaled logits stay in registers;
+//                 1. lane l owns slots l + 64 j (j < 9) of the 570-slot row (the layout, the load and the reductions of step 2: cc4_row_wave.h,
+//                    shared with k_sample_actions); validity is the mask byte; the scaled logits stay in registers;
 //                 2. the five stored actions are wave-uniform (scalar loads); per agent that is not skipped: the maximum of the valid x by a
 //                    butterfly of shuffles, "some valid x refuses" and "the action's slot is a valid slot of this segment" as ballots, x_a read
-//                    from the lane that owns it, then in one more butterfly the sum of exponentials and the sum of e (x - m) -- the sums of
-//                    k_sample_actions in its order, so that the two kernels round alike;
+//                    from the lane that owns it, then in one more butterfly the sum of exponentials and the sum of e (x - m) -- the one
+//                    row_agent_sums k_sample_actions runs, so the two kernels round alike;
 //                 3. lanes 0..19 store one of the row's twenty aux words each; a refused agent ORs LP_REFUSED into the fault word.
 //   k_logp_bwd  cc4_logp_actions_grad_device: the same lane layout, elementwise.  The row's 5 actions, 20 aux words and 10 g words are wave-uniform
 //               (scalar loads, no reduction anywhere); a lane picks its agent's by compares against the segment offsets -- which of the five a
@@ -17,19 +17,12 @@
 #include <hip/hip_runtime.h>
 #include "cc4_logp.h"
 #include "cc4_elem.h"
+#include "cc4_row_wave.h"
 #include "cc4_kernel_decls.h"
 
 static_assert(LP_REFUSED == CC4_LOGP_REFUSED && SA_SLOTS == CC4_MASK_PER_ENV && NBLUE == CC4_NUM_BLUE, "include/cc4.h states the bit and the shapes");
-constexpr int LP_ROUNDS = (SA_SLOTS + WAVE - 1) / WAVE;      // slots per lane
-static_assert(LP_ROUNDS == 9 && NBLUE * LP_AUX <= WAVE, "the lanes of step 1 and 3");
-// no slot of agent b among the 64 of round j
-__host__ __device__ constexpr bool lp_round_misses(int j, int b) { return WAVE * j + WAVE - 1 < sa_off(b) || WAVE * j >= sa_off(b) + sa_len(b); }
+static_assert(NBLUE * LP_AUX <= WAVE, "the lanes of step 3");
 
-__device__ __forceinline__ float lp_wave_max(float v) {
-#pragma unroll
-  for (int d = 1; d < WAVE; d <<= 1) { const float o = __shfl_xor(v, d); v = o > v ? o : v; }
-  return v;
-}
 // the row of this wavefront, wave-uniform to the compiler too; -1: none
 __device__ __forceinline__ int lp_row(int n) {
   const int r = (int)blockIdx.x * LP_WAVES + __builtin_amdgcn_readfirstlane((int)threadIdx.x / WAVE);
@@ -39,25 +32,19 @@ __device__ __forceinline__ int lp_row(int n) {
 template <int DT>
 __device__ __forceinline__ void logp_fwd_row(const void* __restrict__ logits, const uint8_t* __restrict__ mask, const int32_t* __restrict__ actions, int row,
                                              int lane, float inv_t, float* __restrict__ aux, int32_t* __restrict__ fault) {
-  using E = typename LpElem<DT>::type;
+  using E = typename Elem<DT>::type;
   const E* const lrow = static_cast<const E*>(logits) + (size_t)row * SA_SLOTS;
   const uint8_t* const mrow = mask + (size_t)row * SA_SLOTS;
   const int32_t* const arow = actions + (size_t)row * NBLUE;
 
-  // 1. this lane's slots: agent, validity, scaled logit
-  float x[LP_ROUNDS];
-  int ag[LP_ROUNDS];
-  uint32_t vmask = 0;
-#pragma unroll
-  for (int j = 0; j < LP_ROUNDS; ++j) {
-    const int f = lane + WAVE * j;
-    x[j] = 0.0f; ag[j] = 0;
-    if (f < SA_SLOTS) {
-      ag[j] = sa_agent(f);
-      const E raw = lrow[f];
-      if (mrow[f] != 0) { vmask |= 1u << j; x[j] = sa_x(lp_to_float<DT>(raw), inv_t); }
-    }
-  }
+  // 1. this lane's slots: agent, validity, scaled logit (the logit is loaded beside the mask byte, not behind it)
+  RowSlots r;
+  row_load(r, lane, [&](int, int f, float* x) {
+    const E raw = lrow[f];
+    if (mrow[f] == 0) return false;
+    *x = sa_x(elem_to_float<DT>(raw), inv_t);
+    return true;
+  });
 
   // 2. per agent
   float st = 0.0f;             // lanes 0 .. 19: aux word `lane`
@@ -70,37 +57,17 @@ __device__ __forceinline__ void logp_fwd_row(const void* __restrict__ logits, co
     if (!lp_skipped(a)) {
       const int fa = sa_off(b) + a;                                // the action's slot of the row, if it is one of the segment's
       const bool in_seg = a >= 0 && a < sa_len(b);
-      bool bad = false, hit = false;
-      float m = -sa_inf(), xa = 0.0f;
-#pragma unroll
-      for (int j = 0; j < LP_ROUNDS; ++j) {
-        if (lp_round_misses(j, b)) continue;
-        if (ag[j] == b && ((vmask >> j) & 1u)) {
-          bad = bad || sa_refuses(x[j]);
-          m = x[j] > m ? x[j] : m;
-          if (in_seg && lane + WAVE * j == fa) { hit = true; xa = x[j]; }
-        }
-      }
-      m = lp_wave_max(m);
-      if (__ballot(bad) != 0ull || m == -sa_inf() || __ballot(hit) == 0ull) {
+      bool hit = false;
+      float m, S, sx, xa = 0.0f;
+      const bool ok = row_agent_max(r, b, &m, [&](int j) {
+        if (in_seg && lane + WAVE * j == fa) { hit = true; xa = r.x[j]; }
+      });
+      if (!ok || __ballot(hit) == 0ull) {
         refused = true;
         lp_aux_empty(true, w);
       } else {
         xa = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(xa), fa & (WAVE - 1)));
-        float S = 0.0f, sx = 0.0f;
-#pragma unroll
-        for (int j = 0; j < LP_ROUNDS; ++j) {
-          if (lp_round_misses(j, b)) continue;
-          if (ag[j] != b || !((vmask >> j) & 1u)) continue;
-          const float d = x[j] - m, ex = expf(d);
-          S += ex;
-          sx += ex > 0.0f ? ex * d : 0.0f;
-        }
-#pragma unroll
-        for (int d = 1; d < WAVE; d <<= 1) {
-          S += __shfl_xor(S, d);
-          sx += __shfl_xor(sx, d);
-        }
+        row_agent_sums(r, b, m, &S, &sx, RowNoHook{}, RowNoHook{});
         lp_aux(xa, m, S, sx, w);
       }
     }
@@ -127,7 +94,7 @@ __global__ __launch_bounds__(LP_WAVES * WAVE) void k_logp_fwd(const void* __rest
 template <int DT>
 __device__ __forceinline__ void logp_bwd_row(const void* __restrict__ logits, const uint8_t* __restrict__ mask, const int32_t* __restrict__ actions, int row,
                                              int lane, float inv_t, const float* __restrict__ aux, const float* __restrict__ g, void* __restrict__ grad) {
-  using E = typename LpElem<DT>::type;
+  using E = typename Elem<DT>::type;
   const E* const lrow = static_cast<const E*>(logits) + (size_t)row * SA_SLOTS;
   E* const grow = static_cast<E*>(grad) + (size_t)row * SA_SLOTS;
   const uint8_t* const mrow = mask + (size_t)row * SA_SLOTS;
@@ -145,7 +112,7 @@ __device__ __forceinline__ void logp_bwd_row(const void* __restrict__ logits, co
     zero[b] = lp_skipped(a[b]) || lp_refused(m[b]);
   }
 #pragma unroll
-  for (int j = 0; j < LP_ROUNDS; ++j) {
+  for (int j = 0; j < ROW_ROUNDS; ++j) {
     const int f = lane + WAVE * j;
     if (f >= SA_SLOTS) continue;
     const int ab = sa_agent(f);
@@ -154,13 +121,13 @@ __device__ __forceinline__ void logp_bwd_row(const void* __restrict__ logits, co
     float pm = 0.0f, pls = 0.0f, pH = 0.0f, p0 = 0.0f, p1 = 0.0f;
 #pragma unroll
     for (int b = 0; b < NBLUE; ++b) {
-      if (lp_round_misses(j, b)) continue;
+      if (round_misses(j, b)) continue;
       if (ab == b) { fa = sa_off(b) + a[b]; z = zero[b]; pm = m[b]; pls = ls[b]; pH = H[b]; p0 = g0[b]; p1 = g1[b]; }
     }
     const E raw = lrow[f];
     float gr = 0.0f;
-    if (!z && mrow[f] != 0) gr = lp_grad(sa_x(lp_to_float<DT>(raw), inv_t), f == fa, pm, pls, pH, p0, p1, inv_t);
-    grow[f] = lp_from_float<DT>(gr);
+    if (!z && mrow[f] != 0) gr = lp_grad(sa_x(elem_to_float<DT>(raw), inv_t), f == fa, pm, pls, pH, p0, p1, inv_t);
+    grow[f] = elem_from_float<DT>(gr);
   }
 }
 

@@ -9,11 +9,13 @@ import ctypes
 import numpy as np
 import torch
 from . import _lib as L
+from . import _tensors as TS
 from . import _views as V
+from ._tensors import dptr as _dptr
 from .vec_env import CC4VecEnv, as_env_mask, as_ptr, as_seeds, raise_on_copy_faults, split_obs, split_mask  # noqa: F401  (split_obs / split_mask slice tensors too)
 
-_OBS_DTYPES = {torch.uint8: 0, torch.float16: 1, torch.bfloat16: 2, torch.float32: 3}
-_LOGIT_DTYPES = {torch.float16: 1, torch.bfloat16: 2, torch.float32: 3}      # the same codes: what sample_actions() takes
+_OBS_DTYPES = TS.torch_codes(torch, TS.OBS_DTYPE_CODES)
+_LOGIT_DTYPES = TS.torch_codes(torch)      # the same codes: what sample_actions() takes
 _TORCH_DTYPES = {np.dtype(np.uint8): torch.uint8, np.dtype(np.int32): torch.int32, np.dtype(np.float32): torch.float32}      # of the views' outputs
 
 
@@ -35,10 +37,6 @@ def seed_tensor(x, n, device, what='seeds'):
     if torch.is_tensor(x) and x.dtype == torch.uint64 and tuple(x.shape) == (n,) and x.device == device:
         return x.view(torch.int64).contiguous()
     return int_tensor(x, (n,), device, what, to=torch.int64)
-
-
-def _dptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
 def mask_tensor(x, n, device, what='env_mask'):
@@ -320,11 +318,9 @@ class CC4TorchVecEnv:
             a, b = (torch.empty(shp, dtype=dt, device=self.device) for shp, dt, _al in specs)
         else:
             a, b = out
-            for x, (shp, dt, al) in zip((a, b), specs):
-                if (not torch.is_tensor(x) or tuple(x.shape) != shp or x.dtype != dt or x.device != self.device or not x.is_contiguous()
-                        or x.data_ptr() % al):
-                    want = ', '.join(f'{str(dt_).replace("torch.", "")} {list(shp_)} (aligned to {al_} bytes)' for shp_, dt_, al_ in specs)
-                    raise ValueError(f'out must be contiguous tensors ({want}) on {self.device}')
+            for k, (x, (shp, dt, al)) in enumerate(zip((a, b), specs)):
+                if TS.check_tensor(torch, f'out[{k}]', x, shape=shp, dtypes=(dt,), device=self.device).data_ptr() % al:
+                    raise ValueError(f'out[{k}] must be aligned to {al} bytes')
         self._call(V.VIEWS[view].device, bp, cap, _dptr(ids), n, *extra, _dptr(a), _dptr(b))
         return a, b
 
@@ -378,9 +374,7 @@ class CC4TorchVecEnv:
         n = int(ids.numel()) if torch.is_tensor(ids) else (int(bank.shape[0]) if torch.is_tensor(bank) else self.num_envs)
         code, lp = 3, None
         if logits is not None:
-            if (not torch.is_tensor(logits) or tuple(logits.shape) != (n, L.MASK_PER_ENV) or logits.dtype not in _LOGIT_DTYPES
-                    or logits.device != self.device or not logits.is_contiguous()):
-                raise ValueError(f'logits must be a contiguous float16, bfloat16 or float32 tensor [{n}, {L.MASK_PER_ENV}] on {self.device}')
+            TS.check_tensor(torch, 'logits', logits, shape=(n, L.MASK_PER_ENV), dtypes=tuple(_LOGIT_DTYPES), device=self.device)
             code, lp = _LOGIT_DTYPES[logits.dtype], _dptr(logits)
         if t is None:
             t, self._sample_t = self._sample_t, self._sample_t + 1

@@ -8,6 +8,7 @@ import ctypes
 import numpy as np
 from . import _lib as L
 from . import _views as V
+from ._tensors import NUMPY_CODES
 
 RNG_PCG64 = 0    # numpy Generator(PCG64(SeedSequence(seed))): bit-exact with the reference under the same seed
 RNG_PHILOX = 1   # Philox4x32-10 keyed by seed, counter (draw, stream, step, episode)
@@ -606,7 +607,7 @@ class CC4VecEnv:
                 raise ValueError(f'logits must have shape ({n}, {L.MASK_PER_ENV}), got {lg.shape}')
             if lg.dtype == np.float64:
                 lg = lg.astype(np.float32)
-            code = {np.dtype(np.float16): 1, np.dtype(np.uint16): 2, np.dtype(np.float32): 3}.get(lg.dtype)
+            code = NUMPY_CODES.get(lg.dtype)
             if code is None:
                 raise ValueError(f'logits must be float16, float32 (or uint16: bfloat16 bit patterns), got {lg.dtype}')
             lg = np.ascontiguousarray(lg)

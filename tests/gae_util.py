@@ -9,21 +9,9 @@ evaluated in float64 along the reference; ret = adv + v adds one more rounding: 
 the one rounding of gamma lam) to first order."""
 import numpy as np
 
+from bf16_util import to_bits as to_bf16_bits, upcast  # noqa: F401  (test_gae_device reads both from here)
+
 U32 = 2.0 ** -24
-
-
-def upcast(arr):
-    """What an array of bfloat16 bit patterns (uint16), float16 or float32 carries, as float32 -- exactly."""
-    arr = np.asarray(arr)
-    if arr.dtype == np.uint16:
-        return (arr.astype(np.uint32) << np.uint32(16)).view(np.float32)
-    return arr.astype(np.float32)
-
-
-def to_bf16_bits(x):
-    """float32 -> bfloat16 bit patterns (uint16), rounded to nearest even (finite inputs)."""
-    u = np.ascontiguousarray(x, np.float32).view(np.uint32)
-    return ((u + np.uint32(0x7FFF) + ((u >> np.uint32(16)) & np.uint32(1))) >> np.uint32(16)).astype(np.uint16)
 
 
 def random_rollout(rng, T, N, A, done_rate=0.15, heads=1, none_rate=0.2, scale=50.0):

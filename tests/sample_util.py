@@ -8,6 +8,7 @@ max(1, max |z|): an error of about 10 * 2^-24 * max(1, max |z|), plus a few ulp 
 and entropy: |value - reference| <= 2^-12 * max(1, |reference|)."""
 import numpy as np
 
+from bf16_util import to_bits, upcast
 from cage_challenge_4_amd import action_sampling as AS
 from cage_challenge_4_amd import blue_view as BV
 
@@ -15,22 +16,13 @@ SEG = AS.SEGMENTS
 SLEEP = (49, 49, 49, 49, 145)          # the agents' Sleep slots (3 * hosts + 1): always valid
 
 
-def to_bf16(x):
-    """float32 values rounded to the nearest bfloat16 (ties to even), as float32, and their 16-bit patterns."""
-    u = np.ascontiguousarray(x, np.float32).view(np.uint32).astype(np.uint64)
-    r = ((u + np.uint64(0x7FFF) + ((u >> np.uint64(16)) & np.uint64(1))) >> np.uint64(16)).astype(np.uint16)
-    nan = np.isnan(x)
-    r = np.where(nan, np.uint16(0x7FC0), r)
-    return (r.astype(np.uint32) << np.uint32(16)).view(np.float32).reshape(np.shape(x)), r.reshape(np.shape(x))
-
-
 def value_sets(lg):
     """lg float32 [.., 570] -> {dtype code: (the float32 values that dtype carries, the array to hand the device)}: 3 float32, 2 bfloat16 (uint16
     bit patterns), 1 float16."""
-    bf, bits = to_bf16(lg)
+    bits = to_bits(lg)
     with np.errstate(over='ignore'):
         h = lg.astype(np.float16)
-    return {3: (lg, lg), 2: (bf, bits), 1: (h.astype(np.float32), h)}
+    return {3: (lg, lg), 2: (upcast(bits), bits), 1: (h.astype(np.float32), h)}
 
 
 def busy_of(hot, steps=0):

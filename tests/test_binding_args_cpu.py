@@ -77,6 +77,13 @@ def test_view_modules_keep_their_constants():
     assert (reward_terms.SUBNETS, reward_terms.COLS, reward_terms.NWORDS) == (9, 4, 16) and len(reward_terms.WORDS) == 16
     assert action_sampling.SEGMENTS == (0, 82, 164, 246, 328, 570) and action_sampling.SLOTS == 570
     assert action_sampling.noise_words(-1, 2 ** 32 + 5) == (2 ** 64 - 1, 5)
+    # the dtype codes: one table (include/cc4.h: "1 float16, 2 bfloat16, 3 float32", 0 the observations' bytes), and the modules' names for it
+    from cage_challenge_4_amd import _tensors, action_logp, advantages
+    assert _tensors.DTYPE_CODES == {'float16': 1, 'bfloat16': 2, 'float32': 3} and _tensors.OBS_DTYPE_CODES == dict(_tensors.DTYPE_CODES, uint8=0)
+    assert action_logp.DTYPE_CODES is _tensors.DTYPE_CODES and advantages.DTYPE_CODES is _tensors.DTYPE_CODES
+    assert _tensors.NUMPY_CODES == {np.dtype(np.float16): 1, np.dtype(np.uint16): 2, np.dtype(np.float32): 3}
+    by_code = sorted(_tensors.OBS_DTYPE_CODES.items(), key=lambda kc: kc[1])
+    assert 'obs_dtype ' + ', '.join(f'{c} {k}' for k, c in by_code) in open(os.path.join(ROOT, 'include', 'cc4.h')).read()
 
 
 def _check_layout(parts):

@@ -11,6 +11,7 @@ import pytest
 
 import logp_util as LU
 import sample_util as U
+from bf16_util import upcast
 from cage_challenge_4_amd import action_logp as AL
 from view_util import DevMem
 
@@ -24,13 +25,6 @@ ITEM = {3: 4, 2: 2, 1: 2}
 def _lib():
     from cage_challenge_4_amd import _lib
     return _lib.load()
-
-
-def _values(arr, code):
-    """What a device array of dtype `code` carries, as float32."""
-    if code == 2:
-        return (arr.astype(np.uint32) << np.uint32(16)).view(np.float32)
-    return arr.astype(np.float32)
 
 
 def _run(dev_logits, code, mask, act, T, g, fill=0x5A):
@@ -53,7 +47,7 @@ def _run(dev_logits, code, mask, act, T, g, fill=0x5A):
     aux = d_aux.down(np.float32, (n, 5, 4))
     raw = d_grad.down(np.uint8, d_grad.nbytes)
     assert (raw[:it] == fill).all(), 'the element in front of the gradient was written'
-    grad = _values(raw[it:].copy().view({3: np.float32, 2: np.uint16, 1: np.float16}[code]).reshape(n, 570), code)
+    grad = upcast(raw[it:].copy().view({3: np.float32, 2: np.uint16, 1: np.float16}[code]).reshape(n, 570))
     fault = int(d_fault.down(np.int32, 1)[0])
     for m in (d_lg, d_mk, d_ac, d_aux, d_g, d_grad, d_fault):
         m.free()

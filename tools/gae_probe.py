@@ -14,9 +14,7 @@ tensors in the same job; the builds of the kernel (wavefronts per workgroup, row
                  kernel's own duration per dispatch (package build only), quoted beside the event times
 A run needs a GPU; without one it fails."""
 import argparse
-import csv
 import ctypes
-import glob
 import json
 import os
 import sys
@@ -26,6 +24,8 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from cage_challenge_4_amd._tensors import ELEM_BYTES      # noqa: E402
+from trace_util import kernel_times      # noqa: E402
 
 TS, NS, A = (20, 128, 500), (1024, 8192), 5
 GAMMA, LAM, FLAGS = 0.99, 0.95, 3
@@ -34,7 +34,7 @@ PEAK = 8.0e12
 VP = ctypes.c_void_p
 
 
-def bytes_per_call(T, N, a=A, elt=2):
+def bytes_per_call(T, N, a=A, elt=ELEM_BYTES['bfloat16']):
     """What one call must move: values, actions in; adv, ret, weight out; rewards and dones per episode; last and done0 once."""
     return T * N * a * (elt + 4 + 4 + 4 + 1) + T * N * (4 + 1) + N * a * elt + N
 
@@ -155,15 +155,6 @@ def run(a):
     report(res, a)
 
 
-def kernel_times(trace_dir):
-    files = sorted(glob.glob(os.path.join(trace_dir, '**', '*kernel_trace.csv'), recursive=True))
-    if len(files) != 1:
-        raise SystemExit(f'expected one *kernel_trace.csv under {trace_dir}, found {files}')
-    rows = [r for r in csv.DictReader(open(files[0])) if 'k_gae' in r['Kernel_Name']]
-    rows.sort(key=lambda r: int(r['Start_Timestamp']))
-    return [(int(r['End_Timestamp']) - int(r['Start_Timestamp'])) / 1000.0 for r in rows]
-
-
 def report(res, a):
     names = list(res['libs'])
     lines = ['# tools/gae_probe.py: cc4_gae_device (k_gae) on one MI355X against the same definition as a PyTorch loop (reverse over T, torch.where); A = 5 heads, '
@@ -172,7 +163,7 @@ def report(res, a):
              'median (min .. max) us per call.  PyTorch: wall clock of the loop + one synchronise, fastest of three, float32 values',
              '# bytes per call from the shapes (values, actions in; adv, ret, weight out; rewards, dones per episode); fraction of 8 TB/s at the median',
              '# builds: ' + ', '.join(f'{n} (GAE_ROWS {r})' for n, r in res['libs'].items())]
-    trace = kernel_times(a.trace) if a.trace else None
+    trace = kernel_times(a.trace, 'k_gae') if a.trace else None
     per = WARM + TRACE_REPS
     for j, (key, c) in enumerate(res['cases'].items()):
         T, N = (int(x) for x in key.split())

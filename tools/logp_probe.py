@@ -16,8 +16,6 @@ bfloat16 and float32 logits; the masks and the stored actions come from a counte
 Bytes the kernels must move per row, from the shapes: forward 570 logits in their dtype, 570 mask bytes, 5 x 4 action bytes in, 20 x 4 aux bytes
 out; backward the same inputs, the aux and 10 x 4 g bytes in, 570 gradient values in the logits' dtype out."""
 import argparse
-import csv
-import glob
 import json
 import os
 import sys
@@ -27,10 +25,11 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from cage_challenge_4_amd._tensors import ELEM_BYTES      # noqa: E402
+from cage_challenge_4_amd.action_sampling import SEGMENTS as SEG      # noqa: E402
+from trace_util import kernel_times      # noqa: E402
 
 ROWS, DTYPES, WARM = (8192, 32768), ('bfloat16', 'float32'), 3
-SEG = (0, 82, 164, 246, 328, 570)
-ELT = {'bfloat16': 2, 'float32': 4}
 
 
 def torch_chain(torch, logits, mask, actions):
@@ -110,15 +109,6 @@ def run(a):
     print(res)
 
 
-def kernel_times(trace_dir, name):
-    files = sorted(glob.glob(os.path.join(trace_dir, '**', '*kernel_trace.csv'), recursive=True))
-    if len(files) != 1:
-        raise SystemExit(f'expected one *kernel_trace.csv under {trace_dir}, found {files}')
-    rows = [r for r in csv.DictReader(open(files[0])) if name in r['Kernel_Name']]
-    rows.sort(key=lambda r: int(r['Start_Timestamp']))
-    return [(int(r['End_Timestamp']) - int(r['Start_Timestamp'])) / 1000.0 for r in rows]
-
-
 def report(a):
     c = json.load(open(a.calls))
     k, per = c['steps'], WARM + c['reps']
@@ -135,7 +125,7 @@ def report(a):
              f'# kernel us: rocprofv3 --kernel-trace --stats in a run of its own (no counters), median of {c["reps"]} dispatches on the same rows; (min .. max); '
              'bytes per row from the shapes']
     for j, (n, dt) in enumerate(cases):
-        e = ELT[dt]
+        e = ELEM_BYTES[dt]
         for kern, b in (('k_logp_fwd', 570 * e + 570 + 20 + 80), ('k_logp_bwd', 2 * 570 * e + 570 + 20 + 80 + 40), ('k_sample_actions', None)):
             m, lo, hi = stat(times[kern][j * per:(j + 1) * per])
             tail = f'   {b:5d} B per row   {b * n / (m * 1e-6) / 1e12:5.2f} TB/s' if b else ''

@@ -18,8 +18,6 @@ against the same loop with the sampling written in PyTorch.  8192 episodes, coun
 Bytes k_sample_actions must move per entry, from the shapes: 570 logits in their dtype, of the hot row the 20 bytes of exists and the five busy
 bytes, and 5 x 4 + 10 x 4 output bytes."""
 import argparse
-import csv
-import glob
 import json
 import os
 import sys
@@ -29,9 +27,11 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from cage_challenge_4_amd._tensors import ELEM_BYTES      # noqa: E402
+from cage_challenge_4_amd.action_sampling import SEGMENTS as SEG      # noqa: E402
+from trace_util import kernel_times      # noqa: E402
 
 N, WARM = 8192, 3
-SEG = (0, 82, 164, 246, 328, 570)
 VARIANTS = ('float32', 'bfloat16', 'float16', 'none')
 ROW_READ, OUT_BYTES = 20 + 5, 5 * 4 + 10 * 4
 
@@ -120,15 +120,6 @@ def run(a):
     print(res)
 
 
-def kernel_times(trace_dir, name):
-    files = sorted(glob.glob(os.path.join(trace_dir, '**', '*kernel_trace.csv'), recursive=True))
-    if len(files) != 1:
-        raise SystemExit(f'expected one *kernel_trace.csv under {trace_dir}, found {files}')
-    rows = [r for r in csv.DictReader(open(files[0])) if name in r['Kernel_Name']]
-    rows.sort(key=lambda r: int(r['Start_Timestamp']))
-    return [(int(r['End_Timestamp']) - int(r['Start_Timestamp'])) / 1000.0 for r in rows]
-
-
 def report(a):
     c = json.load(open(a.calls))
     n, k, per = c['n'], c['steps'], WARM + c['reps']
@@ -146,7 +137,7 @@ def report(a):
              f'# kernel us: rocprofv3 --kernel-trace --stats in a run of its own (no counters), median of {c["reps"]} dispatches on the same rows; (min .. max)']
     for j, name in enumerate(VARIANTS):
         m, lo, hi = stat(tail[j::4])
-        elt = {'float32': 4, 'bfloat16': 2, 'float16': 2, 'none': 0}[name]
+        elt = ELEM_BYTES.get(name, 0)      # (none: no logits)
         b = 570 * elt + ROW_READ + OUT_BYTES
         lines.append(f'  k_sample_actions, logits {name:9s} {m:7.1f} us  ({lo:.1f} .. {hi:.1f})   {b:5d} B per episode from the shapes ({OUT_BYTES} B out)   '
                      f'{b * n / (m * 1e-6) / 1e12:5.2f} TB/s')
